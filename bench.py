@@ -2,7 +2,7 @@
 """bench.py -- edges/sec per GNN layer (fwd+bwd) on the synthetic ncRNA-protein bipartite graph.
 
 Contract: `python bench.py --gpus N --steps K --warmup W`; rank 0's LAST stdout line is ONE compact strict-JSON object
-(< 8 KB: metric, value, roofline, cpu_baseline, parity, one number per side config); everything longer -- per-tensor tables,
+(< 8 KB: metric, value, ms_per_step; with --full also roofline, cpu_baseline, parity, one number per side config); everything longer -- per-tensor tables,
 per-rank arrays, prose -- goes to `bench_detail.json` in the working directory.  For N > 1 the driver launches
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`; a plain `python bench.py --gpus N` (no
 WORLD_SIZE in the environment) starts exactly that command itself as a child process BEFORE anything in this process touches
@@ -14,10 +14,13 @@ and the graph already resident in HBM.  Workload = BASELINE.json configs[3] ("C4
 hidden = 256, fp32 -- it fits one GPU, so N=1 runs the full graph; N>1 shards the same graph (strong scaling;
 npi_gnn_amd/dist.py, --partition).
 
-The default N=1 run: graph build, 40 + W + K steps, the roofline block (live HIP-event durations of the aggregation launches),
-the parity of exactly what was timed (every row of out / dX and dW, db against the formulas in fp64 torch ops), the
-cache-hostile control, one number per other BASELINE config inside a wall-clock budget, and the CPU path on the host cores.
-`--extras` adds the lab harness (tools/bench_extras.py: per-head sweeps, the virtual worlds of every partition, the emulated
+The plain run: graph build, 40 + W + K steps, the line.  `--dump-outputs DIR` writes what the last timed step computed
+(out, dX, dW, db; a fixed row sample of the large ones) as .npy files.  `--full` adds, for N=1: the roofline block (live
+HIP-event durations of the aggregation launches in K more steps after the timed ones, PMC bytes from child passes), two repeat
+regions of K steps, the parity of the timed path (every row of out / dX and dW, db of the last repeat step against the
+formulas in fp64 torch ops), the cache-hostile control, one number per other BASELINE config inside a wall-clock budget, and
+the CPU path on the host cores.
+`--extras` (implies --full) adds the lab harness (tools/bench_extras.py: per-head sweeps, the virtual worlds of every partition, the emulated
 wire, the C5 stack in its 8-rank form with its parity) -- detail file only.
 
 N > 1: every rank launched by torch.distributed.run is a SUPERVISOR that never touches the GPU; it starts the rank's worker as
@@ -100,9 +103,22 @@ def parse(argv=None):
     ap.add_argument("--setup-steps", type=int, default=SETUP_STEPS, help="untimed steps before the warm-up")
     ap.add_argument("--detail-file", default=DETAIL_FILE,
                     help="where the full record goes ('' = nowhere; the live PMC child passes write none)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the live PMC passes, the roofline / projection / exchange figures "
+                         "(HIP events around every launch of K more steps after the timed ones), two repeat regions, the parity check, the control, the "
+                         "per-config summary, the virtual worlds and the CPU baseline.  Without it a run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (out, grad_x and every parameter "
+                         "gradient; a fixed seeded sample of rows where a tensor is large) as DIR/<name>.npy, float32")
     ap.add_argument("--rank-check", action="store_true",
                     help="every rank prints {rank, world} and exits before any GPU call (launcher test)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.extras:                       # the lab harness is part of the full record
+        args.full = True
+    if not args.full:                     # a plain run: the headline figure only
+        args.no_live_pmc = args.no_control = args.no_configs = args.no_parity = args.no_cpu_baseline = True
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -552,7 +568,7 @@ def timed_config_parity(ei_dev, N, x, go, conv, out, chunk=2_000_000):
     err = {"out": rel(out, want_out), "dX": rel(x.grad, want_dx), "dW": rel(conv.weight.grad, want_dw),
            "db": rel(conv.bias.grad, want_db)}
     return {"parity_max_err": max(err.values()), "by_tensor": err,
-            "against": f"every row of out / dX and dW, db of the last timed step (the conv on the CSR the timed region used) against "
+            "against": f"every row of out / dX and dW, db of the last step of the timed path (the conv on the CSR the timed region used) against "
                        "mean-aggregate @ W + b and its transpose evaluated in fp64 torch ops over the original edge list; max |diff| / "
                        "max |reference|"}
 
@@ -720,7 +736,8 @@ def compact_line(res: dict) -> str:
                                     "frac_traffic": _num(cu.get("frac_traffic"), 4),
                                     "frac": _num(cu.get("frac_traffic") or cu.get("frac_algorithmic"), 4),
                                     "what": "same kernel, sources and targets uniform over all rows (nothing cache-resident)"})
-    line["roofline"] = roof
+    if r:                                                       # (a plain run measures no roofline)
+        line["roofline"] = roof
     pj = res.get("projection")
     if isinstance(pj, dict):
         line["projection"] = {"bound": "mfma", "achieved": _num(pj.get("achieved"), 5), "peak": pj.get("peak"), "unit": "TFLOP/s",
@@ -765,6 +782,44 @@ def emit(res: dict, detail_file: str = DETAIL_FILE) -> None:
         res["detail"] = None
     sys.stdout.flush()
     print(compact_line(res), flush=True)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path hands its caller, for comparing two builds output for output
+# ---------------------------------------------------------------------------------------------------------
+DUMP_BUDGET = 60 << 20                # bytes over all files of a run (every rank's together), under 64 MiB
+DUMP_SEED = 1234                      # the row sample of a tensor too large to write whole
+
+
+def step_outputs(out, x, module) -> dict:
+    """the layer's output, dL/dx and every parameter's gradient after the last step"""
+    res = {"out": out, "grad_x": x.grad}
+    for name, p in module.named_parameters():
+        res["grad_" + name.replace(".", "_")] = p.grad
+    return res
+
+
+def dump_outputs(dirname: str, tensors: dict, rank: int = 0, world: int = 1) -> dict:
+    """Write every tensor as float32 `<name>.npy` (`rank<r>_<name>.npy` for N > 1).  A tensor above its share of DUMP_BUDGET is
+    written as a sorted sample of its rows drawn from DUMP_SEED: the same rows in every run of the same arguments.
+    Returns {name: rows written or None if whole}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    tensors = {k: v for k, v in tensors.items() if v is not None}
+    share = DUMP_BUDGET // (max(len(tensors), 1) * world)
+    written = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        rows = None
+        if t.numel() * 4 > share and t.dim() >= 1:
+            keep = max(1, share // (4 * max(t[0].numel(), 1)))
+            idx = torch.randperm(t.size(0), generator=torch.Generator().manual_seed(DUMP_SEED))[:keep].sort().values
+            t = t.index_select(0, idx.to(t.device))
+            rows = int(idx.numel())
+        a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(dirname, (f"rank{rank}_" if world > 1 else "") + name + ".npy"), a)
+        written[name] = rows
+    return written
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -846,6 +901,7 @@ def main():
         _ = graph.by_src
         torch.cuda.synchronize()
         t_build = time.time() - t0
+        torch.manual_seed(args.graph_seed)  # what W / bias do not overwrite (GATConv's att) is the same in every run
         conv = {"sage": npi.SAGEConv, "gcn": npi.GCNConv, "gat": npi.GATConv}[args.conv](F, F).to(dev)
         with torch.no_grad():
             conv.weight.copy_(W)
@@ -914,6 +970,7 @@ def main():
             x.grad = None
             out = layer(x)
             out.backward(go)
+            last["out"] = out.detach()
 
         # Set-up phase.  Anything that raises here ends THIS process with a non-zero code (the error in err_<attempt>_<rank>): the
         # supervisors then end every rank's worker and start fresh ones on the conservative schedule.  No rank tries to recover
@@ -1001,25 +1058,36 @@ def main():
         captured = True
         step()
         barrier()
-    NF._PROFILE = seg_events if not captured else None
-    NF._PROFILE_GEMM = gemm_events if not captured else None
     comm_events = []                      # (tag, start, end) around every wait on a collective (sharded path only)
     if sharded:
         from npi_gnn_amd import dist as ND_
-        ND_._COMM_PROFILE = comm_events
+    # the timed region: the layer as its caller runs it, no per-launch hooks -- the same path in a plain and a --full run
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     barrier()
     dt = time.perf_counter() - t0
-    NF._PROFILE = None
-    NF._PROFILE_GEMM = None
-    if sharded:
-        ND_._COMM_PROFILE = None
-    # two more regions of exactly K steps, reported BESIDE the contract's measurement (never instead of it): the spread says
-    # whether the timed region met a quiet GPU (one run of this bench on a shared box measured 9.7 ms between two of 7.0)
+    if args.dump_outputs:                 # the last timed step's results, before anything else runs the layer again
+        dump_outputs(args.dump_outputs, step_outputs(last["out"], x, conv if not sharded else layer), rank, world)
+    # --full: K more steps with HIP events around every aggregation launch, projection GEMM and wait on a collective (the
+    # roofline, projection and exchange figures); with the hooks on, the layers issue their launches one call at a time
+    if args.full and not captured:
+        NF._PROFILE = seg_events
+        NF._PROFILE_GEMM = gemm_events
+        if sharded:
+            ND_._COMM_PROFILE = comm_events
+        for _ in range(args.steps):
+            step()
+        barrier()
+        NF._PROFILE = None
+        NF._PROFILE_GEMM = None
+        if sharded:
+            ND_._COMM_PROFILE = None
+    # --full: two more regions of exactly K steps, reported BESIDE the contract's measurement (never instead of it): the spread says
+    # whether the timed region met a quiet GPU (one run of this bench on a shared box measured 9.7 ms between two of 7.0); the
+    # parity check below then reads the last of them, a step of the timed path
     repeats = []
-    if world == 1:
+    if world == 1 and args.full:
         for _ in range(2):
             barrier()
             r0 = time.perf_counter()
@@ -1036,7 +1104,7 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = E * args.steps / dt
     parity = None
-    if sharded:
+    if sharded and args.full:
         try:
             parity = sharded_parity(dev, args, world, sg, layer, x, go, ei, x_full, go_full, W, bias,
                                     att=att_full if args.conv == "gat" and args.partition != "edges" else None)
@@ -1179,6 +1247,9 @@ def main():
                 "note": "bwd_weight (gemm_dw_split_kernel: both operands split on the fly) is timed while it shares the CUs "
                         "with the backward aggregation on a second stream; alone it takes 0.93 ms"},
         }
+        if not args.full:                 # measured from the profiled timed steps of a --full run only
+            for k in ("roofline", "exchange", "aggregation_only", "projection"):
+                del res[k]
         if parity is not None:
             res["parity_max_err"] = parity["parity_max_err"]
             res["parity"] = parity

@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -136,3 +138,107 @@ def test_a_failed_first_attempt_restarts_every_rank_as_a_fresh_worker(tmp_path):
     assert "starting a fresh worker" in outs[0][1] and "starting a fresh worker" in outs[1][1]
     names = sorted(os.listdir(tmp_path / "rdv"))
     assert {"fail_0_0", "fail_0_1", "err_0_1", "ok_1_0", "ok_1_1"} <= set(names), names       # (ok_0_0 only if rank 0 got that far in time)
+
+
+# ---- a plain run does only the headline; --full adds the side measurements ---------------------------------------------------
+def test_plain_run_turns_the_side_measurements_off_and_full_keeps_them():
+    sys.path.insert(0, ROOT)
+    import bench
+    plain = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert plain.steps == 7 and not plain.full and plain.dump_outputs is None
+    assert plain.no_live_pmc and plain.no_control and plain.no_configs and plain.no_parity and plain.no_cpu_baseline
+    full = bench.parse(["--full"])
+    assert full.full and not (full.no_live_pmc or full.no_control or full.no_configs or full.no_parity or full.no_cpu_baseline)
+    assert bench.parse(["--extras"]).full                        # the lab harness is part of the full record
+    assert not bench.parse(["--full", "--no-parity"]).no_control and bench.parse(["--full", "--no-parity"]).no_parity
+
+
+def test_a_line_without_side_measurements_has_no_roofline_block():
+    sys.path.insert(0, ROOT)
+    import bench
+    rec = {k: v for k, v in _fat_record().items() if k not in ("roofline", "projection", "aggregation_only", "exchange", "configs",
+                                                             "cpu_baseline", "parity", "parity_max_err")}
+    got = json.loads(bench.compact_line(rec))
+    assert "roofline" not in got and got["ms_per_step"] == 6.640757 and got["value"] == 3011704000.0
+    assert got["metric"] == "edges/sec per GNN layer (fwd+bwd)" and got["higher_is_better"] is True and got["dtype"] == "f32"
+
+
+def test_dump_outputs_writes_float32_files_within_the_budget_with_the_same_sample_every_time(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    big = torch.randn(200_000, 64, generator=g)                  # 51 MB: above its share of the budget
+    t = {"out": big, "grad_x": big.to(torch.bfloat16), "grad_weight": torch.randn(64, 64, generator=g), "grad_bias": None}
+    rows = bench.dump_outputs(str(tmp_path / "a"), t)
+    assert set(rows) == {"out", "grad_x", "grad_weight"} and rows["grad_weight"] is None and 0 < rows["out"] < 200_000
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 64 << 20
+    a = np.load(tmp_path / "a" / "out.npy")
+    assert a.dtype == np.float32 and a.shape == (rows["out"], 64)
+    assert np.array_equal(np.load(tmp_path / "a" / "grad_weight.npy"), t["grad_weight"].numpy())
+    bench.dump_outputs(str(tmp_path / "b"), t)
+    assert np.array_equal(np.load(tmp_path / "b" / "out.npy"), a)
+    # the sample is a set of whole rows of the tensor, in row order
+    idx = torch.randperm(200_000, generator=torch.Generator().manual_seed(bench.DUMP_SEED))[:rows["out"]].sort().values
+    assert np.array_equal(a, big[idx].numpy())
+    bench.dump_outputs(str(tmp_path / "c"), {"out": big}, rank=1, world=2)
+    assert os.listdir(tmp_path / "c") == ["rank1_out.npy"]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_steps_outputs(dev, tmp_path):
+    """the driver's command on a small graph: the contract's keys, no side measurements, the outputs of the last timed step"""
+    import numpy as np
+    import torch
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    lines = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--nodes", "200000", "--edges", "4000000", "--detail-file", "", "--dump-outputs", str(tmp_path / d)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines.append(json.loads(p.stdout.strip().splitlines()[-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and abs(line["value"] - 4_000_000 * 1e3 / line["ms_per_step"]) < 1e-3 * line["value"]
+    assert "roofline" not in line and "cpu_baseline" not in line and "parity_max_err" not in line and line["ms_per_step_repeats"] == []
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["grad_bias.npy", "grad_weight.npy", "grad_x.npy", "out.npy"], names
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and a.shape == b.shape and np.isfinite(a).all()
+        assert np.allclose(a, b, rtol=1e-4, atol=1e-5), n           # same inputs in both runs
+    assert np.load(tmp_path / "a" / "grad_weight.npy").shape == (256, 256)
+    assert np.load(tmp_path / "a" / "out.npy").shape[1] == 256
+    # what was written is the layer's result: the SAGEConv formulas in fp64 torch ops on bench.py's inputs, at the sampled rows
+    sys.path.insert(0, ROOT)
+    import bench
+    from npi_gnn_amd.synth import bipartite_edge_index
+    N, E, F = 200_000, 4_000_000, 256
+    ei = bipartite_edge_index(N, E, seed=20260310).to(dev)
+    g = torch.Generator().manual_seed(1)                         # the draws of bench.main(), in its order
+    x = torch.randn(N, F, generator=g).to(dev).double()
+    W = ((torch.rand(F, F, generator=g) * 2 - 1) / F ** 0.5).to(dev).double()
+    b = ((torch.rand(F, generator=g) * 2 - 1) / F ** 0.5).to(dev).double()
+    go = torch.randn(N, F, generator=g).to(dev).double()
+    src, dst = ei[0], ei[1]
+    keep = src != dst                                            # existing self loops dropped, one added per row
+    cnt = (torch.bincount(dst[keep], minlength=N) + 1).double().view(-1, 1)
+
+    def spread(table, frm, to, chunk=500_000):                  # table + sum over the kept edges of table[frm[e]] into to[e]
+        acc = table.clone()
+        for lo in range(0, frm.numel(), chunk):
+            k = keep[lo: lo + chunk]
+            acc.index_add_(0, to[lo: lo + chunk][k], table[frm[lo: lo + chunk][k]])
+        return acc
+    agg = spread(x, src, dst) / cnt
+    want = {"out": agg @ W + b, "grad_weight": agg.t() @ go, "grad_bias": go.sum(0),
+            "grad_x": spread((go @ W.t()) / cnt, dst, src)}
+    for n, ref in want.items():
+        got = torch.from_numpy(np.load(tmp_path / "a" / (n + ".npy"))).double().to(dev)
+        if got.shape != ref.shape:                               # a row sample: the rows bench.dump_outputs draws
+            idx = torch.randperm(N, generator=torch.Generator().manual_seed(bench.DUMP_SEED))[:got.size(0)].sort().values
+            ref = ref[idx.to(dev)]
+        err = float((got - ref).abs().max() / ref.abs().max())
+        assert err <= 1e-5, f"{n}: {err} of its largest entry away from the fp64 formula"

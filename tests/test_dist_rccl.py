@@ -152,7 +152,7 @@ def test_bench_checks_its_own_output_for_more_than_one_gpu(partition, conv):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
                         "--nodes", "200000", "--edges", "4000000", "--partition", partition, "--conv", conv,
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]
     assert line["n_gpus"] == world
@@ -165,7 +165,7 @@ def test_bench_parity_block_with_one_rank_through_the_sharded_code(dev):
     for partition, conv in (("hubs", "sage"), ("edges", "sage"), ("hubs", "gat")):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-sharded", "--steps", "2", "--warmup", "1",
                             "--nodes", "200000", "--edges", "4000000", "--partition", partition, "--conv", conv,
-                            "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                            "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stderr[-3000:]
         line = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]
         assert line["parity_max_err"] is not None and line["parity_max_err"] < 1e-5, line.get("parity")
@@ -181,7 +181,7 @@ def test_bench_rehearsal_of_the_node_run_on_one_gpu(dev):
     env["NPI_BENCH_RCCL_SOLO"] = "1"
     for conv in ("sage", "gat"):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-sharded", "--steps", "2", "--warmup", "1",
-                            "--nodes", "200000", "--edges", "4000000", "--conv", conv, "--no-cpu-baseline"],
+                            "--nodes", "200000", "--edges", "4000000", "--conv", conv, "--no-cpu-baseline", "--full"],
                            env=env, capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stderr[-3000:]
         line = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -204,7 +204,7 @@ def test_bench_falls_back_to_the_conservative_schedule_when_its_preflight_step_f
     for inject in ("1", "0"):
         env["NPI_BENCH_INJECT_FAILURE"] = inject
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-sharded", "--nodes", "200000", "--edges",
-                            "4000000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+                            "4000000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"],
                            env=env, capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stderr[-2000:]
         line = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")][-1]

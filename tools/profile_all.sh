@@ -7,7 +7,7 @@
 #   -> profiles/<tag>[_gat|_c5|_gcn|_bf16]_kernel_stats.csv, <tag>*_pmc_summary.json, <tag>_control_*  (tools/rocprof_summary.py)
 #   -> profiles/pmc_traffic.json: HBM-side bytes per aggregation launch + the sha of the kernel sources they were measured on
 #   -> profiles/<tag>_mfma_util.json: SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE of the two projection kernels (tools/gemm_pair.py)
-# then the bench itself: the driver's command -> profiles/<tag>_bench_line.json (the compact line; bench.py reads
+# then the bench itself: `bench.py --full` -> profiles/<tag>_bench_line.json (the compact line; bench.py reads
 # pmc_traffic.json: frac_traffic is current again) and `bench.py --extras` -> profiles/<tag>_bench.json (the full record).
 cd "${GRAFT_REPO_ROOT:-$(pwd)}" || exit 1
 export TMPDIR=/tmp
@@ -32,9 +32,8 @@ python tools/mfma_util_summary.py "$(find gpurun_out/prof_${T}_mfma -name '*coun
 rm -rf gpurun_out/prof_${T}_mfma
 cat profiles/pmc_traffic.json
 rm -rf gpurun_out/prof_${T} gpurun_out/prof_${T}_c5 gpurun_out/prof_${T}_gat gpurun_out/prof_${T}_gcn gpurun_out/prof_${T}_bf16 gpurun_out/prof_${T}_control
-# the driver's command first (the compact line as the driver will see it), then the lab harness (--extras: the full record)
-python bench.py --steps 20 --warmup 5 > gpurun_out/${T}_bench_line.json 2> gpurun_out/${T}_bench_line.err; echo "bench rc=$?"
-cp gpurun_out/${T}_bench_line.json profiles/${T}_bench_line.json
+# the compact line with the side measurements first (--full: roofline, projection, parity, ...), then the lab harness (--extras)
+python bench.py --full --steps 20 --warmup 5 > profiles/${T}_bench_line.json; echo "bench --full rc=$?"
 timeout 1700 python bench.py --extras > gpurun_out/${T}_bench_extras_line.json 2> gpurun_out/${T}_bench.err; echo "bench --extras rc=$?"
 cp bench_detail.json gpurun_out/${T}_bench.json; cp bench_detail.json profiles/${T}_bench.json
 mkdir -p gpurun_out/profiles_${T}; cp profiles/${T}* profiles/pmc_traffic.json gpurun_out/profiles_${T}/

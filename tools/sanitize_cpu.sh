@@ -20,12 +20,12 @@ for f in $(cd "$ROOT" && python3 -c "from npi_gnn_amd.build import SOURCES; prin
   # files took 4-5 minutes of every CPU test run
   KEY="$HDR $(sha256sum "$ROOT/npi_gnn_amd/csrc/$f.hip" | cut -d" " -f1)"
   if [ -f "$OUT/$f.o" ] && [ "$(cat "$OUT/$f.key" 2>/dev/null)" = "$KEY" ]; then continue; fi
-  ( $HIPCC -O1 -g -fno-gpu-sanitize -std=c++17 --offload-arch=gfx950 -fPIC -fno-gpu-rdc -fno-omit-frame-pointer \
-         -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libasan \
+  ( $HIPCC -O1 -g -std=c++17 --offload-arch=gfx950 -fPIC -fno-gpu-rdc -fno-omit-frame-pointer -fno-sanitize-recover=undefined \
+         -fno-gpu-sanitize -fsanitize=address,undefined -shared-libasan \
          -c "$ROOT/npi_gnn_amd/csrc/$f.hip" -o "$OUT/$f.o" && echo "$KEY" > "$OUT/$f.key" ) &
 done
 wait
-$HIPCC -shared -fPIC -fsanitize=address,undefined -shared-libasan -o "$OUT/libnpi_gnn_asan.so" $objs
+$HIPCC -shared -fPIC -fno-gpu-sanitize -fsanitize=address,undefined -shared-libasan -o "$OUT/libnpi_gnn_asan.so" $objs
 echo "built $OUT/libnpi_gnn_asan.so"
 cd "$ROOT"
 LD_PRELOAD="$RT" ASAN_OPTIONS=detect_leaks=0:abort_on_error=1:verify_asan_link_order=0 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
