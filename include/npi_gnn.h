@@ -259,8 +259,11 @@ int64_t npi_linear_bwd_weight_workspace_elems(int64_t M, int64_t K, int64_t N);
 #define NPI_GEMM_SPLIT_F16X2 16
 #define NPI_PREPARE_F16X2 4
 int64_t npi_linear_workspace_bytes(int64_t K, int64_t N);
-/* scales[m] = the power of two s with max_k |A[m, k]| s in [2^14, 2^15) (1 for an all-zero row or one that holds Inf; clamped so
- * that s and 1 / s are normal f32) -- the `a_scales` of the NPI_GEMM_SPLIT_F16X2 calls.  One pass over A. */
+/* scales[m] = the power of two s with max_k |A[m, k]| s in [2^14, 2^15), clamped so that s and 1 / s are normal f32 (2^-126 ..
+ * 2^126); NaN elements are skipped, and a row with no magnitude -- all zero (or NaN), or one that holds Inf -- gets the clamp
+ * maximum 2^126, so that it never lowers the smallest scale of a matrix (npi_col_scales) -- the `a_scales` of the
+ * NPI_GEMM_SPLIT_F16X2 calls.  Every launch that writes row scales (npi_segsum_ex, the GATConv fused passes) writes these values.
+ * One pass over A. */
 int npi_row_scales(const float* A, int64_t lda, int64_t M, int64_t K, float* scales, void* stream);
 /* The re-laid copies of W [K, N] (the `weight` of PyG's `torch.matmul(aggr_out, self.weight)`, reference call sites
  * src/classes.py:62,66,70) for the matrix-core kernels, in ONE launch: which = 1: the copy npi_linear_fwd_ex uses, 2: the one
@@ -277,11 +280,12 @@ int npi_linear_bwd_weight_ex(const void* A, int64_t lda, const void* dC, int64_t
                              int64_t M, int64_t K, int64_t N,
                              float* workspace, int64_t workspace_elems, int dtype, int flags, int shared,
                              const float* a_col_scales, const float* dc_col_scales, void* stream);
-/* scales[k] = the power of two that puts column k's largest magnitude into [2^14, 2^15).  A != NULL: from the column maxima of A
- * [M, K] (one pass over it: for a matrix that does not change between steps, once).  A == NULL: from `row_scales` [M] (npi_row_scales,
- * or the launch that wrote the matrix): the SMALLEST row scale -- the scale of the matrix's largest magnitude -- for every column
- * alike, without a pass over the matrix; elements more than 2^-18 below that magnitude then keep an absolute 2^-39 of it rather
- * than 22 relative bits.  workspace: npi_col_scales_workspace_elems(M, K) floats. */
+/* scales[k] = the power of two that puts column k's largest magnitude into [2^14, 2^15) (npi_row_scales' rule: a column with no
+ * magnitude gets 2^126).  A != NULL: from the column maxima of A [M, K] (one pass over it: for a matrix that does not change between
+ * steps, once).  A == NULL: from `row_scales` [M] (npi_row_scales, or the launch that wrote the matrix): the SMALLEST row scale --
+ * the scale of the matrix's largest finite magnitude; 2^126 when every row is zero, 1 when M == 0 -- for every column alike,
+ * without a pass over the matrix; elements more than 2^-18 below that magnitude then keep an absolute 2^-39 of it rather than 22
+ * relative bits.  workspace: npi_col_scales_workspace_elems(M, K) floats. */
 int64_t npi_col_scales_workspace_elems(int64_t M, int64_t K);
 int npi_col_scales(const float* A, int64_t lda, int64_t M, int64_t K, const float* row_scales, float* scales,
                    float* workspace, int64_t workspace_elems, void* stream);

@@ -597,9 +597,9 @@ colsum_partial_kernel(const float* __restrict__ X, int64_t ldx, int M, int N, in
 
 // Power-of-two COLUMN scales for the fp16 x 2 weight-gradient GEMM (the contraction runs over the rows, so only a column scale
 // factors out of the sum).  Two sources: the column maxima of a matrix (one pass over it: static input features, once), or --
-// no pass at all -- the smallest of the ROW scales its producer wrote, i.e. the scale of the whole matrix's largest magnitude, for
-// every column alike (what an aggregation or the fused GATConv pass leaves behind; elements more than 2^-18 below that magnitude
-// then keep an absolute 2^-39 of it instead of 22 relative bits).
+// no pass at all -- the smallest of the ROW scales its producer wrote, i.e. the scale of the whole matrix's largest finite magnitude
+// (rows with none carry the clamp maximum 2^126: pow2_scale_of), for every column alike (what an aggregation or the fused GATConv
+// pass leaves behind; elements more than 2^-18 below that magnitude then keep an absolute 2^-39 of it instead of 22 relative bits).
 __global__ void __launch_bounds__(256)
 colmax_partial_kernel(const float* __restrict__ X, int64_t ldx, int M, int N, int rows, float* __restrict__ part) {
     __shared__ float red[4][256];
@@ -649,7 +649,7 @@ minscale_finish_kernel(const float* __restrict__ part, int nparts, int K, float*
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     m = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
-    if (!(m < 3.0e38f)) m = 1.f;                          // no row at all
+    if (!(m < 3.0e38f)) m = 1.f;                          // no row at all (all-zero rows: 2^126, below the sentinel)
     for (int k = threadIdx.x; k < K; k += 256) scales[k] = m;
 }
 
@@ -2432,7 +2432,7 @@ extern "C" int npi_col_scales(const float* A, int64_t lda, int64_t M, int64_t K,
                               float* workspace, int64_t workspace_elems, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     NPI_REQUIRE(M >= 0 && K > 0 && M < 0x7fffffff && K < 0x7fffffff, "npi_col_scales: bad size");
-    NPI_REQUIRE(scales && workspace && (A != nullptr || row_scales != nullptr), "npi_col_scales: null pointer (A or row_scales)");
+    NPI_REQUIRE(scales && workspace && (A != nullptr || row_scales != nullptr || M == 0), "npi_col_scales: null pointer (A or row_scales)");
     if (workspace_elems < npi_col_scales_workspace_elems(M, K)) {
         set_error("npi_col_scales: workspace too small (npi_col_scales_workspace_elems)");
         return NPI_ERR_WORKSPACE;

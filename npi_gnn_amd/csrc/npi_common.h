@@ -42,13 +42,13 @@ __device__ __forceinline__ T* uniform_ptr(T* p) {
 }
 
 // fp16 x 2 projection (NPI_GEMM_SPLIT_F16X2, gemm_f32.hip): power-of-two scale for a row / column whose largest magnitude is m,
-// m * scale in [2^14, 2^15) (1 for an all-zero row and for Inf / NaN -- which then propagate as in the bf16 split --; clamped so
-// that scale and 1 / scale are normal f32).  Written by npi_row_scales, by the weight preparation, and by the aggregation
-// kernels for the rows they finish (npi_segsum_ex).
+// m * scale in [2^14, 2^15), clamped so that scale and 1 / scale are normal f32 (2^-126 .. 2^126).  A row with no magnitude -- all
+// zero, or an Inf / NaN maximum (which then propagates as in the bf16 split) -- takes the clamp maximum 2^126, the scale of the
+// tiniest real rows: the smallest scale of a matrix (npi_col_scales from row scales) is then that of its largest FINITE magnitude.
+// Written by npi_row_scales, by the weight preparation, and by the aggregation kernels for the rows they finish (npi_segsum_ex).
 __device__ __forceinline__ float pow2_scale_of(float m) {
     const uint32_t eb = (__float_as_uint(m) >> 23) & 0xff;
-    if (m == 0.f || eb == 255) return 1.f;
-    int es = 268 - (int)eb;                                   // biased exponent of 2^(14 - (eb - 127))
+    int es = eb == 255 ? 253 : 268 - (int)eb;                 // biased exponent of 2^(14 - (eb - 127)); 0 and subnormals: > 253
     es = es > 253 ? 253 : (es < 1 ? 1 : es);
     return __uint_as_float((uint32_t)es << 23);
 }
