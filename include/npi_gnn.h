@@ -140,6 +140,43 @@ int npi_segsum_ex(const int32_t* rowptr, const int32_t* col, const int32_t* item
                    const void* x2, int64_t split, void* out, int64_t ldo, int64_t F, int dtype, int mean,
                    const float* bias, float* carry, float* row_scales_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The heaviest rows of a side ("hubs") aggregated by streaming the source table once instead of gathering it.
+ * A row that holds a sizeable fraction of all columns re-reads a table no cache can hold; streamed, every source row is
+ * fetched once and added into the accumulators of the hubs its mask names.  One-table sides with n_cols == N, f32, F = 256.
+ *
+ * npi_hub_plan (once per graph and side): the up to h_max <= NPI_HUB_MAX rows with the most entries among the rows with at
+ * least min_degree entries (ties: the lower row first), minus rows that hold a column twice (a mask bit cannot count twice).
+ *   hub_rows[NPI_HUB_MAX]   : int32, the hubs by descending degree; -1 behind the last
+ *   mask[n_cols][NPI_HUB_MAX / 32] : uint32, bit j of mask[c] set iff the side has an entry (hub j, c) -- a self loop included
+ *   info[4]                 : int32 device words: [0] H, the number of hubs -- 0 (plan EMPTY: use npi_segsum_ex alone) when their
+ *                             entries add up to less than min_entries or more than 4,096 rows reach min_degree; [1] the entries of
+ *                             the hub rows; [2] rows with >= min_degree entries; [3] hubs before the duplicate check
+ *   workspace               : int32, npi_hub_plan_workspace_elems() elements
+ * npi_hub_light_side: the same side with the hub rows EMPTY and every other entry in its order (arrays as npi_csr_build_ex writes
+ * them, capacity nnz_max_light >= nnz - info[1]); npi_segsum_ex walks it unchanged and leaves zeros in the hub rows.
+ * npi_segsum_hub (same stream, BEHIND the light side's npi_segsum_ex on the same `out`): for every hub j
+ *     out[hub_rows[j], :] = scale_j * sum_{c : bit j of mask[c]} col_scale[c] * x[c, :]
+ *   mean != 0   : scale_j = 1 / max(length of the ORIGINAL row, 1) (rowptr: the original side's); col_scale == NULL: ones
+ *   partial     : f32 scratch, npi_segsum_hub_partial_elems(n_cols) elements, no need to clear; two launches that may run
+ *                 concurrently need two buffers
+ *   row_scales_out : as npi_segsum_ex (the hub rows' elements are overwritten)
+ * No float atomics: every hub row is summed in a fixed order, bitwise reproducible from launch to launch.
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_HUB_MAX 128
+int64_t npi_hub_plan_workspace_elems(void);
+int npi_hub_plan(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t n_cols, int64_t nnz_max, int64_t h_max,
+                 int64_t min_degree, int64_t min_entries, int32_t* hub_rows, uint32_t* mask, int32_t* info, int32_t* workspace,
+                 void* stream);
+int npi_hub_light_side(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const int32_t* rowidx, int64_t N,
+                       int64_t nnz_max, const int32_t* hub_rows, int64_t H, int64_t nnz_max_light, int64_t item_edges,
+                       int32_t* rowptr_l, int32_t* col_l, int32_t* eid_l, int32_t* rowidx_l, int32_t* item_row_l, void* stream);
+int64_t npi_segsum_hub_slabs(int64_t n_cols);
+int64_t npi_segsum_hub_partial_elems(int64_t n_cols);
+int npi_segsum_hub(const int32_t* hub_rows, int64_t H, const uint32_t* mask, const int32_t* rowptr, int64_t N, int64_t n_cols,
+                   const float* col_scale, const float* x, int64_t ldx, float* out, int64_t ldo, int64_t F, int mean,
+                   float* partial, float* row_scales_out, void* stream);
+
 /* GCNConv.norm (PyG 1.4.2): deg[j] = sum of weights of entries in row j of the BY-SOURCE CSR
  * (deg == NULL: unweighted, the row lengths of deg_rowptr are used);
  * norm[p] = deg^-1/2[rowidx[p]] * w[p] * deg^-1/2[col[p]] for the entries of either CSR

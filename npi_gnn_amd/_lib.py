@@ -22,6 +22,7 @@ NPI_GEMM_A_ZERO_PADDED = 4   # A stored with zero pad columns up to a multiple o
 NPI_GEMM_WORKSPACE_PREPARED = 8   # the workspace already holds npi_linear_prepare's copy of this weight matrix
 NPI_GEMM_SPLIT_F16X2 = 16         # two fp16 pieces per operand, three matrix products per tile pair (needs the row scales of A)
 NPI_PREPARE_F16X2 = 4             # npi_linear_prepare(which | this): the fp16 x 2 planes of the weight matrix
+NPI_HUB_MAX = 128                 # hubs per plan (npi_hub_plan; mask words of NPI_HUB_MAX / 32 per source row)
 
 
 def NPI_GEMM_RESERVE_CUS(n: int) -> int:
@@ -47,6 +48,12 @@ PROTOTYPES = {
     "npi_segsum_carry_elems": (_I, [_I, _I, _I]),
     "npi_segsum_ex": (c_int, [_P, _P, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _I, c_int, c_int, _P, _P, _P, _P]),
     "npi_segsum_scales_supported": (c_int, [_I, c_int]),
+    "npi_hub_plan_workspace_elems": (_I, []),
+    "npi_hub_plan": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "npi_hub_light_side": (c_int, [_P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "npi_segsum_hub_slabs": (_I, [_I]),
+    "npi_segsum_hub_partial_elems": (_I, [_I]),
+    "npi_segsum_hub": (c_int, [_P, _I, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, c_int, _P, _P, _P]),
     "npi_row_weight_sum": (c_int, [_P, _P, _I, _P, _P]),
     "npi_gcn_norm": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "npi_row_inv_count": (c_int, [_P, _I, _P, _P]),

@@ -15,7 +15,7 @@ import torch
 
 from ._lib import (NPI_BF16, NPI_F32, NPI_GEMM_A_ZERO_PADDED, NPI_GEMM_EXACT_F32, NPI_GEMM_RESERVE_CUS, NPI_GEMM_SPLIT_F16X2,
                    NPI_GEMM_WORKSPACE_PREPARED, NPI_PREPARE_F16X2, check, load, ptr, require_gpu, stream_ptr)
-from .graph import CSRGraph, CSRSide, as_graph
+from .graph import CSRGraph, CSRSide, HubPlan, as_graph
 from .schedule import DEFAULT, Schedule
 
 
@@ -136,13 +136,17 @@ def segsum_scales_ok(side: CSRSide, x: torch.Tensor, out: Optional[torch.Tensor]
 def segsum(graph: CSRGraph, side: CSRSide, x: torch.Tensor, w: Optional[torch.Tensor] = None,
            mean: bool = False, bias: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None, x2: Optional[torch.Tensor] = None,
-           scales_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+           scales_out: Optional[torch.Tensor] = None, hub: Optional[HubPlan] = None,
+           col_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[i] = scale_i * sum_{p in row i} w[p] * x[col[p]] (+ bias): fused gather + segmented
     reduction (``npi_segsum``).  ``x2``: second part of a two-part table -- entries with
     ``col >= x.size(0)`` read ``x2[col - x.size(0)]`` (``npi_segsum_ex``; the sharded layers).
     ``scales_out`` ``[n_rows]`` f32: also the power-of-two scale of every finished row (what ``row_scales(out)`` would compute in
-    a pass of its own; ``segsum_scales_ok``) for the fp16 x 2 projection behind the aggregation."""
-    dev = require_gpu(x, w, bias, x2)
+    a pass of its own; ``segsum_scales_ok``) for the fp16 x 2 projection behind the aggregation.
+    ``hub``: ``side``'s plan (``hub_plan_for``) -- the plain launch walks ``hub.light`` (``w``: ITS per-entry weights) and the hub
+    rows are summed by streaming the table (``npi_segsum_hub``, same stream): ``out[hub j] = sum_r col_scale[r] x[r]`` over the
+    source rows ``r`` of hub j (``col_scale`` ``[n_cols]`` f32 or None: ones), divided by the ORIGINAL row's count under ``mean``."""
+    dev = require_gpu(x, w, bias, x2, col_scale)
     x = _fcp(x, "x")
     if bias is not None:
         bias = _fc(bias, "bias", x)
@@ -162,6 +166,18 @@ def segsum(graph: CSRGraph, side: CSRSide, x: torch.Tensor, w: Optional[torch.Te
         out = torch.empty((N, F), dtype=x.dtype, device=dev)
     else:
         _check_out(out, N, F, x, "segsum")
+    full = side
+    if hub is not None:
+        if not (x.dtype == torch.float32 and F == 256 and x2 is None and bias is None and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+                and out.stride(0) % 4 == 0 and out.data_ptr() % 16 == 0 and hub.light.n_rows == N):
+            raise ValueError("segsum(hub=): the streaming path takes one f32 table of 256 columns, 16-byte aligned rows, no bias")
+        if col_scale is not None:
+            col_scale = _f32c(col_scale, "col_scale")
+            if col_scale.numel() != side.n_cols:
+                raise ValueError(f"segsum: col_scale has {col_scale.numel()} elements, the table {side.n_cols} rows")
+        side = hub.light
+    elif col_scale is not None:
+        raise ValueError("segsum: col_scale belongs to the streaming path (hub=); the plain launch takes per-entry weights")
     carry = side.carry(F)
     prof = _PROFILE
     if prof is not None:        # bench.py: HIP events on the launch stream around this launch
@@ -172,10 +188,22 @@ def segsum(graph: CSRGraph, side: CSRSide, x: torch.Tensor, w: Optional[torch.Te
     check(load().npi_segsum_ex(ptr(side.rowptr), ptr(side.col), ptr(side.item_row), side.item, ptr(w), N, side.nnz_max,
                                 ptr(x), x.stride(0), ptr(x2), split if x2 is not None else 0, ptr(out), out.stride(0), F,
                                 _code(x), 1 if mean else 0, ptr(bias), ptr(carry), ptr(scales_out), stream_ptr(dev)), "npi_segsum")
+    if hub is not None:
+        check(load().npi_segsum_hub(ptr(hub.hub_rows), hub.H, ptr(hub.mask), ptr(full.rowptr), N, full.n_cols, ptr(col_scale), ptr(x),
+                                    x.stride(0), ptr(out), out.stride(0), F, 1 if mean else 0, ptr(hub.partial()), ptr(scales_out),
+                                    stream_ptr(dev)), "npi_segsum_hub")
     if prof is not None:
         ev1.record(torch.cuda.current_stream(dev))
         prof.append((ev0, ev1))
     return out
+
+
+def hub_plan_for(graph: CSRGraph, side: CSRSide, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> Optional[HubPlan]:
+    """``side``'s hub plan when the aggregation of ``x`` over it may take the streaming path (``CSRGraph.hub_stream``; f32, 256
+    columns, 16-byte aligned rows) and the side has one; else None: the plain launch."""
+    if not graph.hub_stream or not segsum_scales_ok(side, x, out) or x.size(0) != side.n_cols:
+        return None
+    return side.hub_plan()
 
 
 # Arithmetic of the f32 projection GEMMs: an argument of every call (``flags``: 0 = the split on the 16-bit matrix cores,
@@ -711,15 +739,17 @@ def _aggregate_first_ok(sch: Schedule, f16: bool, weight: torch.Tensor, grad_out
 
 
 def _backward_aggregate_first(graph, tside: CSRSide, w_t: Optional[torch.Tensor], agg, weight, grad_out, ws_bwd: "Planes", want_w: bool,
-                              has_bias: bool, overlap: bool, k_valid=None):
+                              has_bias: bool, overlap: bool, k_valid=None, hub: Optional[HubPlan] = None):
     """``dX = (A_w^T dOut) W^T`` instead of ``A_w^T (dOut W^T)`` -- the same number up to fp32 rounding (the aggregation is linear;
     GCNConv's forward uses the same freedom).  What it buys on large graphs: the transposed aggregation now WRITES
     the left operand of the backward's data GEMM, so it writes that operand's row scales too (``segsum(scales_out=)``) and the
     GEMM runs on two fp16 pieces per operand -- three matrix products instead of six -- with no pass over dOut for its scales
     (which arrive from outside the layer).  dW = agg^T dOut needs neither and goes first on the launch stream, so that it is
     resident on every CU before the aggregation -- on the side stream -- fills the remaining wave slots (as before).
-    ``w_t``: per-entry weights of the transposed side (``mean_bwd_weights`` / the GCN norm).  Returns ``(dx, dw, db)``."""
+    ``w_t``: per-entry weights of the transposed side (``mean_bwd_weights`` / the GCN norm).  ``hub``: ``tside``'s plan -- then
+    ``w_t`` belongs to ``hub.light`` and the hub rows take the mean's divisors as a column scale.  Returns ``(dx, dw, db)``."""
     dev = grad_out.device
+    cs = graph.inv_count(graph.by_dst) if hub is not None else None
     N, Nout = grad_out.shape
     t = torch.empty((N, Nout), dtype=torch.float32, device=dev)
     t_scales = torch.empty(N, dtype=torch.float32, device=dev)
@@ -730,14 +760,14 @@ def _backward_aggregate_first(graph, tside: CSRSide, w_t: Optional[torch.Tensor]
         side.wait_stream(main)                                   # dOut (and the buffers above) are ready for the side stream
         dw, db = linear_bwd_weight(agg, grad_out, want_bias=has_bias, shared=True, k_valid=k_valid)
         with torch.cuda.stream(side):
-            segsum(graph, tside, grad_out, w=w_t, mean=False, out=t, scales_out=t_scales)
+            segsum(graph, tside, grad_out, w=w_t, mean=False, out=t, scales_out=t_scales, hub=hub, col_scale=cs)
         for buf in (grad_out, t, t_scales):
             buf.record_stream(side)                              # allocated on main, used on side
         main.wait_stream(side)
     else:
         if want_w:
             dw, db = linear_bwd_weight(agg, grad_out, want_bias=has_bias, k_valid=k_valid)
-        segsum(graph, tside, grad_out, w=w_t, mean=False, out=t, scales_out=t_scales)
+        segsum(graph, tside, grad_out, w=w_t, mean=False, out=t, scales_out=t_scales, hub=hub, col_scale=cs)
     dx = linear_bwd_data(t, weight, ws=ws_bwd, dc_scales=t_scales)
     return dx, dw, db
 
@@ -762,7 +792,9 @@ class _SageConvFn(torch.autograd.Function):
             # agg itself (a wave maximum per finished row); where it cannot, a pass over agg would cost what the GEMM saves
             agg = torch.empty((graph.by_dst.n_rows, x.size(1)), dtype=x.dtype, device=x.device)
             scales = torch.empty(agg.size(0), dtype=torch.float32, device=x.device)
-            segsum(graph, graph.by_dst, x, w=w_entry[0] if w_entry else None, mean=True, out=agg, scales_out=scales)
+            # (no edge weights: the heaviest rows by streaming x once, the rest by the plain launch -- CSRGraph.hub_stream)
+            hub = hub_plan_for(graph, graph.by_dst, x, agg) if not w_entry else None
+            segsum(graph, graph.by_dst, x, w=w_entry[0] if w_entry else None, mean=True, out=agg, scales_out=scales, hub=hub)
             # both fp16 x 2 copies of W in one call: the backward runs aggregate-first (_backward_aggregate_first), so its data GEMM
             # takes the row scales the transposed aggregation writes -- no pass over dOut, which arrives from outside the layer
             wsf, ctx.ws_bwd = prepare_weight(weight, backward=ctx.needs_input_grad[0], f16=True)
@@ -784,7 +816,8 @@ class _SageConvFn(torch.autograd.Function):
         # columns stay zero under a weighted mean -- and both GEMMs run on it (linear_fwd / linear_bwd_weight)
         agg = None if fl else padded_aggregate_buffer(x, weight.size(0), graph.by_dst.n_rows, bf16_ok=True)
         if agg is None:
-            agg = segsum(graph, graph.by_dst, x, w=w_entry[0] if w_entry else None, mean=True)
+            agg = segsum(graph, graph.by_dst, x, w=w_entry[0] if w_entry else None, mean=True,
+                         hub=hub_plan_for(graph, graph.by_dst, x) if not w_entry else None)
         else:
             segsum(graph, graph.by_dst, x, w=w_entry[0] if w_entry else None, mean=True, out=agg[:, : x.size(1)])
         if agg.size(1) != weight.size(0) and agg.dtype == torch.bfloat16:
@@ -827,8 +860,12 @@ class _SageConvFn(torch.autograd.Function):
         dx = dw = db = None
         if want_x and _aggregate_first_ok(ctx.sch, ctx.f16, weight, grad_out, tside(), ctx.ws_bwd):
             ts = tside()
-            dx, dw, db = _backward_aggregate_first(graph, ts, mean_bwd_weights(graph, ts, ctx.w_src), agg, weight, grad_out, ctx.ws_bwd,
-                                                   want_w, ctx.has_bias, overlap, ctx.k_valid)
+            # no edge weights: the weights are inv_count[col], a factor of the GATHERED row -- the streaming path's column scale;
+            # the plain launch over the light side takes the same factors per entry (cached per graph and side, as before)
+            hub = hub_plan_for(graph, ts, grad_out) if ctx.w_src is None else None
+            w_t = mean_bwd_weights(graph, ts if hub is None else hub.light, ctx.w_src)
+            dx, dw, db = _backward_aggregate_first(graph, ts, w_t, agg, weight, grad_out, ctx.ws_bwd, want_w, ctx.has_bias, overlap,
+                                                   ctx.k_valid, hub=hub)
             return dx, dw, db, None, None, None, None
         ws_bwd = ctx.ws_bwd if not (isinstance(ctx.ws_bwd, Planes) and ctx.ws_bwd.f16) else None     # (fp16 x 2 planes: not for this order)
         if want_w and not overlap:
@@ -850,12 +887,14 @@ class _SageConvFn(torch.autograd.Function):
                 side.wait_stream(main)                               # dAgg is complete for the side stream
                 dw, db = linear_bwd_weight(agg, grad_out, want_bias=ctx.has_bias, shared=True, k_valid=ctx.k_valid, flags=fl)
                 with torch.cuda.stream(side):
-                    dx = segsum(graph, tside(), dagg, w=ctx.w_src, mean=False)
+                    dx = segsum(graph, tside(), dagg, w=ctx.w_src, mean=False,
+                                hub=hub_plan_for(graph, tside(), dagg) if ctx.w_src is None else None)
                 dagg.record_stream(side)                             # allocated on main, read on side
                 dx.record_stream(main)                               # allocated on side, consumed on main
                 main.wait_stream(side)
             else:
-                dx = segsum(graph, tside(), dagg, w=ctx.w_src, mean=False)
+                dx = segsum(graph, tside(), dagg, w=ctx.w_src, mean=False,
+                            hub=hub_plan_for(graph, tside(), dagg) if ctx.w_src is None else None)
         if dw is not None and ctx.k_rows is not None:
             dw = dw[: ctx.k_rows]                                             # the gradient of the zero rows is not W's
         return dx, dw, db, None, None, None, None

@@ -102,6 +102,8 @@ class CSRSide:
     n_rows: int = -1          # output rows (key id space)
     n_cols: int = -1          # rows of the feature table the entries index (== n_rows unless sharded)
     item: int = 0             # entries per item this side was cut with
+    _hub: Optional["HubPlan"] = None      # the streaming path for the heaviest rows (``hub_plan()``), None: none / not asked yet
+    _hub_asked: bool = False
 
     def inv_count(self) -> torch.Tensor:
         """1 / max(row length, 1): the scatter_mean divisor (count includes the self loop)."""
@@ -112,6 +114,18 @@ class CSRSide:
                   "npi_row_inv_count")
             self._inv_cnt = out
         return self._inv_cnt
+
+    def hub_plan(self) -> Optional["HubPlan"]:
+        """The plan for aggregating this side's heaviest rows by streaming the table (``build_hub_plan``), made on first use and
+        kept; None when the side has no such rows (then the plain launch is all there is).  One device read, once per side --
+        so never inside a capture: a side first met there is walked the plain way until somebody asks again outside."""
+        if not self._hub_asked:
+            if self.n_rows != self.n_cols or self.n_cols < HUB_MIN_COLS or self.nnz_max <= 0:
+                self._hub_asked = True
+            elif not torch.cuda.is_current_stream_capturing():
+                self._hub = build_hub_plan(self)
+                self._hub_asked = True
+        return self._hub
 
     def carry(self, F: int) -> torch.Tensor:
         """f32 scratch of the aggregation launches (partial sums of rows cut by a workgroup boundary + their arrival
@@ -148,6 +162,89 @@ class CSRSide:
         """Drop every scratch buffer of this side (after an aborted launch or a failed ``check()``): the next launch of each
         (width, stream) gets a freshly zeroed one."""
         self._carry.clear()
+
+
+#: A side gets a hub plan only when its table is larger than the 256 MB Infinity Cache (262,144 rows of 256 f32): a smaller table
+#: is gathered from cache, and streaming it saves no HBM traffic.  Every small batched configuration stops here, at no cost.
+HUB_MIN_COLS = 262_144
+#: A row qualifies as a hub from ``n_cols / HUB_DEGREE_DIV`` entries on.  In bytes any row pays once the table is streamed anyway
+#: (its bit rides in a mask word that is read regardless); the bound keeps the candidates few and the rows long enough that the
+#: scalar mask test per (source row, hub) stays small beside the row's 1 KiB.
+HUB_DEGREE_DIV = 512
+#: ... and the plan is empty unless the hubs' entries together are at least this many times the rows that have to be streamed:
+#: 1 is break-even in bytes (entries x 1 KiB gathered against n_cols x 1 KiB streamed); the second launch, its tail and the
+#: partial sums have to be paid for as well.
+HUB_ENTRIES_PER_STREAMED_ROW = 2
+
+
+@dataclass
+class HubPlan:
+    """The heaviest rows of one ``CSRSide`` and what the streaming aggregation needs (``npi_hub_plan`` / ``npi_segsum_hub``):
+    ``hub_rows[NPI_HUB_MAX]`` int32 (the first ``H`` valid, by descending degree), ``mask[n_cols, NPI_HUB_MAX / 32]`` (bit j of
+    source row r: the side has an entry (hub j, r)), and ``light``: the same side with the hub rows empty."""
+    H: int
+    n_entries: int                     # entries of the hub rows (what the light side no longer holds)
+    hub_rows: torch.Tensor
+    mask: torch.Tensor
+    light: CSRSide
+    _partial: Dict[int, torch.Tensor] = field(default_factory=dict)
+
+    def partial(self) -> torch.Tensor:
+        """scratch of the streaming launch (one partial sum per slab and hub), by the rules of ``CSRSide.carry``: one buffer per
+        stream in use, the least recently used one dropped beyond ``CARRY_SLOTS`` -- never during a capture, whose graph replays
+        the launch on the buffer it saw.  Needs no clearing."""
+        dev = self.mask.device
+        key = _lib.stream_ptr(dev)
+        buf = self._partial.pop(key, None)
+        if buf is None:
+            buf = torch.empty(int(load().npi_segsum_hub_partial_elems(self.mask.size(0))), dtype=torch.float32, device=dev)
+            if len(self._partial) >= CARRY_SLOTS and not torch.cuda.is_current_stream_capturing():
+                self._partial.pop(next(iter(self._partial)))
+        self._partial[key] = buf
+        return buf
+
+
+def build_hub_plan(side: CSRSide, h_max: int = _lib.NPI_HUB_MAX, min_degree: Optional[int] = None,
+                   min_entries: Optional[int] = None) -> Optional[HubPlan]:
+    """``npi_hub_plan`` + ``npi_hub_light_side`` for one side (a one-table side, ``n_cols == n_rows``); None when the plan comes
+    out empty.  Reads four words back from the device.  ``min_degree`` / ``min_entries``: the two thresholds (defaults: the
+    module's policy, ``HUB_DEGREE_DIV`` / ``HUB_ENTRIES_PER_STREAMED_ROW``)."""
+    if side.n_rows != side.n_cols:
+        raise ValueError("build_hub_plan: one-table sides with n_cols == n_rows only")
+    lib = load()
+    dev = side.rowptr.device
+    N = side.n_rows
+    if N <= 0 or side.nnz_max <= 0:
+        return None
+    if min_degree is None:
+        min_degree = max(-(-side.n_cols // HUB_DEGREE_DIV), 2)
+    if min_entries is None:
+        min_entries = HUB_ENTRIES_PER_STREAMED_ROW * side.n_cols
+    i32 = dict(dtype=torch.int32, device=dev)
+    hub_rows = torch.empty(_lib.NPI_HUB_MAX, **i32)
+    mask = torch.empty((side.n_cols, _lib.NPI_HUB_MAX // 32), **i32)
+    info = torch.empty(4, **i32)
+    ws = torch.empty(int(lib.npi_hub_plan_workspace_elems()), **i32)
+    s = stream_ptr(dev)
+    check(lib.npi_hub_plan(ptr(side.rowptr), ptr(side.col), N, side.n_cols, side.nnz_max, int(h_max), int(min_degree), int(min_entries),
+                           ptr(hub_rows), ptr(mask), ptr(info), ptr(ws), s), "npi_hub_plan")
+    H, n_entries = info.tolist()[:2]
+    if H == 0:
+        return None
+    nnz_max = side.nnz_max - n_entries
+    n_items = int(lib.npi_num_items(nnz_max, side.item))
+    rowptr = torch.empty(N + 1, **i32)
+    col = torch.empty(max(nnz_max, 1), **i32)
+    eid = torch.empty(max(nnz_max, 1), **i32)
+    rowidx = torch.empty(max(nnz_max, 1), **i32)
+    item_row = torch.empty(n_items + 1, **i32)
+    check(lib.npi_hub_light_side(ptr(side.rowptr), ptr(side.col), ptr(side.eid), ptr(side.rowidx), N, side.nnz_max, ptr(hub_rows), H,
+                                 nnz_max, side.item, ptr(rowptr), ptr(col), ptr(eid), ptr(rowidx), ptr(item_row), s),
+          "npi_hub_light_side")
+    light = CSRSide(rowptr, col, eid, rowidx, item_row, side.status, nnz_max, n_items)
+    light.n_rows, light.n_cols, light.item = N, side.n_cols, side.item
+    light._hub_asked = True                                   # (the light side has no plan of its own)
+    return HubPlan(H, n_entries, hub_rows, mask, light)
 
 
 def item_hint(nnz_max: int) -> int:
@@ -198,7 +295,8 @@ class CSRGraph:
     ``by_src`` groups them by source node (backward: dX = A^T ...), built lazily."""
 
     def __init__(self, edge_index: torch.Tensor, num_nodes: int, self_loops: bool = True, by_dst: Optional[CSRSide] = None,
-                 symmetric: bool = False, item: Optional[int] = None, sort_columns: bool = False, keep_equal: bool = False):
+                 symmetric: bool = False, item: Optional[int] = None, sort_columns: bool = False, keep_equal: bool = False,
+                 hub_stream: bool = True):
         """``item``: entries per item of both sides (64 or 256; default: the hint for this capacity, ``item_hint``).
         ``sort_columns``: both sides with every row's entries in column order (a second key for the build's sort: at 4M nodes /
         100M edges 3 ms more per side, once, for 1.2 % of every GATConv layer step and 0.6 % of every SAGEConv one -- the
@@ -206,6 +304,9 @@ class CSRGraph:
         ``self_loops=False, keep_equal=True``: the edge list exactly as it is -- no loop appended, existing ``(i, i)`` columns kept
         as ordinary entries (what PyG's ``SAGEConv(concat=True)`` aggregates over; the default drops them first, as
         ``add_remaining_self_loops`` does).
+        ``hub_stream``: SAGEConv (f32, 256 features, no edge weights) aggregates the heaviest rows of a side that has a hub plan
+        (``CSRSide.hub_plan``) by streaming the table once (``npi_segsum_hub``) beside the plain launch over the rest; False: the
+        plain launch alone, as for a side without such rows.  A plain attribute: both paths can be run over one graph and compared.
         ``by_dst``: a by-target side somebody already derived for this very edge list (``filtered_side``): not rebuilt.
         ``symmetric``: the producer of the edge list vouches that it holds every edge in both directions (the device-side
         subgraph extraction emits both, src/classes.py:701-704, and filter_adj keeps the property; ``GraphBatch.symmetric``).
@@ -229,6 +330,7 @@ class CSRGraph:
         self._item = item if by_dst is None else by_dst.item
         self.sort_columns = bool(sort_columns)
         self.keep_equal = bool(keep_equal)
+        self.hub_stream = bool(hub_stream)
         if self.keep_equal and self.self_loops:
             raise ValueError("CSRGraph: keep_equal=True (existing self loops stay ordinary entries) needs self_loops=False")
         self.by_dst = by_dst if by_dst is not None else \
