@@ -199,6 +199,31 @@ int npi_row_inv_count(const int32_t* rowptr, int64_t N, float* inv_cnt, void* st
 int npi_entry_weights(const int32_t* eid, const int32_t* rowidx, const int32_t* rowptr,
                       const float* edge_w, const float* loop_w_node, float fill,
                       int64_t N, int64_t nnz_max, float* w_entry, void* stream);
+/* Gradients w.r.t. edge_weight of SAGEConv / GCNConv: what autograd computes for `edge_weight.view(-1, 1) * x_j` in front of the
+ * scatter (PyG 1.4.2 SAGEConv.message / GCNConv.message: the backward of the broadcast multiply, a row-wise sum of
+ * grad * x_j per edge) -- one dot product per entry p of one CSR side (i = rowidx[p]):
+ *   g[p] = row_scale[i] * <a[i, :], b[col[p], :]>      a [N, F] (lda), read once per row; b [n_cols, F] (ldb), gathered
+ * f32, any F; 16-byte lanes when F % 4 == 0 and both tables have 16-byte aligned rows.  row_scale [N] may be NULL (ones).
+ * Outputs, each optional (NULL: not written; at least one):
+ *   g_entry  [nnz_max]  g in entry order
+ *   gm_entry [nnz_max]  g[p] * mul[p] (mul [nnz_max]: both or neither) -- g norm for npi_gcn_norm_bwd's row sums
+ *   d_edge   [n_edges]  d_edge[eid[p]] = g[p] for eid[p] >= 0: every edge owns one entry of a side, so plain stores; elements of
+ *                       edges without an entry (existing self loops, dropped or padding columns) are NOT written
+ *   d_loop   [N]        d_loop[i] = g[p] for the implicit self loop of row i (eid[p] < 0)
+ * No float atomics, fixed summation order: bitwise reproducible from launch to launch.  Nothing is allocated. */
+int npi_edge_dot(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* eid, int64_t N, int64_t n_cols,
+                 int64_t nnz_max, int64_t n_edges, const float* a, int64_t lda, const float* b, int64_t ldb, int64_t F,
+                 const float* row_scale, const float* mul, float* g_entry, float* gm_entry, float* d_edge, float* d_loop,
+                 void* stream);
+/* Backward of GCNConv.norm (PyG 1.4.2: deg = scatter_add(edge_weight, row); norm = deg^-1/2[row] * edge_weight * deg^-1/2[col];
+ * autograd through the pow, the two gathers and the scatter_add) over the BY-TARGET CSR, g_entry = d loss / d norm per entry:
+ *   d w_p = g_p deg^-1/2[j] deg^-1/2[i] - (s_a[j] + s_b[j]) / (2 deg[j])        i = rowidx[p] (target), j = col[p] (source)
+ * s_a + s_b [N]: the sum of g norm over the entries whose source is k plus that over the entries whose target is k
+ * (npi_seg_rowsum_ex over both orientations of npi_edge_dot's gm_entry; s_b may be NULL).  deg <= 0: both terms are 0.
+ * Stored like npi_edge_dot's d_edge / d_loop (either may be NULL, not both). */
+int npi_gcn_norm_bwd(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* eid, int64_t N,
+                     int64_t nnz_max, int64_t n_edges, const float* g_entry, const float* deg, const float* s_a, const float* s_b,
+                     float* d_edge, float* d_loop, void* stream);
 /* Backward of the ReLU that SAGEConv(..., relu=True) applies in its projection epilogue (autograd's threshold_backward):
  * dz[r, c] = y[r, c] > 0 ? dy[r, c] : 0 over M rows of F floats, y = the layer's (post-ReLU) output. */
 /* Measurement support (no reference counterpart): `workgroups` workgroups that each hold 64 KB of a CU's LDS for `nanoseconds` --

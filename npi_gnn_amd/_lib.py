@@ -59,6 +59,8 @@ PROTOTYPES = {
     "npi_row_inv_count": (c_int, [_P, _I, _P, _P]),
     "npi_entry_col_scale": (c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "npi_entry_weights": (c_int, [_P, _P, _P, _P, _P, c_float, _I, _I, _P, _P]),
+    "npi_edge_dot": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "npi_gcn_norm_bwd": (c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "npi_relu_backward": (c_int, [_P, _I, _P, _I, _I, _I, _P, _I, _P]),
     "npi_l2_normalize_rows": (c_int, [_P, _I, _I, _I, c_float, _P, _I, _P, _P]),
     "npi_l2_normalize_rows_bwd": (c_int, [_P, _I, _P, _I, _P, _I, _I, c_float, _P, _I, _P]),

@@ -696,7 +696,7 @@ def entry_weights(graph: CSRGraph, edge_weight: Optional[torch.Tensor], fill: fl
     loop_w = None
     if edge_weight is not None:
         require_gpu(edge_weight)
-        edge_weight = _f32c(edge_weight.detach(), "edge_weight")
+        edge_weight = _f32c(edge_weight.detach(), "edge_weight").view(-1)       # ([E, 1], as PyG's `edge_weight.view(-1, 1)` takes it)
         if edge_weight.numel() != graph.num_edges:
             raise ValueError(f"edge_weight has {edge_weight.numel()} entries, edge_index {graph.num_edges} columns")
     src, dst = graph._src, graph._dst
@@ -770,6 +770,126 @@ def _backward_aggregate_first(graph, tside: CSRSide, w_t: Optional[torch.Tensor]
         segsum(graph, tside, grad_out, w=w_t, mean=False, out=t, scales_out=t_scales, hub=hub, col_scale=cs)
     dx = linear_bwd_data(t, weight, ws=ws_bwd, dc_scales=t_scales)
     return dx, dw, db
+
+
+# ---------------------------------------------------------------------------------------------
+# d edge_weight of SAGEConv / GCNConv
+# ---------------------------------------------------------------------------------------------
+def edge_dot(side: CSRSide, a: torch.Tensor, b: torch.Tensor, n_edges: int, row_scale: Optional[torch.Tensor] = None,
+             mul: Optional[torch.Tensor] = None, want_entry: bool = False, d_edge: Optional[torch.Tensor] = None,
+             d_loop: Optional[torch.Tensor] = None):
+    """``g[p] = row_scale[i] * <a[i, :], b[col[p], :]>`` for every entry ``p`` of ``side`` (``i`` its row; ``npi_edge_dot``): the
+    gradient w.r.t. the per-entry weight of ``segsum(side, b, w=...)`` when ``a`` is the gradient of its output.  ``a`` / ``b``
+    f32, rows may have a pitch.  ``d_edge [n_edges]`` / ``d_loop [n_rows]``: written through ``side.eid`` (an edge's element by its
+    one entry, a node's by its implicit self loop; other elements are left as they are).  ``want_entry``: also ``g`` in entry
+    order, and with ``mul [nnz_max]`` the products ``g * mul`` -- returns ``(g_entry, gm_entry)``, None where not asked for."""
+    dev = require_gpu(a, b, row_scale, mul, d_edge, d_loop)
+    for t, name in ((a, "a"), (b, "b")):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.size(1):
+            raise ValueError(f"edge_dot: {name} must be float32 [rows, F] with unit column stride")
+    F = a.size(1)
+    if b.size(1) != F or a.size(0) < side.n_rows or b.size(0) < side.n_cols:
+        raise ValueError(f"edge_dot: a {tuple(a.shape)} / b {tuple(b.shape)} do not fit a side of {side.n_rows} rows over {side.n_cols}")
+    for t, n, name in ((row_scale, side.n_rows, "row_scale"), (mul, side.nnz_max, "mul"), (d_edge, n_edges, "d_edge"),
+                       (d_loop, side.n_rows, "d_loop")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n):
+            raise ValueError(f"edge_dot: {name} must be a contiguous float32 vector of at least {n} elements")
+    g = torch.empty(max(side.nnz_max, 1), dtype=torch.float32, device=dev) if want_entry else None
+    gm = torch.empty(max(side.nnz_max, 1), dtype=torch.float32, device=dev) if (want_entry and mul is not None) else None
+    if g is None and (d_edge is None or d_edge.numel() == 0) and d_loop is None:
+        return None, None                                           # (no edges and nothing else asked for)
+    check(load().npi_edge_dot(ptr(side.rowptr), ptr(side.col), ptr(side.rowidx), ptr(side.eid), side.n_rows, side.n_cols, side.nnz_max,
+                              n_edges, ptr(a), a.stride(0), ptr(b), b.stride(0), F, ptr(row_scale), ptr(mul) if gm is not None else 0,
+                              ptr(g), ptr(gm), ptr(d_edge), ptr(d_loop), stream_ptr(dev)), "npi_edge_dot")
+    return g, gm
+
+
+def _loop_edges(graph: CSRGraph) -> torch.Tensor:
+    """positions of the existing self-loop columns ``(k, k)`` of the edge list (padding ``(-1, -1)`` is none), kept on the graph"""
+    idx = graph.__dict__.get("_loop_edge_idx")
+    if idx is None:
+        idx = ((graph._src == graph._dst) & (graph._src >= 0)).nonzero().view(-1)
+        graph._loop_edge_idx = idx
+    return idx
+
+
+class _EdgeWeightGradFn(torch.autograd.Function):
+    """Makes ``edge_weight`` a differentiable input of a SAGEConv / GCNConv call: the identity on the layer's output, whose
+    backward hands ``dOut`` on unchanged -- so dX, dW and db come from the layer's own backward, launch for launch as without a
+    weight gradient -- and computes ``d edge_weight`` beside it (``sage_conv`` / ``gcn_conv`` have the closed forms):
+
+      * aggregate-first layers (SAGEConv, GCNConv with F_in <= F_out): ``dAgg = dOut W^T`` (one GEMM of its own: the layer's
+        backward forms ``dAgg`` only in one of its two orders, and never when fp16 x 2 applies), dotted per by-target entry
+        against the gathered rows of ``x`` -- the one tensor saved in addition (the layer itself keeps ``agg``, not ``x``);
+      * project-first GCNConv (F_in > F_out): ``xW`` is recomputed (one GEMM) and dotted against ``dOut`` at the narrower width
+        F_out, instead of keeping ``xW`` alive through the step or gathering at F_in;
+      * GCNConv(normalize=True): the chain through ``deg^-1/2`` (two ``npi_seg_rowsum_ex`` over ``g norm``, ``npi_gcn_norm_bwd``).
+
+    Existing self-loop edges take the gradient of their node's loop entry (a few lines of indexing, per such edge)."""
+
+    @staticmethod
+    def forward(ctx, out, edge_weight, x, weight, graph: CSRGraph, kind: str, relu: bool, norm):
+        ctx.graph, ctx.kind, ctx.relu, ctx.norm = graph, kind, relu, norm
+        ctx.w_shape = edge_weight.shape
+        ctx.save_for_backward(x, weight, *([out] if relu else []))
+        return out.view_as(out)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[1]:
+            return grad_out, None, None, None, None, None, None, None
+        x, weight = ctx.saved_tensors[:2]
+        graph: CSRGraph = ctx.graph
+        side = graph.by_dst
+        dev = grad_out.device
+        N, E = graph.num_nodes, graph.num_edges
+        go = _f32c(grad_out, "grad_out")
+        if ctx.relu:
+            go = relu_backward(go, ctx.saved_tensors[2])
+        x = x.detach()                                              # (may be a column block of a wider buffer: the dot takes a pitch)
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        weight = weight.detach()
+        if ctx.kind == "gcn" and weight.size(0) > weight.size(1):
+            a, b = go, linear_fwd(x, weight)                         # <dOut_i, (xW)_j> at width F_out
+        else:
+            a, b = linear_bwd_data(go, weight), x                    # <dAgg_i, x_j> at width F_in
+            if ctx.kind == "concat":
+                a = a[:, x.size(1):]                                 # the aggregate's half of [x | mean] (a row pitch of 2 F)
+        d_edge = torch.zeros(E, dtype=torch.float32, device=dev)     # padding columns and dropped edges: 0
+        d_loop = torch.zeros(N, dtype=torch.float32, device=dev) if graph.self_loops else None
+        gcn_norm = ctx.kind == "gcn" and isinstance(ctx.norm, GCNNorm)
+        if not gcn_norm:
+            # SAGEConv: the mean's divisor belongs to the row; GCNConv(normalize=False): norm IS the weight
+            edge_dot(side, a, b, E, row_scale=graph.inv_count(side) if ctx.kind != "gcn" else None, d_edge=d_edge, d_loop=d_loop)
+        else:
+            nrm: GCNNorm = ctx.norm
+            g, gm = edge_dot(side, a, b, E, mul=nrm.by_dst, want_entry=True)
+            s_dst = seg_rowsum(side, gm, 1)                                                  # entries whose TARGET is k
+            s_src = seg_rowsum(graph.by_src, gm, 1, map_=_transpose_map(graph))              # entries whose SOURCE is k
+            check(load().npi_gcn_norm_bwd(ptr(side.rowptr), ptr(side.col), ptr(side.rowidx), ptr(side.eid), N, side.nnz_max, E, ptr(g),
+                                          ptr(nrm.deg), ptr(s_dst), ptr(s_src), ptr(d_edge), ptr(d_loop), stream_ptr(dev)),
+                  "npi_gcn_norm_bwd")
+        if graph.self_loops and E > 0:
+            le = _loop_edges(graph)
+            if le.numel():
+                d_edge[le] = d_loop[graph._src[le]]
+        return grad_out, d_edge.view(ctx.w_shape), None, None, None, None, None, None
+
+
+def _with_edge_weight_grad(out, edge_weight, x, weight, graph: CSRGraph, kind: str, relu: bool = False, norm=None):
+    if edge_weight is None or not edge_weight.requires_grad or not torch.is_grad_enabled():
+        return out
+    return _EdgeWeightGradFn.apply(out, edge_weight, x, weight, graph, kind, relu, norm)
+
+
+def _check_edge_weight_grad(edge_weight, x, weight) -> bool:
+    """does this call want ``d edge_weight``?  f32 only: other storage types keep refusing (never silently detached)"""
+    if edge_weight is None or not edge_weight.requires_grad or not torch.is_grad_enabled():
+        return False
+    if x.dtype != torch.float32 or weight.dtype != torch.float32 or edge_weight.dtype != torch.float32:
+        raise NotImplementedError("gradients w.r.t. edge_weight are implemented for float32 features and weights only")
+    return True
 
 
 # ---------------------------------------------------------------------------------------------
@@ -940,12 +1060,22 @@ def sage_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, bias: Optional[
               normalize: bool = False, edge_weight: Optional[torch.Tensor] = None, relu: bool = False,
               pad_base: Optional[torch.Tensor] = None, schedule: Schedule = DEFAULT, concat: bool = False) -> torch.Tensor:
     """PyG 1.4.2 ``SAGEConv(normalize=False, concat=False).forward`` on MI355X
-    (call sites: reference ``src/classes.py:62,66,70``).  ``edge_weight [E]`` scales the messages
-    (no gradient flows to it, as in the reference's use of the layer).  ``pad_base``: the wider buffer ``x`` is the leading
-    columns of, its other columns zero (``GraphBatch.pad_base``)."""
+    (call sites: reference ``src/classes.py:62,66,70``).  ``edge_weight [E]`` scales the messages.  ``pad_base``: the wider
+    buffer ``x`` is the leading columns of, its other columns zero (``GraphBatch.pad_base``).
+
+    ``edge_weight`` is differentiable (f32 layers; bf16 storage raises ``NotImplementedError``).  With entry ``p`` of the
+    by-target CSR = (target ``i``, source ``j``, edge ``eid[p]``) and ``dAgg = dOut W^T`` (``relu`` / ``normalize`` only change
+    ``dOut`` first; ``concat=True``: the right half of ``dOut W^T``, the edge list as it is)::
+
+        g_p = inv_count[i] * <dAgg[i, :], x[j, :]>          d edge_weight[eid[p]] = g_p
+
+    (``_EdgeWeightGradFn``, ``npi_edge_dot``).  As under ``add_remaining_self_loops``, an existing self-loop edge ``(k, k)``
+    receives the gradient of node k's loop entry -- if several such edges name the same node, EACH of them receives it (what
+    the backward of autograd's ``index_put`` does) -- the loop entries of the other nodes carry the constant 1, and padding
+    columns ``(-1, -1)`` and dropped edges get 0.  The gradient has ``edge_weight``'s shape and dtype."""
     require_gpu(x, weight, bias)
-    if edge_weight is not None and edge_weight.requires_grad:
-        raise NotImplementedError("gradients w.r.t. edge_weight are not implemented")      # as gcn_conv: never silently detached
+    w_grad = _check_edge_weight_grad(edge_weight, x, weight)
+    x_in = x
     if concat:
         # PyG 1.4.2: ``concat=True`` skips add_remaining_self_loops -- the edge list as it is, weight [2 F_in, F_out]
         if isinstance(edge_index, CSRGraph):
@@ -962,6 +1092,8 @@ def sage_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, bias: Optional[
             raise ValueError(f"sage_conv(concat=True): weight must have {2 * x.size(1)} rows (got {weight.size(0)})")
         w_entry = entry_weights(graph, edge_weight, 1.0) if edge_weight is not None else None
         out = _SageConcatFn.apply(x, weight, bias, graph, w_entry)
+        if w_grad:
+            out = _with_edge_weight_grad(out, edge_weight, x_in, weight, graph, "concat")
         if relu:
             out = torch.relu(out)
         return l2_normalize(out) if normalize else out
@@ -976,6 +1108,8 @@ def sage_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, bias: Optional[
     if relu and normalize:
         raise ValueError("sage_conv: relu=True applies to the projection's output; normalize=True comes after it in PyG")
     out = _SageConvFn.apply(x, weight, bias, graph, w_entry, relu, schedule)
+    if w_grad:
+        out = _with_edge_weight_grad(out, edge_weight, x_in, weight, graph, "sage", relu)
     if normalize:
         out = l2_normalize(out)
     return out
@@ -987,7 +1121,8 @@ def sage_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, bias: Optional[
 class GCNNorm:
     """Per-entry symmetric normalisation for both orientations (``GCNConv.norm``), cacheable."""
 
-    def __init__(self, graph: CSRGraph, edge_weight: Optional[torch.Tensor] = None, improved: bool = False):
+    def __init__(self, graph: CSRGraph, edge_weight: Optional[torch.Tensor] = None, improved: bool = False, keep_deg: bool = False):
+        """``keep_deg``: keep the weighted degrees (``.deg``) -- the backward w.r.t. ``edge_weight`` needs them (``gcn_conv``)"""
         lib = load()
         dev = graph.device
         N = graph.num_nodes
@@ -1007,6 +1142,7 @@ class GCNNorm:
                                    ptr(graph.by_src.rowptr), N, side.nnz_max, ptr(nrm), s), "npi_gcn_norm")
             self.norm.append(nrm)
         self.graph = graph
+        self.deg = deg if keep_deg else None
 
     @property
     def by_dst(self) -> torch.Tensor:
@@ -1156,16 +1292,41 @@ def gcn_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, bias: Optional[t
              norm: Optional[GCNNorm] = None, schedule: Schedule = DEFAULT, normalize: bool = True) -> torch.Tensor:
     """PyG 1.4.2 ``GCNConv.forward`` (normalize=True) on MI355X.  Evaluated as ``(A_hat x) W + b`` when the input is not wider
     than the output (``_GcnAggFirstFn``: the aggregation at the narrower width, dW under the backward aggregation), in PyG's
-    literal order ``A_hat (x W) + b`` otherwise -- the same number up to fp32 rounding."""
+    literal order ``A_hat (x W) + b`` otherwise -- the same number up to fp32 rounding.
+
+    ``edge_weight`` is differentiable (f32 layers; bf16 storage raises ``NotImplementedError``; a precomputed ``norm=`` is a
+    constant, so passing it together with an ``edge_weight`` that requires grad raises ``ValueError``).  With entry ``p`` of the
+    by-target CSR = (target ``i``, source ``j``, edge ``eid[p]``), ``g_p = <dAgg[i, :], x[j, :]>``, ``dAgg = dOut W^T`` (in the
+    project-first order ``<dOut[i, :], (xW)[j, :]>``, the same number):
+
+      * ``normalize=False``: ``d edge_weight[eid[p]] = g_p`` (the edge list as it is);
+      * ``normalize=True``: ``norm_p = dis[j] w_p dis[i]``, ``dis = deg^-1/2``, ``deg[k]`` = the sum of ``w_p`` over the entries
+        whose source is k (loops included, weight 1 or -- ``improved`` -- 2).  ``g_p`` is the gradient w.r.t. ``norm_p``, and with
+        ``s[k]`` = the sum of ``g_p norm_p`` over the entries whose source is k plus that over the entries whose target is k::
+
+            d w_p = g_p dis[j] dis[i] - s[j] / (2 deg[j])          (both terms 0 where deg <= 0: PyG masks the inf)
+
+        and ``d edge_weight[eid[p]] = d w_p``.  As under ``add_remaining_self_loops``, an existing self-loop edge ``(k, k)``
+        receives the gradient of node k's loop entry -- if several such edges name the same node, EACH of them receives it (what
+        the backward of autograd's ``index_put`` does) -- the other nodes' loop entries carry the constant fill, and padding
+        columns ``(-1, -1)`` and dropped edges get 0.
+
+    The gradient has ``edge_weight``'s shape and dtype (``_EdgeWeightGradFn``: ``npi_edge_dot``, ``npi_gcn_norm_bwd``)."""
     require_gpu(x, weight, bias)
-    if edge_weight is not None and edge_weight.requires_grad:
-        raise NotImplementedError("gradients w.r.t. edge_weight are not implemented")
+    w_grad = _check_edge_weight_grad(edge_weight, x, weight)
+    if w_grad and norm is not None:
+        raise ValueError("gcn_conv: norm= is a precomputed constant; an edge_weight that requires grad cannot be passed with it "
+                         "(leave norm=None, or detach the weight)")
     if norm is None:
-        norm = GCNNorm(as_graph(edge_index, x.size(0)), edge_weight, improved) if normalize else \
+        norm = GCNNorm(as_graph(edge_index, x.size(0)), edge_weight, improved, keep_deg=w_grad) if normalize else \
             PlainWeights(edge_index, x.size(0), edge_weight)            # normalize=False: norm = edge_weight, no self loops
     if weight.size(0) <= weight.size(1):
-        return _GcnAggFirstFn.apply(x, weight, bias, norm, schedule)
-    return _GcnConvFn.apply(x, weight, bias, norm)
+        out = _GcnAggFirstFn.apply(x, weight, bias, norm, schedule)
+    else:
+        out = _GcnConvFn.apply(x, weight, bias, norm)
+    if w_grad:
+        out = _with_edge_weight_grad(out, edge_weight, x, weight, norm.graph, "gcn", False, norm)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

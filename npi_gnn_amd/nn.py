@@ -178,6 +178,13 @@ class GCNConv(nn.Module):
         if isinstance(x, GraphBatch):
             gb = _only_batch(x, edge_index, "GCNConv")
             return gb.with_x(self.forward(gb.x, gb.graph() if self.normalize else gb.edge_index, edge_weight))
+        if edge_weight is not None and edge_weight.requires_grad and torch.is_grad_enabled():
+            # a differentiable weight: the normalisation is part of the graph of this very call, not a constant to keep
+            if self.cached:
+                raise ValueError("GCNConv(cached=True) keeps the normalisation as a constant: an edge_weight that requires grad "
+                                 "needs cached=False (or detach the weight)")
+            return F_.gcn_conv(x, edge_index, self.weight, self.bias, edge_weight=edge_weight, improved=self.improved,
+                               schedule=self.schedule, normalize=self.normalize)
         norm = None
         if self.cached and self.cached_result is not None:
             E = edge_index.num_edges if isinstance(edge_index, CSRGraph) else edge_index.size(1)
