@@ -143,7 +143,9 @@ int npi_segsum_ex(const int32_t* rowptr, const int32_t* col, const int32_t* item
 /* ------------------------------------------------------------------------------------------
  * The heaviest rows of a side ("hubs") aggregated by streaming the source table once instead of gathering it.
  * A row that holds a sizeable fraction of all columns re-reads a table no cache can hold; streamed, every source row is
- * fetched once and added into the accumulators of the hubs its mask names.  One-table sides with n_cols == N, f32, F = 256.
+ * fetched once and added into the accumulators of the hubs its mask names.  f32, F = 256; N rows over a table of n_cols rows
+ * (N == n_cols for the sides of a square graph; the two id spaces of a bipartite side are independent: every kernel below walks
+ * rows with N and masks / table rows with n_cols).
  *
  * npi_hub_plan (once per graph and side): the up to h_max <= NPI_HUB_MAX rows with the most entries among the rows with at
  * least min_degree entries (ties: the lower row first), minus rows that hold a column twice (a mask bit cannot count twice).
@@ -234,6 +236,21 @@ int npi_gcn_norm_bwd(const int32_t* rowptr, const int32_t* col, const int32_t* r
 int npi_hold_cus(int workgroups, int64_t nanoseconds, uint64_t* start_word, void* stream);
 int npi_relu_backward(const float* dy, int64_t ldd, const float* y, int64_t ldy, int64_t M, int64_t F, float* dz, int64_t ldz,
                       void* stream);
+
+/* Row gather into a column block of a wider buffer -- replaces the left half of `torch.cat([x[0][res_n_id], aggr_out], dim=-1)`
+ * (PyG 1.4.2 SAGEConv.update, the bipartite `(x_src, x_dst)` form with concat=True): where torch gathers `x[0][res_n_id]` into a
+ * tensor of its own and copies it again into the concatenation, this writes every gathered row once, straight into the left
+ * half of the [n, 2F] operand of the projection GEMM (npi_segsum_ex writes the mean into the right half):
+ *     out[i, 0:F] = x[idx[i], 0:F]     i < n;  x [n_src, F] (ldx), out [n, F] (ldo), leading dimensions in elements
+ *   idx    : int64 [n] row ids (`res_n_id` as PyG hands it over) or NULL: the identity (then n <= n_src is expected)
+ *   dtype  : NPI_F32 or NPI_BF16.  16-byte lanes when F % 4 == 0 (f32) / F % 8 == 0 (bf16) and both bases and pitches are
+ *            16-byte aligned; a guarded per-element path otherwise
+ *   status : int32 device word as npi_csr_build_ex's (may be NULL): an id outside [0, n_src) writes a ZERO row and ORs
+ *            NPI_STATUS_BAD_ROW_ID into it (torch's index_select raises there); the word is never cleared here
+ * One pass, no synchronisation, nothing allocated. */
+#define NPI_STATUS_BAD_ROW_ID 8
+int npi_rows_gather(const void* x, int64_t ldx, int64_t n_src, const int64_t* idx, int64_t n, int64_t F, void* out, int64_t ldo,
+                    int dtype, int32_t* status, void* stream);
 
 /* SAGEConv(normalize=True): y_i = x_i / max(||x_i||_2, eps) -- torch.nn.functional.normalize(out, p=2, dim=-1) at the end of
  * PyG 1.4.2 SAGEConv.update (the reference constructs its layers with the default normalize=False, src/classes.py:48-52; the

@@ -7,8 +7,8 @@ Only what the path needs: ``csrc/`` (hand-written gfx950 kernels + the C ABI of
 be imported.
 """
 from ._lib import LIB_PATH, NpiError, load  # noqa: F401
-from .graph import CSRGraph, GraphBatch, as_graph, set_debug  # noqa: F401
-from .functional import GCNNorm, gat_conv, gcn_conv, sage_conv, segsum  # noqa: F401
+from .graph import BipartiteGraph, CSRGraph, GraphBatch, as_graph, set_debug  # noqa: F401
+from .functional import GCNNorm, gat_conv, gat_conv_bipartite, gcn_conv, sage_conv, sage_conv_bipartite, segsum  # noqa: F401
 from .nn import GATConv, GCNConv, SAGEConv  # noqa: F401
 from .schedule import Schedule  # noqa: F401
 from .graphed import GraphedStack  # noqa: F401

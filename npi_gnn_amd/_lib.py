@@ -22,6 +22,7 @@ NPI_GEMM_A_ZERO_PADDED = 4   # A stored with zero pad columns up to a multiple o
 NPI_GEMM_WORKSPACE_PREPARED = 8   # the workspace already holds npi_linear_prepare's copy of this weight matrix
 NPI_GEMM_SPLIT_F16X2 = 16         # two fp16 pieces per operand, three matrix products per tile pair (needs the row scales of A)
 NPI_PREPARE_F16X2 = 4             # npi_linear_prepare(which | this): the fp16 x 2 planes of the weight matrix
+NPI_STATUS_BAD_ROW_ID = 8         # status bit of npi_rows_gather: a row id outside the source table
 NPI_HUB_MAX = 128                 # hubs per plan (npi_hub_plan; mask words of NPI_HUB_MAX / 32 per source row)
 
 
@@ -62,6 +63,7 @@ PROTOTYPES = {
     "npi_edge_dot": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "npi_gcn_norm_bwd": (c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "npi_relu_backward": (c_int, [_P, _I, _P, _I, _I, _I, _P, _I, _P]),
+    "npi_rows_gather": (c_int, [_P, _I, _I, _P, _I, _I, _P, _I, c_int, _P, _P]),
     "npi_l2_normalize_rows": (c_int, [_P, _I, _I, _I, c_float, _P, _I, _P, _P]),
     "npi_l2_normalize_rows_bwd": (c_int, [_P, _I, _P, _I, _P, _I, _I, c_float, _P, _I, _P]),
     "npi_colsum_workspace_elems": (_I, [_I, _I]),

@@ -15,7 +15,7 @@ import torch
 
 from ._lib import (NPI_BF16, NPI_F32, NPI_GEMM_A_ZERO_PADDED, NPI_GEMM_EXACT_F32, NPI_GEMM_RESERVE_CUS, NPI_GEMM_SPLIT_F16X2,
                    NPI_GEMM_WORKSPACE_PREPARED, NPI_PREPARE_F16X2, check, load, ptr, require_gpu, stream_ptr)
-from .graph import CSRGraph, CSRSide, HubPlan, as_graph
+from .graph import BipartiteGraph, CSRGraph, CSRSide, GraphBatch, HubPlan, as_graph, note_status
 from .schedule import DEFAULT, Schedule
 
 
@@ -153,7 +153,9 @@ def segsum(graph: CSRGraph, side: CSRSide, x: torch.Tensor, w: Optional[torch.Te
     N, F = side.n_rows, x.size(1)                  # `graph` may be None for a stand-alone (sharded) side
     split = x.size(0)
     if x2 is not None:
-        x2 = _fc(x2, "x2", x)
+        x2 = _fcp(x2, "x2")                         # (may be a column block of the buffer x is a block of: same pitch)
+        if x2.dtype != x.dtype:
+            raise TypeError(f"x2 is {x2.dtype} but the other operand is {x.dtype}")
         if x2.size(1) != F:
             raise ValueError("x2 must have the width of x")
         if x2.stride(0) != x.stride(0):
@@ -750,7 +752,7 @@ def _backward_aggregate_first(graph, tside: CSRSide, w_t: Optional[torch.Tensor]
     ``w_t`` belongs to ``hub.light`` and the hub rows take the mean's divisors as a column scale.  Returns ``(dx, dw, db)``."""
     dev = grad_out.device
     cs = graph.inv_count(graph.by_dst) if hub is not None else None
-    N, Nout = grad_out.shape
+    N, Nout = tside.n_rows, grad_out.size(1)                     # (rows of dX: the SOURCE id space -- grad_out's own on a square graph)
     t = torch.empty((N, Nout), dtype=torch.float32, device=dev)
     t_scales = torch.empty(N, dtype=torch.float32, device=dev)
     dw = db = None
@@ -842,7 +844,7 @@ class _EdgeWeightGradFn(torch.autograd.Function):
         graph: CSRGraph = ctx.graph
         side = graph.by_dst
         dev = grad_out.device
-        N, E = graph.num_nodes, graph.num_edges
+        N, E = side.n_rows, graph.num_edges
         go = _f32c(grad_out, "grad_out")
         if ctx.relu:
             go = relu_backward(go, ctx.saved_tensors[2])
@@ -1920,3 +1922,427 @@ def gat_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, att: torch.Tenso
     out = out + bias if bias is not None else out
     out = torch.relu(out) if relu else out
     return (out, None) if return_scales else out
+
+
+# ---------------------------------------------------------------------------------------------
+# Bipartite ``(x_src, x_dst)`` / ``size=`` form of SAGEConv and GATConv (PyG 1.4.2 MessagePassing.propagate with a size pair)
+# ---------------------------------------------------------------------------------------------
+# Everything under these layers already has two id spaces -- the CSR build, the aggregation (plain and hub-streamed), the per-entry
+# dots, the GAT statistics / aggregation / backward kernels and the GEMMs, built for the sharded layers -- so the layers below are
+# compositions of those entry points over the sides of a ``graph.BipartiteGraph``.  The one new kernel is ``npi_rows_gather``.
+def rows_gather(x: torch.Tensor, idx: Optional[torch.Tensor], out: torch.Tensor, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[i, :] = x[idx[i], :]`` (``idx`` None: the identity) in one pass, ``out`` possibly a column block of a wider buffer
+    (``npi_rows_gather``).  f32 or bf16, unit column stride.  An id outside ``[0, x.size(0))`` gives a ZERO row and raises
+    ``NPI_STATUS_BAD_ROW_ID`` in ``status`` (an int32 device word, e.g. a side's; filed with ``note_status`` here: the host sees it
+    at its next device read); no synchronisation."""
+    dev = require_gpu(x, idx, out, status)
+    for t, name in ((x, "x"), (out, "out")):
+        if t.dtype not in (torch.float32, torch.bfloat16) or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.size(1):
+            raise ValueError(f"rows_gather: {name} must be float32 / bfloat16 [rows, F] with unit column stride")
+    n, F = out.shape
+    if x.dtype != out.dtype or x.size(1) != F or x.device != out.device:
+        raise ValueError("rows_gather: x and out must share dtype, width and device")
+    if idx is not None:
+        if idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() != n or not idx.is_contiguous():
+            raise ValueError(f"rows_gather: idx must be a contiguous LongTensor [{n}]")
+    elif x.size(0) < n:
+        raise ValueError("rows_gather: the identity gather needs at least as many source rows as output rows")
+    if status is not None and (status.dtype != torch.int32 or status.numel() < 1):
+        raise ValueError("rows_gather: status must be an int32 device word")
+    check(load().npi_rows_gather(ptr(x), x.stride(0), x.size(0), ptr(idx), n, F, ptr(out), out.stride(0), _code(x), ptr(status),
+                                 stream_ptr(dev)), "npi_rows_gather")
+    if status is not None and idx is not None:
+        note_status(status)
+    return out
+
+
+def _pair_sizes(x, size, who: str, edge_index=None):
+    """PyG 1.4.2 size resolution of the pair form: ``(x_src, x_dst or None, N_src, N_dst)``; every mismatch is a ValueError.
+    A ``BipartiteGraph`` in place of ``edge_index`` names ``N_dst`` where neither ``x_dst`` nor ``size[1]`` does."""
+    if len(x) != 2:
+        raise ValueError(f"{who}: the bipartite form takes x = (x_src, x_dst) (x_dst may be None)")
+    x_src, x_dst = x
+    if x_src is None:
+        raise ValueError(f"{who}: x_src (x[0]) is required: the messages are gathered from it")
+    for t, name in ((x_src, "x_src"), (x_dst, "x_dst")):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dim() != 2):
+            raise ValueError(f"{who}: {name} must be a [rows, F] tensor")
+    if size is not None and (not isinstance(size, (tuple, list)) or len(size) != 2):
+        raise ValueError(f"{who}: size must be a pair (N_src, N_dst)")
+    s0, s1 = (None, None) if size is None else size
+    n_src = int(x_src.size(0))
+    if s0 is not None and int(s0) != n_src:
+        raise ValueError(f"{who}: x_src has {n_src} rows, size[0] is {int(s0)}")
+    if x_dst is not None:
+        n_dst = int(x_dst.size(0))
+        if s1 is not None and int(s1) != n_dst:
+            raise ValueError(f"{who}: x_dst has {n_dst} rows, size[1] is {int(s1)}")
+    else:
+        n_dst = int(s1) if s1 is not None else (edge_index.num_dst if isinstance(edge_index, BipartiteGraph) else n_src)
+    return x_src, x_dst, n_src, n_dst
+
+
+def _as_bipartite(edge_index, n_src: int, n_dst: int, who: str) -> BipartiteGraph:
+    if isinstance(edge_index, (CSRGraph, GraphBatch)):
+        raise TypeError(f"{who}: a {type(edge_index).__name__} holds ONE id space (self loops included); the pair form (x_src, x_dst) "
+                        "takes the [2, E] edge_index or a BipartiteGraph")
+    if isinstance(edge_index, BipartiteGraph):
+        if edge_index.size != (n_src, n_dst):
+            raise ValueError(f"{who}: the BipartiteGraph was built for size {edge_index.size}, the features give {(n_src, n_dst)}")
+        return edge_index
+    if not isinstance(edge_index, torch.Tensor):
+        raise TypeError(f"{who}: edge_index must be the [2, E] LongTensor or a BipartiteGraph")
+    return BipartiteGraph(edge_index, (n_src, n_dst))
+
+
+def _bipartite_entry_weights(graph: BipartiteGraph, edge_weight: torch.Tensor):
+    """``edge_weight [E]`` in the entry order of both sides (there are no loop entries): ``[by_dst, by_src]``, and the flat weight"""
+    dev = require_gpu(edge_weight)
+    ew = _f32c(edge_weight.detach(), "edge_weight").view(-1)
+    if ew.numel() != graph.num_edges:
+        raise ValueError(f"edge_weight has {ew.numel()} entries, edge_index {graph.num_edges} columns")
+    out = []
+    for side in (graph.by_dst, graph.by_src):
+        we = torch.empty(max(side.nnz_max, 1), dtype=torch.float32, device=dev)
+        check(load().npi_entry_weights(ptr(side.eid), ptr(side.rowidx), ptr(side.rowptr), ptr(ew), 0, 1.0, side.n_rows, side.nnz_max,
+                                       ptr(we), stream_ptr(dev)), "npi_entry_weights")
+        out.append(we)
+    return out, ew
+
+
+class _SageBipartiteFn(torch.autograd.Function):
+    """``out = mean_{e: j -> i}(w_e x_src[j]) @ W + b`` over a ``BipartiteGraph`` -- the structure of ``_SageConvFn`` on two id
+    spaces: aggregation (hub-streamed where the side has a plan) writing the row scales of its output, the projection on two fp16
+    pieces per operand where ``_f16x2`` / ``segsum_scales_ok`` allow, and the backward aggregate-first
+    (``dX_src = (A^T D^-1 dOut) W^T`` over ``by_src``) under the same conditions, per-op otherwise; dW beside the transposed
+    aggregation on the side stream by ``_SageConvFn``'s rule."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, graph: BipartiteGraph, w_entry=None, relu: bool = False, sch: Schedule = DEFAULT):
+        d = graph.by_dst
+        ctx.graph, ctx.relu, ctx.sch = graph, relu, sch
+        ctx.w_src = w_entry[1] if w_entry else None
+        ctx.has_bias = bias is not None
+        w_dst = w_entry[0] if w_entry else None
+        f16 = _f16x2(sch, d.n_rows, weight.size(0), weight.size(1), x.dtype) and segsum_scales_ok(d, x)
+        ctx.f16 = f16
+        if f16:
+            agg = torch.empty((d.n_rows, x.size(1)), dtype=x.dtype, device=x.device)
+            scales = torch.empty(d.n_rows, dtype=torch.float32, device=x.device)
+            hub = hub_plan_for(graph, d, x, agg) if not w_entry else None
+            segsum(graph, d, x, w=w_dst, mean=True, out=agg, scales_out=scales, hub=hub)
+            wsf, ctx.ws_bwd = prepare_weight(weight, backward=ctx.needs_input_grad[0], f16=True)
+            out = linear_fwd(agg, weight, bias, relu=relu, ws=wsf, a_scales=scales)
+        else:
+            fl = _gflags(sch)
+            agg = segsum(graph, d, x, w=w_dst, mean=True, hub=hub_plan_for(graph, d, x) if not w_entry else None)
+            wsf, ctx.ws_bwd = (None, None) if fl else prepare_weight(weight, backward=ctx.needs_input_grad[0])
+            out = linear_fwd(agg, weight, bias, relu=relu, ws=wsf, flags=fl)
+        ctx.save_for_backward(agg, weight, *([out] if relu else []))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        agg, weight = ctx.saved_tensors[:2]
+        graph: BipartiteGraph = ctx.graph
+        grad_out = _f32c(grad_out, "grad_out")
+        want_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
+        want_x = ctx.needs_input_grad[0]
+        overlap = want_w and want_x and _overlaps(ctx.sch, grad_out.size(0))
+        fl = _gflags(ctx.sch)
+        if ctx.relu:
+            grad_out = relu_backward(grad_out, ctx.saved_tensors[2])
+        dx = dw = db = None
+        if want_x:
+            ts = graph.by_src
+            if (_aggregate_first_ok(ctx.sch, ctx.f16, weight, grad_out, ts, ctx.ws_bwd)
+                    and f16x2_shape(ts.n_rows, grad_out.size(1), weight.size(0))):
+                hub = hub_plan_for(graph, ts, grad_out) if ctx.w_src is None else None
+                w_t = mean_bwd_weights(graph, ts if hub is None else hub.light, ctx.w_src)
+                dx, dw, db = _backward_aggregate_first(graph, ts, w_t, agg, weight, grad_out, ctx.ws_bwd, want_w, ctx.has_bias, overlap,
+                                                       hub=hub)
+                return dx, dw, db, None, None, None, None
+        ws_bwd = ctx.ws_bwd if not (isinstance(ctx.ws_bwd, Planes) and ctx.ws_bwd.f16) else None
+        if want_w and not overlap:
+            dw, db = linear_bwd_weight(agg, grad_out, want_bias=ctx.has_bias, flags=fl)
+        if want_x:
+            dagg = linear_bwd_data(grad_out, weight, rowscale=graph.inv_count(), ws=ws_bwd, flags=fl)       # D^-1 dOut W^T  [N_dst, F]
+            hub = hub_plan_for(graph, ts, dagg) if ctx.w_src is None else None
+            if overlap:
+                dev = grad_out.device
+                main = torch.cuda.current_stream(dev)
+                side = _side_stream(dev)
+                side.wait_stream(main)
+                dw, db = linear_bwd_weight(agg, grad_out, want_bias=ctx.has_bias, shared=True, flags=fl)
+                with torch.cuda.stream(side):
+                    dx = segsum(graph, ts, dagg, w=ctx.w_src, mean=False, hub=hub)
+                dagg.record_stream(side)
+                dx.record_stream(main)
+                main.wait_stream(side)
+            else:
+                dx = segsum(graph, ts, dagg, w=ctx.w_src, mean=False, hub=hub)
+        return dx, dw, db, None, None, None, None
+
+
+def _root_weights(graph: BipartiteGraph, side: CSRSide, ew: Optional[torch.Tensor]) -> torch.Tensor:
+    """per-entry weights of ``BipartiteGraph.root_side``: ``inv_count[i]`` (times the edge's weight) for an edge entry whose target
+    is i, 1 for a root entry -- ``npi_entry_col_scale`` over the table ``[inv_count ; ones]``; without edge weights kept on the side"""
+    if ew is None and "_root_w" in side.__dict__:
+        return side._root_w
+    dev, nd = graph.device, graph.num_dst
+    table = torch.cat([graph.inv_count(), torch.ones(nd, dtype=torch.float32, device=dev)])
+    w_in = None
+    if ew is not None:
+        ext = torch.cat([ew, torch.ones(nd, dtype=torch.float32, device=dev)])             # eid of a root entry: E + i
+        w_in = torch.empty(max(side.nnz_max, 1), dtype=torch.float32, device=dev)
+        check(load().npi_entry_weights(ptr(side.eid), ptr(side.rowidx), ptr(side.rowptr), ptr(ext), 0, 1.0, side.n_rows, side.nnz_max,
+                                       ptr(w_in), stream_ptr(dev)), "npi_entry_weights")
+    out = torch.empty(max(side.nnz_max, 1), dtype=torch.float32, device=dev)
+    check(load().npi_entry_col_scale(ptr(side.col), ptr(side.rowptr), ptr(table), ptr(w_in), side.n_rows, 2 * nd, side.nnz_max,
+                                     ptr(out), stream_ptr(dev)), "npi_entry_col_scale")
+    if ew is None:
+        side._root_w = out
+    return out
+
+
+class _SageBipartiteConcatFn(torch.autograd.Function):
+    """``out = [x_src[res_n_id] | mean_{e: j -> i}(w_e x_src[j])] @ W[2F, Fo] + b``: the gathered roots (``npi_rows_gather``) and the
+    mean (``segsum(out=)``) are written straight into the two halves of the ``[N_dst, 2F]`` operand of ONE projection GEMM.  The
+    backward's ``dX_src`` -- the transposed aggregation of ``dcat[:, F:] / count`` plus the scatter of ``dcat[:, :F]`` through
+    ``res_n_id`` -- is ONE segmented sum over ``BipartiteGraph.root_side`` with the two halves of ``dcat`` as the two parts of its
+    table: a fixed order, no float atomics, bitwise reproducible; duplicates in ``res_n_id`` accumulate."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, graph: BipartiteGraph, res_n_id, w_entry=None, ew=None):
+        d = graph.by_dst
+        F = x.size(1)
+        cat = torch.empty((d.n_rows, 2 * F), dtype=x.dtype, device=x.device)
+        rows_gather(x, res_n_id, cat[:, :F], status=d.status)
+        segsum(graph, d, x, w=w_entry[0] if w_entry else None, mean=True, out=cat[:, F:])
+        out = linear_fwd(cat, weight, bias)
+        ctx.graph, ctx.F, ctx.res_n_id, ctx.ew = graph, F, res_n_id, ew
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(cat, weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        cat, weight = ctx.saved_tensors
+        graph: BipartiteGraph = ctx.graph
+        F = ctx.F
+        grad_out = _f32c(grad_out, "grad_out")
+        dx = dw = db = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            dw, db = linear_bwd_weight(cat, grad_out, want_bias=ctx.has_bias)
+        if ctx.needs_input_grad[0]:
+            dcat = linear_bwd_data(grad_out, weight)                              # [N_dst, 2F]: [d root | d mean]
+            side = graph.root_side(ctx.res_n_id)
+            dx = segsum(graph, side, dcat[:, F:], w=_root_weights(graph, side, ctx.ew), x2=dcat[:, :F], mean=False)
+        return dx, dw, db, None, None, None, None
+
+
+def sage_conv_bipartite(x, edge_index, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, size=None,
+                        res_n_id: Optional[torch.Tensor] = None, normalize: bool = False, concat: bool = False,
+                        edge_weight: Optional[torch.Tensor] = None, relu: bool = False, schedule: Schedule = DEFAULT) -> torch.Tensor:
+    """PyG 1.4.2 ``SAGEConv.forward((x_src, x_dst), edge_index, edge_weight, size, res_n_id)``: ``edge_index[0]`` indexes
+    ``x_src``, ``edge_index[1]`` the ``N_dst`` output rows (``N_dst``: ``x_dst``'s rows, else ``size[1]``, else ``N_src``).  No self
+    loop is added or removed; a target without an in-edge gets ``bias`` (or 0).
+
+    ``concat=False``: ``mean_{e: j -> i}(w_e x_src[j]) @ weight + bias`` (the mean divides by the in-edge count); ``x_dst`` is not
+    read.  ``concat=True``: ``[x_src[res_n_id] | mean] @ weight[2F, out] + bias`` with ``res_n_id`` a LongTensor ``[N_dst]`` of rows
+    of ``x_src`` (an id out of range gives a zero root row and is reported like a dropped edge, ``graph.note_status``).
+    ``edge_index``: the ``[2, E]`` tensor (sorted here, every call) or a ``BipartiteGraph``.  float32 only.  Gradients: ``x_src``,
+    ``weight``, ``bias`` and ``edge_weight`` (``d edge_weight[e] = inv_count[i] <dAgg[i], x_src[j]>``, ``npi_edge_dot`` over the
+    by-target side)."""
+    who = "sage_conv_bipartite"
+    x_src, x_dst, n_src, n_dst = _pair_sizes(x, size, who, edge_index)
+    if concat and res_n_id is None:
+        raise ValueError(f"{who}(concat=True): res_n_id [N_dst] is required -- the rows of x_src that are the targets' own features")
+    if relu and normalize and not concat:
+        raise ValueError(f"{who}: relu=True applies to the projection's output; normalize=True comes after it in PyG")
+    if isinstance(edge_index, (CSRGraph, GraphBatch)):
+        _as_bipartite(edge_index, n_src, n_dst, who)
+    if weight.size(0) != (2 if concat else 1) * x_src.size(1):
+        raise ValueError(f"{who}: weight must have {(2 if concat else 1) * x_src.size(1)} rows (got {weight.size(0)})")
+    if concat and (res_n_id.dtype != torch.int64 or res_n_id.dim() != 1 or res_n_id.numel() != n_dst):
+        raise ValueError(f"{who}: res_n_id must be a LongTensor [{n_dst}] (one row of x_src per target)")
+    require_gpu(x_src, weight, bias, edge_weight, res_n_id)
+    if x_src.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise NotImplementedError(f"{who}: the bipartite layers run on float32 features and weights (bf16 storage is not implemented "
+                                  "for the pair form)")
+    w_grad = _check_edge_weight_grad(edge_weight, x_src, weight)
+    graph = _as_bipartite(edge_index, n_src, n_dst, who)
+    x_in = x_src
+    x_src = _f32c(x_src, "x_src")
+    w_entry = ew = None
+    if edge_weight is not None:
+        w_entry, ew = _bipartite_entry_weights(graph, edge_weight)
+    if concat:
+        out = _SageBipartiteConcatFn.apply(x_src, weight, bias, graph, res_n_id.contiguous(), w_entry, ew)
+        if w_grad:
+            out = _with_edge_weight_grad(out, edge_weight, x_in, weight, graph, "concat")
+        if relu:
+            out = torch.relu(out)
+        return l2_normalize(out) if normalize else out
+    out = _SageBipartiteFn.apply(x_src, weight, bias, graph, w_entry, relu, schedule)
+    if w_grad:
+        out = _with_edge_weight_grad(out, edge_weight, x_in, weight, graph, "sage", relu)
+    return l2_normalize(out) if normalize else out
+
+
+class _GatBipartiteFn(torch.autograd.Function):
+    """GATConv over a ``BipartiteGraph``: ``h_src = x_src W``, ``h_dst = x_dst W`` (the same W; ``shared``: ``x_dst`` IS ``x_src``,
+    projected once), ``e = leaky_relu(<h_dst[i], att[:C]> + <h_src[j], att[C:]>)`` (no target term when ``x_dst`` is None), softmax
+    over the in-edges of i with the ``+1e-16`` denominator, ``out[i] = sum alpha h_src[j]`` (+ bias).  Composed from the per-op entry
+    points, which take row and column tables separately: one head takes the fused aggregation (statistics inside the launch) and,
+    on the shapes ``gat_fused_shape`` names, the packed fused backward over ``by_src`` (d h_src, dz and its by-source row sums in
+    one gather pass); ``g_dst`` -- needed only when there is a target term -- is one ``npi_gat_edge_grad`` pass over ``by_dst``."""
+
+    @staticmethod
+    def forward(ctx, x_src, x_dst, weight, att, bias, graph: BipartiteGraph, heads: int, slope: float, relu: bool, sch: Schedule,
+                shared: bool):
+        H = int(heads)
+        C = weight.size(1) // H
+        dev = x_src.device
+        att2 = _f32c(att.reshape(H, 2 * C), "att")
+        d = graph.by_dst
+        fl = _gflags(sch)
+        h_src = linear_fwd(x_src, weight, flags=fl)
+        a_own, a_src = gat_scores(h_src, att2, H, C)
+        h_dst = None
+        if shared:
+            a_dst = a_own
+        elif x_dst is not None:
+            h_dst = linear_fwd(x_dst, weight, flags=fl)
+            a_dst, _ = gat_scores(h_dst, att2, H, C)
+        else:
+            a_dst = torch.zeros((d.n_rows, H), dtype=torch.float32, device=dev)
+        del a_own
+        if d.nnz_max == 0:                                       # no edges: every row is empty -- zeros (+ bias)
+            m = torch.zeros((d.n_rows, H), dtype=torch.float32, device=dev)
+            s = torch.zeros((d.n_rows, H), dtype=torch.float32, device=dev)
+            out = torch.zeros((d.n_rows, H * C), dtype=torch.float32, device=dev)
+            if bias is not None:
+                out += bias.view(1, -1)
+            if relu:
+                out = torch.relu_(out)
+        elif H == 1 and C % 4 == 0 and C <= 256 and sch.gat_fused_stats:
+            out, m, s = gat_aggregate_fused(d, h_src, None, C, a_dst, att2, slope, bias=bias, relu=relu)
+        else:
+            m, s = gat_softmax_stats(d, a_dst, a_src, H, slope)
+            out = _gat_aggregate(graph, d, h_src, H, C, a_dst, a_src, m, s, slope, False, bias=bias)
+            if relu:
+                out = torch.relu_(out)
+        ctx.graph, ctx.H, ctx.C, ctx.slope, ctx.sch = graph, H, C, float(slope), sch
+        ctx.relu, ctx.shared, ctx.has_dst, ctx.has_bias = bool(relu), bool(shared), x_dst is not None, bias is not None
+        empty = torch.empty(0, device=dev)
+        ctx.save_for_backward(x_src, x_dst if x_dst is not None else empty, weight, att2, h_src, h_dst if h_dst is not None else empty,
+                              a_dst, a_src, m, s, out, bias if bias is not None else empty)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x_src, x_dst, weight, att2, h_src, h_dst, a_dst, a_src, m, s, out, bias = ctx.saved_tensors
+        graph: BipartiteGraph = ctx.graph
+        H, C, slope, sch = ctx.H, ctx.C, ctx.slope, ctx.sch
+        dev = x_src.device
+        grad_out = _f32c(grad_out, "grad_out")
+        d, sr = graph.by_dst, graph.by_src
+        n_src, n_dst = sr.n_rows, d.n_rows
+        want_db = ctx.has_bias and ctx.needs_input_grad[4]
+        if ctx.relu:
+            D, db, grad_out = gat_rowdot_colsum(grad_out, out, bias if ctx.has_bias else None, H, C, want_colsum=want_db, relu_mask=True)
+        else:
+            D, db = gat_rowdot_colsum(grad_out, out, bias if ctx.has_bias else None, H, C, want_colsum=want_db)
+        target_term = ctx.shared or ctx.has_dst
+        zeros = lambda n: torch.zeros((n, H), dtype=torch.float32, device=dev)            # noqa: E731
+        g_dst = None
+        if d.nnz_max == 0:
+            dh = torch.zeros((n_src, H * C), dtype=torch.float32, device=dev)
+            g_src = zeros(n_src)
+            g_dst = zeros(n_dst)
+        else:
+            if gat_fused_shape(H, C):
+                tpack = gat_pack_targets(a_dst, m, s, D)                                 # [N_dst H, 4], gathered by column id
+                g_src = torch.empty((n_src, 1), dtype=torch.float32, device=dev) if (H == 1 and sch.gat_src_rowsum_fused) else None
+                dh, dz = gat_backward_fused_packed(sr, grad_out, None, h_src, C, tpack, a_src, slope, H=H, rowsum_out=g_src)
+                if g_src is None:
+                    g_src = seg_rowsum(sr, dz.view(-1, H), H)
+            else:
+                # rows are sources: dz recomputed in the orientation it is summed in, then the by-source aggregation of dOut
+                dz = gat_edge_grad(sr, grad_out, None, h_src, H, C, a_dst, a_src, m, s, D, slope, 1)
+                g_src = seg_rowsum(sr, dz, H)
+                dh = _gat_aggregate(graph, sr, grad_out, H, C, a_dst, a_src, m, s, slope, True)
+            del dz
+            if target_term:
+                dz = gat_edge_grad(d, h_src, None, grad_out, H, C, a_dst, a_src, m, s, D, slope, 0)
+                g_dst = seg_rowsum(d, dz, H)
+                del dz
+        fl = _gflags(sch)
+        want_w, want_att = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        dx_src = dx_dst = dw = datt = None
+        if ctx.shared:
+            # one id space: d h_j = sum_i alpha_ij dOut_i + g_dst[j] att[:C] + g_src[j] att[C:]
+            gat_rank1_add(dh, g_dst, g_src, att2, H, C)
+            if want_att:
+                datt = gat_att_grad(h_src, g_dst, g_src, H, C)
+            if want_w:
+                dw = linear_bwd_weight(x_src, dh, want_bias=False, flags=fl)[0]
+            if ctx.needs_input_grad[0]:
+                dx_src = linear_bwd_data(dh, weight, flags=fl)
+        else:
+            gat_rank1_add(dh, zeros(n_src), g_src, att2, H, C)                           # d h_src_j += g_src[j] att[C:]
+            if want_att:
+                datt = gat_att_grad(h_src, zeros(n_src), g_src, H, C)                    # (its [:C] half is zero)
+            if want_w:
+                dw = linear_bwd_weight(x_src, dh, want_bias=False, flags=fl)[0]
+            if ctx.needs_input_grad[0]:
+                dx_src = linear_bwd_data(dh, weight, flags=fl)
+            if ctx.has_dst and (want_w or want_att or ctx.needs_input_grad[1]):
+                dh_dst = torch.zeros((n_dst, H * C), dtype=torch.float32, device=dev)
+                gat_rank1_add(dh_dst, g_dst, zeros(n_dst), att2, H, C)                   # d h_dst_i = g_dst[i] att[:C]
+                if want_att:
+                    datt = datt + gat_att_grad(h_dst, g_dst, zeros(n_dst), H, C)
+                if want_w:
+                    dw = dw + linear_bwd_weight(x_dst, dh_dst, want_bias=False, flags=fl)[0]      # dW = x_src^T dh_src + x_dst^T dh_dst
+                if ctx.needs_input_grad[1]:
+                    dx_dst = linear_bwd_data(dh_dst, weight, flags=fl)
+        if datt is not None:
+            datt = datt.view(1, H, 2 * C)
+        return dx_src, dx_dst, dw, datt, db, None, None, None, None, None, None
+
+
+def gat_conv_bipartite(x, edge_index, weight: torch.Tensor, att: torch.Tensor, bias: Optional[torch.Tensor] = None, size=None,
+                       heads: int = 1, concat: bool = True, negative_slope: float = 0.2, relu: bool = False,
+                       schedule: Schedule = DEFAULT, shared: bool = False):
+    """PyG 1.4.2 ``GATConv.forward((x_src, x_dst), edge_index, size)``: attention over the edge list AS IT IS (with ``size`` given
+    PyG neither removes nor adds self loops), ``edge_index[0]`` indexing ``x_src`` and ``edge_index[1]`` the ``N_dst`` output rows.
+    ``x_dst`` None: the score has no target term and ``att[..., :C]`` gets a zero gradient.  ``shared``: ``x_dst`` is ``x_src``
+    itself (a tensor ``x`` with ``size=(N, N)``): projected once.  A target without an in-edge gets ``bias`` (or 0).  No attention
+    dropout.  Gradients: ``x_src``, ``x_dst``, ``weight``, ``att``, ``bias``."""
+    who = "gat_conv_bipartite"
+    x_src, x_dst, n_src, n_dst = _pair_sizes(x, size, who, edge_index)
+    if shared and (x_dst is not None and x_dst is not x_src or n_dst != n_src):
+        raise ValueError(f"{who}: shared=True means x_dst is x_src (one table, size (N, N))")
+    if isinstance(edge_index, (CSRGraph, GraphBatch)):
+        _as_bipartite(edge_index, n_src, n_dst, who)
+    if x_dst is not None and x_dst.size(1) != x_src.size(1):
+        raise ValueError(f"{who}: x_src and x_dst share the weight matrix, so they must have the same width")
+    if weight.size(0) != x_src.size(1) or weight.size(1) % int(heads) or att.numel() != 2 * weight.size(1):
+        raise ValueError(f"{who}: weight must be [F_in, heads * out] and att [1, heads, 2 * out]")
+    require_gpu(x_src, x_dst, weight, att, bias)
+    if x_src.dtype != torch.float32 or weight.dtype != torch.float32 or (x_dst is not None and x_dst.dtype != torch.float32):
+        raise NotImplementedError(f"{who}: the bipartite layers run on float32 features and weights (bf16 storage is not implemented "
+                                  "for the pair form)")
+    graph = _as_bipartite(edge_index, n_src, n_dst, who)
+    if x_dst is x_src and x_dst is not None:
+        shared = True
+    x_src = _f32c(x_src, "x_src")
+    x_dst = None if (shared or x_dst is None) else _f32c(x_dst, "x_dst")
+    fused_bias = bias if concat else None
+    out = _GatBipartiteFn.apply(x_src, x_dst, weight, att, fused_bias, graph, heads, negative_slope, relu and concat, schedule, shared)
+    if concat:
+        return out
+    out = out.view(n_dst, int(heads), -1).mean(dim=1)
+    out = out + bias if bias is not None else out
+    return torch.relu(out) if relu else out

@@ -49,6 +49,9 @@ def raise_on_status(values) -> None:
     if any(int(v) & 1 for v in values):
         raise IndexError("edge_index holds a node id outside [0, num_nodes): the edges were dropped by the graph build "
                          "(PyG's index_select / scatter raise here)")
+    if any(int(v) & _lib.NPI_STATUS_BAD_ROW_ID for v in values):
+        raise IndexError("res_n_id holds a row id outside [0, N_src): the row was gathered as zeros (npi_rows_gather; torch's "
+                         "index_select raises here)")
     if any(int(v) & 4 for v in values):
         raise ValueError("InteractionGraph.batch: the n_nodes / n_pairs it was given do not belong to its keys (the device counted "
                          "other totals); that batch holds placeholders only (node 0 / graph 0 rows, padding edges, zero features).  "
@@ -104,6 +107,7 @@ class CSRSide:
     item: int = 0             # entries per item this side was cut with
     _hub: Optional["HubPlan"] = None      # the streaming path for the heaviest rows (``hub_plan()``), None: none / not asked yet
     _hub_asked: bool = False
+    rect_hub: bool = False    # a side of a BipartiteGraph: n_rows and n_cols are independent id spaces and the side may still get a hub plan
 
     def inv_count(self) -> torch.Tensor:
         """1 / max(row length, 1): the scatter_mean divisor (count includes the self loop)."""
@@ -120,7 +124,7 @@ class CSRSide:
         kept; None when the side has no such rows (then the plain launch is all there is).  One device read, once per side --
         so never inside a capture: a side first met there is walked the plain way until somebody asks again outside."""
         if not self._hub_asked:
-            if self.n_rows != self.n_cols or self.n_cols < HUB_MIN_COLS or self.nnz_max <= 0:
+            if (self.n_rows != self.n_cols and not self.rect_hub) or self.n_cols < HUB_MIN_COLS or self.nnz_max <= 0:
                 self._hub_asked = True
             elif not torch.cuda.is_current_stream_capturing():
                 self._hub = build_hub_plan(self)
@@ -206,11 +210,12 @@ class HubPlan:
 
 def build_hub_plan(side: CSRSide, h_max: int = _lib.NPI_HUB_MAX, min_degree: Optional[int] = None,
                    min_entries: Optional[int] = None) -> Optional[HubPlan]:
-    """``npi_hub_plan`` + ``npi_hub_light_side`` for one side (a one-table side, ``n_cols == n_rows``); None when the plan comes
+    """``npi_hub_plan`` + ``npi_hub_light_side`` for one side (a one-table side, ``n_cols == n_rows``, or a side of a
+    ``BipartiteGraph``, whose thresholds then follow ``n_cols``: the rows of the table that would be streamed); None when the plan comes
     out empty.  Reads four words back from the device.  ``min_degree`` / ``min_entries``: the two thresholds (defaults: the
     module's policy, ``HUB_DEGREE_DIV`` / ``HUB_ENTRIES_PER_STREAMED_ROW``)."""
-    if side.n_rows != side.n_cols:
-        raise ValueError("build_hub_plan: one-table sides with n_cols == n_rows only")
+    if side.n_rows != side.n_cols and not side.rect_hub:
+        raise ValueError("build_hub_plan: one-table sides with n_cols == n_rows, or the sides of a BipartiteGraph, only")
     lib = load()
     dev = side.rowptr.device
     N = side.n_rows
@@ -242,7 +247,7 @@ def build_hub_plan(side: CSRSide, h_max: int = _lib.NPI_HUB_MAX, min_degree: Opt
                                  nnz_max, side.item, ptr(rowptr), ptr(col), ptr(eid), ptr(rowidx), ptr(item_row), s),
           "npi_hub_light_side")
     light = CSRSide(rowptr, col, eid, rowidx, item_row, side.status, nnz_max, n_items)
-    light.n_rows, light.n_cols, light.item = N, side.n_cols, side.item
+    light.n_rows, light.n_cols, light.item, light.rect_hub = N, side.n_cols, side.item, side.rect_hub
     light._hub_asked = True                                   # (the light side has no plan of its own)
     return HubPlan(H, n_entries, hub_rows, mask, light)
 
@@ -359,6 +364,86 @@ class CSRGraph:
 
     def nnz(self) -> int:
         """Entries incl. self loops (device read; synchronises -- and reports dropped out-of-range ids)."""
+        n = int(self.by_dst.rowptr[-1].item())
+        check_pending()
+        return n
+
+
+class BipartiteGraph:
+    """Adjacency between TWO id spaces on one GPU: ``edge_index[0]`` indexes a source table of ``size[0]`` rows, ``edge_index[1]``
+    the ``size[1]`` target rows (PyG 1.4.2 ``MessagePassing.propagate(edge_index, size=(N_src, N_dst))``, flow ``source_to_target``)
+    -- what ``SAGEConv`` / ``GATConv`` aggregate over when ``x`` is a pair ``(x_src, x_dst)``.  The edge list as it is: no self loop
+    is added or removed (a ``(k, k)`` column is an ordinary edge from source k to target k); out-of-range and ``(-1, -1)`` columns
+    are dropped and reported exactly as by ``CSRGraph`` (``note_status``).
+
+    ``by_dst`` groups the entries by target (``n_rows = N_dst`` over a table of ``n_cols = N_src`` rows: the forward aggregation),
+    ``by_src`` -- built lazily -- by source (the transposed aggregation of the backward).  ``item`` / ``sort_columns``: as
+    ``CSRGraph``.  ``hub_stream``: the heaviest rows of a side whose TABLE is larger than the Infinity Cache (``HUB_MIN_COLS`` and
+    the degree / entry thresholds apply to ``n_cols``) are aggregated by streaming that table (``CSRSide.hub_plan``)."""
+
+    def __init__(self, edge_index: torch.Tensor, size, item: Optional[int] = None, sort_columns: bool = False, hub_stream: bool = True):
+        if not isinstance(edge_index, torch.Tensor) or edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
+            raise ValueError("edge_index must be a LongTensor of shape [2, E]")
+        if not isinstance(size, (tuple, list)) or len(size) != 2 or size[0] is None or size[1] is None or int(size[0]) < 0 or int(size[1]) < 0:
+            raise ValueError("BipartiteGraph: size must be (N_src, N_dst)")
+        require_gpu(edge_index)
+        self.size = (int(size[0]), int(size[1]))
+        self.num_src, self.num_dst = self.size
+        self.num_edges = int(edge_index.size(1))
+        self.self_loops = False                 # (never appended: the layers' helpers ask)
+        self.symmetric = False
+        self.device = edge_index.device
+        self._ei_version = edge_index._version
+        self._ei_ptr = edge_index.data_ptr()
+        self._src = edge_index[0].contiguous()
+        self._dst = edge_index[1].contiguous()
+        self.sort_columns = bool(sort_columns)
+        self.hub_stream = bool(hub_stream)
+        self.by_dst = build_side(self._dst, self._src, self.num_dst, self.num_src, self_loops=False, drop_equal=False, item=item,
+                                 sort_columns=self.sort_columns)
+        self.by_dst.rect_hub = True
+        self._by_src: Optional[CSRSide] = None
+        self._root = None                       # (res_n_id storage, _version, shape) -> the combined by-source side (root_side)
+
+    @property
+    def by_src(self) -> CSRSide:
+        if self._by_src is None:
+            self._by_src = build_side(self._src, self._dst, self.num_src, self.num_dst, self_loops=False, drop_equal=False,
+                                      item=self.by_dst.item, sort_columns=self.sort_columns)
+            self._by_src.rect_hub = True
+        return self._by_src
+
+    def built_from(self, edge_index: torch.Tensor, size=None) -> bool:
+        """True while ``edge_index`` is still the tensor this structure was built from (storage, shape, ``_version``) -- and
+        ``size``, when given, is its size."""
+        return (self.num_edges == edge_index.size(1) and self._ei_version == edge_index._version
+                and self._ei_ptr == edge_index.data_ptr() and (size is None or (int(size[0]), int(size[1])) == self.size))
+
+    def inv_count(self, side: Optional[CSRSide] = None) -> torch.Tensor:
+        """1 / max(in-edge count, 1) per TARGET (``by_dst``; another side: its rows')"""
+        return (self.by_dst if side is None else side).inv_count()
+
+    def carry(self, side: CSRSide, F: int) -> torch.Tensor:
+        return side.carry(F)
+
+    def root_side(self, res_n_id: torch.Tensor) -> CSRSide:
+        """The by-source side of the backward of ``SAGEConv(concat=True)``: the entries of ``by_src`` over the two-part table
+        ``[dAgg ; dRoot]`` (``N_dst`` rows each) plus ONE entry ``(res_n_id[i], N_dst + i)`` per target i -- the root term
+        ``x_src[res_n_id]`` of the forward, so that ``dX_src`` is one deterministic segmented sum (duplicates in ``res_n_id``
+        accumulate; no float atomics).  Kept for as long as ``res_n_id`` is the same tensor in the same state.  ``eid``: the edge's
+        column for an edge entry, ``num_edges + i`` for the root entry of target i."""
+        key = (res_n_id.data_ptr(), res_n_id._version, tuple(res_n_id.shape))
+        if self._root is None or self._root[0] != key:
+            nd = self.num_dst
+            keys = torch.cat([self._src, res_n_id.reshape(-1)])
+            vals = torch.cat([self._dst, torch.arange(nd, 2 * nd, dtype=torch.int64, device=self.device)])
+            side = build_side(keys, vals, self.num_src, 2 * nd, self_loops=False, drop_equal=False, item=self.by_dst.item,
+                              sort_columns=self.sort_columns)
+            self._root = (key, side, res_n_id)            # (the tensor is held: its storage cannot be reused under the key)
+        return self._root[1]
+
+    def nnz(self) -> int:
+        """Entries (device read; synchronises -- and reports dropped out-of-range ids)."""
         n = int(self.by_dst.rowptr[-1].item())
         check_pending()
         return n

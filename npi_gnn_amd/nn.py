@@ -6,7 +6,8 @@ NPI-GNN's ``Net_1`` (reference ``src/classes.py:45-82``) and its train loop
 
 ``state_dict`` keys are ``weight [in, out]`` (``x @ W`` orientation, not ``nn.Linear``'s) and
 ``bias [out]``, so the reference's checkpoints (``result/<proj>/model_<k>_fold/<epoch>``, loaded at
-``src/test.py:41``) load as they are.  ``forward`` also accepts a prebuilt ``CSRGraph`` in place of
+``src/test.py:41``) load as they are.  ``SAGEConv`` / ``GATConv`` also take PyG's bipartite form -- ``x = (x_src, x_dst)`` and / or ``size=(N_src, N_dst)``, with the
+``[2, E]`` edge list or a prebuilt ``BipartiteGraph`` -- see their ``forward``.  ``forward`` also accepts a prebuilt ``CSRGraph`` in place of
 ``edge_index`` (static full-batch graphs: sort once), and a ``GraphBatch`` in place of ``x`` -- then it
 returns the ``GraphBatch`` with the new features (``conv(gb)``: the CSR is built once per batch and shared
 with the pooling layer behind the conv).  Plain tensors carry no hidden state: ``conv(x, edge_index)``
@@ -22,7 +23,7 @@ from torch import nn
 from torch.nn import Parameter
 
 from . import functional as F_
-from .graph import CSRGraph, GraphBatch, as_graph
+from .graph import BipartiteGraph, CSRGraph, GraphBatch, as_graph
 from .schedule import DEFAULT, Schedule
 
 
@@ -74,11 +75,30 @@ class SAGEConv(nn.Module):
         _uniform(self.weight.size(0), self.weight)
         _uniform(self.weight.size(0), self.bias)
 
-    def forward(self, x, edge_index=None, edge_weight=None, size=None, *, relu: bool = False):
+    def forward(self, x, edge_index=None, edge_weight=None, size=None, res_n_id=None, *, relu: bool = False):
         """``relu=True`` (an extension of the PyG signature): ``F.relu(conv(x, edge_index))`` with the ReLU applied in the
-        projection GEMM's epilogue -- the same values, one launch and one activation-sized tensor fewer."""
+        projection GEMM's epilogue -- the same values, one launch and one activation-sized tensor fewer.
+
+        The bipartite form (PyG 1.4.2): ``x = (x_src, x_dst or None)``, ``edge_index[0]`` indexing ``x_src`` and ``edge_index[1]`` the
+        ``N_dst`` output rows (``x_dst``'s row count, else ``size[1]``, else ``N_src``); ``edge_index`` is the ``[2, E]`` tensor or a
+        ``BipartiteGraph``.  No self loop is added or removed; ``out = mean_{j -> i}(w_e x_src[j]) @ weight + bias`` of shape
+        ``[N_dst, out]``, a target without an in-edge getting ``bias``; ``x_dst`` is not read.  ``concat=True`` needs ``res_n_id``
+        (LongTensor ``[N_dst]``, rows of ``x_src``): ``[x_src[res_n_id] | mean] @ weight[2 in, out] + bias``.  float32 only.
+        A tensor ``x`` with ``size=(N, N)``, ``N = x.size(0)``, runs as ``size=None``; any other ``size`` with a tensor is a
+        ``ValueError`` (pass the pair form)."""
+        if isinstance(x, GraphBatch):
+            if size is not None:
+                raise TypeError("SAGEConv: a GraphBatch is one id space; `size` belongs to the pair form x = (x_src, x_dst)")
+        if isinstance(x, (tuple, list)):
+            return F_.sage_conv_bipartite(x, edge_index, self.weight, self.bias, size=size, res_n_id=res_n_id, normalize=self.normalize,
+                                          concat=self.concat, edge_weight=edge_weight, relu=relu, schedule=self.schedule)
         if size is not None:
-            raise NotImplementedError("SAGEConv: the bipartite `size` form is not used by NPI-GNN")
+            if isinstance(edge_index, GraphBatch):
+                raise TypeError("SAGEConv: a GraphBatch is one id space; `size` belongs to the pair form x = (x_src, x_dst)")
+            if isinstance(edge_index, BipartiteGraph) or not (isinstance(size, (tuple, list)) and len(size) == 2
+                                                              and size[0] == size[1] == x.size(0)):
+                raise ValueError(f"SAGEConv: size={size!r} with a tensor x of {x.size(0)} rows -- two id spaces need the tuple form "
+                                 "x = (x_src, x_dst) (PyG would scatter x.size(0) self loops into size[1] rows)")
         if isinstance(x, GraphBatch):
             gb = _only_batch(x, edge_index, "SAGEConv")
             return gb.with_x(F_.sage_conv(gb.x, gb if self.concat else gb.graph(), self.weight, self.bias, normalize=self.normalize,
@@ -95,7 +115,8 @@ class GATConv(nn.Module):
     """``GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0,
     bias=True)`` (PyG 1.4.2): ``weight [in, heads*out]`` and ``att [1, heads, 2*out]`` glorot,
     ``bias`` zeros (``[heads*out]`` if concat else ``[out]``).  Not used by the reference
-    (BASELINE.json configs[4] only).  ``dropout > 0`` in training mode: the composed variant ``functional._GatDropoutFn``."""
+    (BASELINE.json configs[4] only).  ``dropout > 0`` in training mode: the composed variant ``functional._GatDropoutFn`` (square
+    form only; the bipartite form refuses attention dropout in training mode)."""
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
                  negative_slope: float = 0.2, dropout: float = 0.0, bias: bool = True, schedule: Schedule = DEFAULT, **kwargs):
@@ -122,9 +143,34 @@ class GATConv(nn.Module):
     def forward(self, x, edge_index=None, size=None, *, relu: bool = False, x_scales=None, return_scales: bool = False):
         """``relu=True`` (an extension of the PyG signature, as in ``SAGEConv``): ``F.relu(conv(x, edge_index))`` fused.
         ``x_scales`` / ``return_scales`` (extensions): ``functional.row_scales(x)`` of a feature matrix that does not change between
-        steps, or the ``out_scales`` of the layer in front -- ``functional.gat_conv``."""
-        if size is not None:
-            raise NotImplementedError("GATConv: bipartite `size` is not implemented")
+        steps, or the ``out_scales`` of the layer in front -- ``functional.gat_conv``.
+
+        The bipartite form (PyG 1.4.2): ``x = (x_src, x_dst or None)`` -- ``h_src = x_src @ weight``, ``h_dst = x_dst @ weight``,
+        ``e = leaky_relu(<h_dst[i], att[..., :C]> + <h_src[j], att[..., C:]>)`` (no target term without ``x_dst``), softmax over
+        the in-edges of target i, ``out[i] = sum alpha h_src[j]`` -- and a tensor ``x`` with ``size=(N, N)``, ``N = x.size(0)``, which
+        is the pair form with ``(x, x)``, projected once: whenever ``size`` is given PyG neither removes nor adds self loops.
+        ``edge_index``: the ``[2, E]`` tensor or a ``BipartiteGraph``.  float32, no ``x_scales`` / ``return_scales``, and no
+        attention dropout in training mode (``eval()`` runs)."""
+        if isinstance(x, (tuple, list)) or size is not None:
+            if isinstance(x, GraphBatch) or isinstance(edge_index, GraphBatch):
+                raise TypeError("GATConv: a GraphBatch is one id space; `size` belongs to the pair form x = (x_src, x_dst)")
+            if x_scales is not None or return_scales:
+                raise ValueError("GATConv: x_scales / return_scales belong to the square form (tensor x, size=None)")
+            shared = False
+            if not isinstance(x, (tuple, list)):
+                if not (isinstance(size, (tuple, list)) and len(size) == 2 and size[0] == size[1] == x.size(0)):
+                    raise ValueError(f"GATConv: size={size!r} with a tensor x of {x.size(0)} rows -- two id spaces need the tuple form "
+                                     "x = (x_src, x_dst)")
+                if isinstance(edge_index, CSRGraph):
+                    raise TypeError("GATConv: a CSRGraph holds the self-loop-augmented graph; with `size` the attention runs over the "
+                                    "edge list as it is -- pass the [2, E] edge_index or a BipartiteGraph")
+                x, shared = (x, None), True
+            if self.dropout > 0 and self.training:
+                raise NotImplementedError("GATConv: attention dropout (dropout > 0) in training mode is not implemented for the "
+                                          "bipartite form; eval() runs, and the square form (tensor x, size=None) has it")
+            return F_.gat_conv_bipartite(x, edge_index, self.weight, self.att, self.bias, size=size, heads=self.heads,
+                                         concat=self.concat, negative_slope=self.negative_slope, relu=relu, schedule=self.schedule,
+                                         shared=shared)
         gb = None
         if isinstance(x, GraphBatch):
             gb = _only_batch(x, edge_index, "GATConv")
