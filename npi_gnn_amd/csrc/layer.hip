@@ -6,7 +6,7 @@
 // (C2: 0.54 ms eager for 0.33 ms of GPU time).  PyG's own granularity is one call per layer (SAGEConv.forward, reference
 // src/classes.py:62,66,70; its autograd backward from src/train_with_twoDataset.PY:54): this is that call.
 // Large graphs (the C4 / C5 configurations) keep the per-op entry points: their backward runs on two HIP streams, arranged by the
-// host (functional._SageConvFn), and launch cost is noise there.
+// host (functional._AggProjectFn), and launch cost is noise there.
 #include "npi_common.h"
 
 using namespace npi;

@@ -829,7 +829,7 @@ def _hub_aggregate(sg: ShardedGraph, rows: torch.Tensor, full, partial, w_full, 
 class _ShardedSageFn(torch.autograd.Function):
     """Aggregate, then project.  ``gcn = False``: SAGEConv (mean over in-neighbours and self).  ``gcn = True``: GCNConv in
     the same order, ``(A_hat x) W + b`` with the symmetric normalisation as per-entry weights (see
-    functional._GcnAggFirstFn: identical to PyG's ``A_hat (x W) + b`` up to rounding, dW overlaps the backward aggregation)."""
+    functional._AggProjectFn: identical to PyG's ``A_hat (x W) + b`` up to rounding, dW overlaps the backward aggregation)."""
 
     @staticmethod
     def forward(ctx, x_own, weight, bias, sg: ShardedGraph, gcn: bool = False):
@@ -910,7 +910,7 @@ class _ShardedSageFn(torch.autograd.Function):
             else:
                 dagg = be.linear_bwd_data(grad_out, weight, rs)
         # dW is independent of the dX chain.  On the GPU backend it is launched FIRST, on this stream, so that it is resident
-        # before the aggregations -- BOTH sides, sent to a second stream -- fill the CUs (see functional._SageConvFn); with
+        # before the aggregations -- BOTH sides, sent to a second stream -- fill the CUs (see functional._dw_beside); with
         # side B in front of dW, as in round 1, half of the aggregation ran alone and dW then outlasted the other half
         # (W = 1: 7.99 ms per step).  Other backends run everything in line.
         side = be.side_stream(grad_out, sg.schedule) if (want_w and want_x and hasattr(be, "side_stream")) else None

@@ -240,7 +240,7 @@ def padded_aggregate_buffer(x: torch.Tensor, K: int, rows: int, bf16_ok: bool = 
     its weight-gradient GEMM take the matrix-core kernels (``NPI_GEMM_A_ZERO_PADDED``) instead of the guarded ones -- what
     ``InteractionGraph.batch`` does for extracted batches, here for features the caller hands over 178 wide.  Only when the
     padding costs less than half as much again (178 -> 256 yes, 65 -> 128 no).  (bf16 storage has no padded-operand flag: the
-    layer pads its weight matrix with zero rows instead, ``_SageConvFn``.)"""
+    layer pads its weight matrix with zero rows instead, ``_AggProjectFn``.)"""
     if (x.dtype not in ((torch.float32, torch.bfloat16) if bf16_ok else (torch.float32,)) or x.size(1) != K or K % 128 == 0
             or 2 * _pad128(K) > 3 * K or rows < 128):
         return None
@@ -736,8 +736,32 @@ def mean_bwd_weights(graph: CSRGraph, tside: CSRSide, w_src: Optional[torch.Tens
 def _aggregate_first_ok(sch: Schedule, f16: bool, weight: torch.Tensor, grad_out: torch.Tensor, tside: CSRSide, ws_bwd) -> bool:
     """can the backward of an aggregate-then-project layer run as ``dX = (A^T dOut) W^T`` with the GEMM on fp16 x 2 -- the
     transposed aggregation on dOut itself, writing the row scales of its output (``_backward_aggregate_first``)?"""
+    # (both row counts: dW's contraction runs over the TARGET rows, the data GEMM over the source rows -- one number on a square graph)
     return (sch.aggregate_first_backward and f16 and isinstance(ws_bwd, Planes) and ws_bwd.f16 and grad_out.dtype == torch.float32 and grad_out.size(1) == 256
-            and segsum_scales_ok(tside, grad_out) and f16x2_shape(grad_out.size(0), grad_out.size(1), weight.size(0)))
+            and segsum_scales_ok(tside, grad_out) and f16x2_shape(min(grad_out.size(0), tside.n_rows), grad_out.size(1), weight.size(0)))
+
+
+def _dw_beside(agg, grad_out, has_bias: bool, k_valid, flags: int, aggregate, read_beside):
+    """The two-stream fork of an aggregate-then-project backward: ``dW = agg^T dOut`` (+ db) on the launch stream, ``aggregate()``
+    -- the transposed aggregation -- on the side stream.  Returns ``(aggregate(), dw, db)``.
+
+    dW is independent of the dX chain.  It is launched on THIS stream right behind whatever produced the aggregation's input, one
+    workgroup per CU (``shared=True``), so that it is resident everywhere before the aggregation -- sent to a second HIP stream --
+    fills the remaining wave slots; the two then share every CU.  (The other way round the aggregation wins the race, takes every
+    register of every SIMD, and dW only starts when it is over.)  ``read_beside``: the tensors allocated on the launch stream that
+    the aggregation reads or writes."""
+    dev = grad_out.device
+    main = torch.cuda.current_stream(dev)
+    side = _side_stream(dev)
+    side.wait_stream(main)                                       # the aggregation's input is complete for the side stream
+    dw, db = linear_bwd_weight(agg, grad_out, want_bias=has_bias, shared=True, k_valid=k_valid, flags=flags)
+    with torch.cuda.stream(side):
+        out = aggregate()
+    for buf in read_beside:
+        buf.record_stream(side)                                  # allocated on main, used on side
+    out.record_stream(main)                                      # consumed on main (a no-op where main allocated it)
+    main.wait_stream(side)
+    return out, dw, db
 
 
 def _backward_aggregate_first(graph, tside: CSRSide, w_t: Optional[torch.Tensor], agg, weight, grad_out, ws_bwd: "Planes", want_w: bool,
@@ -756,20 +780,16 @@ def _backward_aggregate_first(graph, tside: CSRSide, w_t: Optional[torch.Tensor]
     t = torch.empty((N, Nout), dtype=torch.float32, device=dev)
     t_scales = torch.empty(N, dtype=torch.float32, device=dev)
     dw = db = None
+
+    def aggregate():
+        return segsum(graph, tside, grad_out, w=w_t, mean=False, out=t, scales_out=t_scales, hub=hub, col_scale=cs)
+
     if overlap and want_w:
-        main = torch.cuda.current_stream(dev)
-        side = _side_stream(dev)
-        side.wait_stream(main)                                   # dOut (and the buffers above) are ready for the side stream
-        dw, db = linear_bwd_weight(agg, grad_out, want_bias=has_bias, shared=True, k_valid=k_valid)
-        with torch.cuda.stream(side):
-            segsum(graph, tside, grad_out, w=w_t, mean=False, out=t, scales_out=t_scales, hub=hub, col_scale=cs)
-        for buf in (grad_out, t, t_scales):
-            buf.record_stream(side)                              # allocated on main, used on side
-        main.wait_stream(side)
+        _, dw, db = _dw_beside(agg, grad_out, has_bias, k_valid, 0, aggregate, (grad_out, t, t_scales))
     else:
         if want_w:
             dw, db = linear_bwd_weight(agg, grad_out, want_bias=has_bias, k_valid=k_valid)
-        segsum(graph, tside, grad_out, w=w_t, mean=False, out=t, scales_out=t_scales, hub=hub, col_scale=cs)
+        aggregate()
     dx = linear_bwd_data(t, weight, ws=ws_bwd, dc_scales=t_scales)
     return dx, dw, db
 
@@ -897,76 +917,84 @@ def _check_edge_weight_grad(edge_weight, x, weight) -> bool:
 # ---------------------------------------------------------------------------------------------
 # SAGEConv
 # ---------------------------------------------------------------------------------------------
-class _SageConvFn(torch.autograd.Function):
+class _AggProjectFn(torch.autograd.Function):
+    """Aggregate, then project: ``out = act(agg @ W + b)`` with ``agg[i] = scale_i sum_{p in row i} w_dst[p] x[col[p]]`` over
+    ``graph.by_dst`` -- a ``CSRGraph`` or, on two id spaces, a ``BipartiteGraph``.  The one schedule of SAGEConv (``mean``; per-entry
+    weights from ``edge_weight`` or none), of GCNConv evaluated as ``(A_hat x) W + b`` (``gcn_conv``: no mean, the weights are the
+    norm) and of the pair form of SAGEConv.  The aggregate is saved, so in the backward dW = agg^T dOut does not wait for the
+    transposed aggregation: on graphs large enough it runs beside it (``_dw_beside``).
+
+    ``w_dst`` / ``w_src``: the per-entry weights of the two orientations, or None.  ``layer_dtypes``: the storage types for which
+    the layer has the whole-layer entry points (``conv_fwd`` / ``conv_bwd``, one id space only) and the zero-padded aggregate
+    (``padded_aggregate_buffer``): f32 and bf16 for SAGEConv, f32 for GCNConv, none for the pair form.  The unweighted mean
+    alone takes the hub plans (``hub_plan_for``) and, on a symmetric edge list, the by-target side for the transposed aggregation."""
+
     @staticmethod
-    def forward(ctx, x, weight, bias, graph: CSRGraph, w_entry=None, relu: bool = False, sch: Schedule = DEFAULT):
-        ctx.graph = graph
-        ctx.w_src = w_entry[1] if w_entry else None
+    def forward(ctx, x, weight, bias, graph, w_dst, w_src, mean: bool, relu: bool, sch: Schedule, layer_dtypes: tuple):
+        d = graph.by_dst
+        ctx.graph, ctx.w_src, ctx.mean, ctx.relu, ctx.sch, ctx.layer_dtypes = graph, w_src, mean, relu, sch, layer_dtypes
         ctx.has_bias = bias is not None
-        ctx.relu = relu
-        ctx.sch = sch
         ctx.k_rows = None
-        f16 = (x.dtype == weight.dtype and x.size(1) == weight.size(0)
-               and _f16x2(sch, graph.by_dst.n_rows, weight.size(0), weight.size(1), x.dtype) and segsum_scales_ok(graph.by_dst, x))
-        ctx.f16 = f16
-        if f16:
+        hubs = mean and w_dst is None
+        fl = _gflags(sch)                                       # (exact-f32 MFMA kernels on request: the per-op calls carry the flag)
+        ctx.f16 = (x.dtype == weight.dtype and x.size(1) == weight.size(0)
+                   and _f16x2(sch, d.n_rows, weight.size(0), weight.size(1), x.dtype) and segsum_scales_ok(d, x))
+        if ctx.f16:
             # large graphs, 256 features: the projection on two fp16 pieces per operand -- the aggregation writes the row scales of
             # agg itself (a wave maximum per finished row); where it cannot, a pass over agg would cost what the GEMM saves
-            agg = torch.empty((graph.by_dst.n_rows, x.size(1)), dtype=x.dtype, device=x.device)
+            agg = torch.empty((d.n_rows, x.size(1)), dtype=x.dtype, device=x.device)
             scales = torch.empty(agg.size(0), dtype=torch.float32, device=x.device)
-            # (no edge weights: the heaviest rows by streaming x once, the rest by the plain launch -- CSRGraph.hub_stream)
-            hub = hub_plan_for(graph, graph.by_dst, x, agg) if not w_entry else None
-            segsum(graph, graph.by_dst, x, w=w_entry[0] if w_entry else None, mean=True, out=agg, scales_out=scales, hub=hub)
+            # (unweighted mean: the heaviest rows by streaming x once, the rest by the plain launch -- CSRGraph.hub_stream)
+            hub = hub_plan_for(graph, d, x, agg) if hubs else None
+            segsum(graph, d, x, w=w_dst, mean=mean, out=agg, scales_out=scales, hub=hub)
             # both fp16 x 2 copies of W in one call: the backward runs aggregate-first (_backward_aggregate_first), so its data GEMM
             # takes the row scales the transposed aggregation writes -- no pass over dOut, which arrives from outside the layer
             wsf, ctx.ws_bwd = prepare_weight(weight, backward=ctx.needs_input_grad[0], f16=True)
             out = linear_fwd(agg, weight, bias, relu=relu, ws=wsf, a_scales=scales)
-            ctx.k_valid = None
-            ctx.save_for_backward(agg, weight, *([out] if relu else []))
-            return out
-        fl = _gflags(sch)                                       # (exact-f32 MFMA kernels on request: the per-op calls carry the flag)
-        if not fl and _layer_calls_ok() and x.dtype == weight.dtype and x.dtype in (torch.float32, torch.bfloat16) and not (
+        elif not fl and _layer_calls_ok() and x.dtype == weight.dtype and x.dtype in layer_dtypes and not (
                 x.dtype == torch.bfloat16 and weight.size(0) % 128 != 0 and 2 * _pad128(weight.size(0)) <= 3 * weight.size(0)):
             # the whole layer call as one entry point (the same launches; one trip through the C ABI instead of three)
-            agg, out, ctx.ws_bwd = conv_fwd(graph.by_dst, x, w_entry[0] if w_entry else None, True, weight, bias, relu,
-                                            ctx.needs_input_grad[0])
-            ctx.k_valid = weight.size(0) if agg.size(1) != weight.size(0) else None
-            ctx.save_for_backward(agg, weight, *([out] if relu else []))
-            return out
-        # a2-a4: gather + scatter_mean (w_entry: PyG's `edge_weight.view(-1, 1) * x_j`; the mean still divides by the count)
-        # x may be the zero-padded base of the caller's features (sage_conv): agg then keeps the padded width -- zero
-        # columns stay zero under a weighted mean -- and both GEMMs run on it (linear_fwd / linear_bwd_weight)
-        agg = None if fl else padded_aggregate_buffer(x, weight.size(0), graph.by_dst.n_rows, bf16_ok=True)
-        if agg is None:
-            agg = segsum(graph, graph.by_dst, x, w=w_entry[0] if w_entry else None, mean=True,
-                         hub=hub_plan_for(graph, graph.by_dst, x) if not w_entry else None)
+            agg, out, ctx.ws_bwd = conv_fwd(d, x, w_dst, mean, weight, bias, relu, ctx.needs_input_grad[0])
         else:
-            segsum(graph, graph.by_dst, x, w=w_entry[0] if w_entry else None, mean=True, out=agg[:, : x.size(1)])
-        if agg.size(1) != weight.size(0) and agg.dtype == torch.bfloat16:
-            # bf16 storage, zero-padded aggregate: W gets zero ROWS to match (one small launch) and all three GEMMs of the layer
-            # run the aligned bf16 matrix-core kernels; dAgg and dW are computed padded and cut back to the true width
-            ctx.k_rows = weight.size(0)
-            weight = torch.nn.functional.pad(weight.detach(), (0, 0, 0, agg.size(1) - weight.size(0)))
-        # both re-laid copies of W (for this GEMM and for dAgg = dOut W^T of the backward) in one launch
-        wsf, ctx.ws_bwd = prepare_weight(weight, backward=ctx.needs_input_grad[0]) if (
-            agg.size(1) == weight.size(0) and agg.dtype == weight.dtype and not fl) else (None, None)
-        out = linear_fwd(agg, weight, bias, relu=relu, ws=wsf, flags=fl)  # a5: agg @ W + b (ReLU in the epilogue on request)
-        ctx.k_valid = weight.size(0) if agg.size(1) != weight.size(0) else None
+            # a2-a4: gather + scatter_mean (w_dst: PyG's `edge_weight.view(-1, 1) * x_j`; the mean still divides by the count)
+            # x may be the zero-padded base of the caller's features (sage_conv): agg then keeps the padded width -- zero
+            # columns stay zero under a weighted mean -- and both GEMMs run on it (linear_fwd / linear_bwd_weight)
+            agg = padded_aggregate_buffer(x, weight.size(0), d.n_rows, bf16_ok=torch.bfloat16 in layer_dtypes) if (
+                not fl and x.dtype in layer_dtypes) else None
+            if agg is None:
+                agg = segsum(graph, d, x, w=w_dst, mean=mean, hub=hub_plan_for(graph, d, x) if hubs else None)
+            else:
+                segsum(graph, d, x, w=w_dst, mean=mean, out=agg[:, : x.size(1)])
+            if agg.size(1) != weight.size(0) and agg.dtype == torch.bfloat16:
+                # bf16 storage, zero-padded aggregate: W gets zero ROWS to match (one small launch) and all three GEMMs of the layer
+                # run the aligned bf16 matrix-core kernels; dAgg and dW are computed padded and cut back to the true width
+                ctx.k_rows = weight.size(0)
+                weight = torch.nn.functional.pad(weight.detach(), (0, 0, 0, agg.size(1) - weight.size(0)))
+            # both re-laid copies of W (for this GEMM and for dAgg = dOut W^T of the backward) in one launch
+            wsf, ctx.ws_bwd = prepare_weight(weight, backward=ctx.needs_input_grad[0]) if (
+                agg.size(1) == weight.size(0) and agg.dtype == weight.dtype and not fl) else (None, None)
+            out = linear_fwd(agg, weight, bias, relu=relu, ws=wsf, flags=fl)  # a5: agg @ W + b (ReLU in the epilogue on request)
+        ctx.k_valid = weight.size(0) if agg.size(1) != weight.size(0) else None       # (an f32 aggregate wider than W: pad columns)
         ctx.save_for_backward(agg, weight, *([out] if relu else []))
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         agg, weight = ctx.saved_tensors[:2]
-        graph: CSRGraph = ctx.graph
+        graph, w_src, mean, sch = ctx.graph, ctx.w_src, ctx.mean, ctx.sch
+        none = (None,) * 7                                      # (graph, w_dst, w_src, mean, relu, sch, layer_dtypes)
         grad_out = _fc(grad_out, "grad_out", agg)
         want_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
         want_x = ctx.needs_input_grad[0]
-        # symmetric edge list, no per-entry weights: A^T has the rows of A (graph.CSRGraph.symmetric) -- skip the second sort
-        tside = (lambda: graph.by_dst) if (graph.symmetric and ctx.w_src is None) else (lambda: graph.by_src)
-        overlap = want_w and want_x and _overlaps(ctx.sch, grad_out.size(0))
-        fl = _gflags(ctx.sch)
-        if not fl and not overlap and ctx.k_rows is None and _layer_calls_ok() and (want_w or want_x) and not ctx.f16:
+        hubs = mean and w_src is None
+        ts = None
+        if want_x:
+            # symmetric edge list, unweighted mean: A^T has the rows of A (graph.CSRGraph.symmetric) -- skip the second sort
+            ts = graph.by_dst if (hubs and graph.symmetric) else graph.by_src
+        overlap = want_w and want_x and _overlaps(sch, grad_out.size(0))
+        fl = _gflags(sch)
+        if (not fl and not overlap and ctx.k_rows is None and _layer_calls_ok() and (want_w or want_x) and not ctx.f16
+                and grad_out.dtype in ctx.layer_dtypes):
             # one stream: the whole backward as one entry point (ReLU mask, dW + db, dAgg GEMM, transposed aggregation)
             out_relu = None
             if ctx.relu:
@@ -974,52 +1002,38 @@ class _SageConvFn(torch.autograd.Function):
                     out_relu = ctx.saved_tensors[2]
                 else:
                     grad_out = relu_backward(grad_out, ctx.saved_tensors[2])
-            dx, dw, db = conv_bwd(tside() if want_x else graph.by_dst, grad_out, out_relu, agg, weight, graph.inv_count(graph.by_dst),
-                                  ctx.w_src, ctx.ws_bwd, want_x, want_w, ctx.has_bias)
-            return dx, dw, db, None, None, None, None
+            return conv_bwd(ts if want_x else graph.by_dst, grad_out, out_relu, agg, weight,
+                            graph.inv_count(graph.by_dst) if mean else None, w_src, ctx.ws_bwd, want_x, want_w, ctx.has_bias) + none
         if ctx.relu:                                            # threshold_backward, as F.relu's autograd does it
             grad_out = relu_backward(grad_out, ctx.saved_tensors[2])
-        dx = dw = db = None
-        if want_x and _aggregate_first_ok(ctx.sch, ctx.f16, weight, grad_out, tside(), ctx.ws_bwd):
-            ts = tside()
-            # no edge weights: the weights are inv_count[col], a factor of the GATHERED row -- the streaming path's column scale;
-            # the plain launch over the light side takes the same factors per entry (cached per graph and side, as before)
-            hub = hub_plan_for(graph, ts, grad_out) if ctx.w_src is None else None
-            w_t = mean_bwd_weights(graph, ts if hub is None else hub.light, ctx.w_src)
-            dx, dw, db = _backward_aggregate_first(graph, ts, w_t, agg, weight, grad_out, ctx.ws_bwd, want_w, ctx.has_bias, overlap,
-                                                   ctx.k_valid, hub=hub)
-            return dx, dw, db, None, None, None, None
+        if want_x and _aggregate_first_ok(sch, ctx.f16, weight, grad_out, ts, ctx.ws_bwd):
+            # unweighted mean: the weights are inv_count[col], a factor of the GATHERED row -- the streaming path's column scale;
+            # the plain launch over the light side takes the same factors per entry (cached per graph and side)
+            hub = hub_plan_for(graph, ts, grad_out) if hubs else None
+            w_t = mean_bwd_weights(graph, ts if hub is None else hub.light, w_src) if mean else w_src
+            return _backward_aggregate_first(graph, ts, w_t, agg, weight, grad_out, ctx.ws_bwd, want_w, ctx.has_bias, overlap,
+                                             ctx.k_valid, hub=hub) + none
         ws_bwd = ctx.ws_bwd if not (isinstance(ctx.ws_bwd, Planes) and ctx.ws_bwd.f16) else None     # (fp16 x 2 planes: not for this order)
+        dx = dw = db = None
         if want_w and not overlap:
             dw, db = linear_bwd_weight(agg, grad_out, want_bias=ctx.has_bias, k_valid=ctx.k_valid, flags=fl)   # aggT dOut, colsum
         if want_x:
-            # dAgg = dOut W^T, pre-divided by the in-count of its row (fused epilogue), then
+            # dAgg = dOut W^T, under a mean pre-divided by the in-count of its row (fused epilogue), then
             # dX[j] = sum over the entries whose SOURCE is j  ==  segsum over the by-source CSR
-            dagg = linear_bwd_data(grad_out, weight, rowscale=graph.inv_count(graph.by_dst), ws=ws_bwd, flags=fl)
+            dagg = linear_bwd_data(grad_out, weight, rowscale=graph.inv_count(graph.by_dst) if mean else None, ws=ws_bwd, flags=fl)
             if ctx.k_rows is not None:
                 dagg = dagg[:, : ctx.k_rows]                                 # (the pad columns of dAgg: dOut times zero rows)
+
+            def aggregate():
+                return segsum(graph, ts, dagg, w=w_src, mean=False, hub=hub_plan_for(graph, ts, dagg) if hubs else None)
+
             if overlap:
-                # dW is independent of the dX chain.  It is launched on THIS stream right behind dAgg's GEMM, one
-                # workgroup per CU, so that it is resident everywhere before the aggregation -- sent to a second HIP
-                # stream -- fills the remaining wave slots; the two then share every CU.  (The other way round the
-                # aggregation wins the race, takes every register of every SIMD, and dW only starts when it is over.)
-                dev = grad_out.device
-                main = torch.cuda.current_stream(dev)
-                side = _side_stream(dev)
-                side.wait_stream(main)                               # dAgg is complete for the side stream
-                dw, db = linear_bwd_weight(agg, grad_out, want_bias=ctx.has_bias, shared=True, k_valid=ctx.k_valid, flags=fl)
-                with torch.cuda.stream(side):
-                    dx = segsum(graph, tside(), dagg, w=ctx.w_src, mean=False,
-                                hub=hub_plan_for(graph, tside(), dagg) if ctx.w_src is None else None)
-                dagg.record_stream(side)                             # allocated on main, read on side
-                dx.record_stream(main)                               # allocated on side, consumed on main
-                main.wait_stream(side)
+                dx, dw, db = _dw_beside(agg, grad_out, ctx.has_bias, ctx.k_valid, fl, aggregate, (dagg,))
             else:
-                dx = segsum(graph, tside(), dagg, w=ctx.w_src, mean=False,
-                            hub=hub_plan_for(graph, tside(), dagg) if ctx.w_src is None else None)
+                dx = aggregate()
         if dw is not None and ctx.k_rows is not None:
             dw = dw[: ctx.k_rows]                                             # the gradient of the zero rows is not W's
-        return dx, dw, db, None, None, None, None
+        return (dx, dw, db) + none
 
 
 class _SageConcatFn(torch.autograd.Function):
@@ -1109,7 +1123,8 @@ def sage_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, bias: Optional[
         x = base
     if relu and normalize:
         raise ValueError("sage_conv: relu=True applies to the projection's output; normalize=True comes after it in PyG")
-    out = _SageConvFn.apply(x, weight, bias, graph, w_entry, relu, schedule)
+    w_dst, w_src = w_entry or (None, None)
+    out = _AggProjectFn.apply(x, weight, bias, graph, w_dst, w_src, True, relu, schedule, (torch.float32, torch.bfloat16))
     if w_grad:
         out = _with_edge_weight_grad(out, edge_weight, x_in, weight, graph, "sage", relu)
     if normalize:
@@ -1205,95 +1220,11 @@ class _GcnConvFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
-class _GcnAggFirstFn(torch.autograd.Function):
-    """The same GCNConv evaluated as ``(A_hat x) W + b`` instead of ``A_hat (x W) + b`` -- identical up to fp32 rounding.
-    Aggregating FIRST (at width F_in <= F_out) gives the layer SAGEConv's schedule: the aggregate is saved, so the
-    weight gradient ``agg^T dOut`` (with ``db`` fused) no longer waits for the backward aggregation and runs on the matrix
-    cores UNDER it (second stream), and the aggregations run at the narrower width (C3's first layer: 178 instead of 256)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, norm: GCNNorm, sch: Schedule = DEFAULT):
-        graph = norm.graph
-        ctx.norm = norm
-        ctx.has_bias = bias is not None
-        ctx.sch = sch
-        if (x.dtype == weight.dtype and x.size(1) == weight.size(0) and segsum_scales_ok(graph.by_dst, x)
-                and _f16x2(sch, graph.by_dst.n_rows, weight.size(0), weight.size(1), x.dtype)):
-            # large graphs, 256 features: the projection on two fp16 pieces per operand, the row scales written by the aggregation
-            # (as in _SageConvFn.forward; the backward aggregates first as well)
-            agg = torch.empty((graph.by_dst.n_rows, x.size(1)), dtype=x.dtype, device=x.device)
-            scales = torch.empty(agg.size(0), dtype=torch.float32, device=x.device)
-            segsum(graph, graph.by_dst, x, w=norm.by_dst, out=agg, scales_out=scales)
-            wsf, ctx.ws_bwd = prepare_weight(weight, backward=ctx.needs_input_grad[0], f16=True)
-            out = linear_fwd(agg, weight, bias, ws=wsf, a_scales=scales)
-            ctx.k_valid = None
-            ctx.f16 = True
-            ctx.save_for_backward(agg, weight)
-            return out
-        ctx.f16 = False
-        fl = _gflags(sch)
-        if not fl and _layer_calls_ok() and x.dtype == weight.dtype == torch.float32:
-            agg, out, ctx.ws_bwd = conv_fwd(graph.by_dst, x, norm.by_dst, False, weight, bias, False, ctx.needs_input_grad[0])
-            ctx.k_valid = weight.size(0) if agg.size(1) != weight.size(0) else None
-            ctx.save_for_backward(agg, weight)
-            return out
-        agg = None if fl else padded_aggregate_buffer(x, weight.size(0), graph.by_dst.n_rows)
-        if agg is None:
-            agg = segsum(graph, graph.by_dst, x, w=norm.by_dst)                # sum_e norm_e x[src]
-        else:
-            segsum(graph, graph.by_dst, x, w=norm.by_dst, out=agg[:, : x.size(1)])
-        wsf, ctx.ws_bwd = prepare_weight(weight, backward=ctx.needs_input_grad[0]) if (
-            agg.size(1) == weight.size(0) and agg.dtype == weight.dtype and not fl) else (None, None)
-        out = linear_fwd(agg, weight, bias, ws=wsf, flags=fl)
-        ctx.k_valid = weight.size(0) if agg.size(1) != weight.size(0) else None
-        ctx.save_for_backward(agg, weight)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        agg, weight = ctx.saved_tensors
-        norm: GCNNorm = ctx.norm
-        graph = norm.graph
-        grad_out = _fc(grad_out, "grad_out", agg)
-        dx = dw = db = None
-        want_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
-        want_x = ctx.needs_input_grad[0]
-        overlap = want_w and want_x and _overlaps(ctx.sch, grad_out.size(0))
-        fl = _gflags(ctx.sch)
-        if not fl and not overlap and _layer_calls_ok() and (want_w or want_x) and grad_out.dtype == torch.float32 and not ctx.f16:
-            dx, dw, db = conv_bwd(graph.by_src if want_x else graph.by_dst, grad_out, None, agg, weight, None, norm.by_src,
-                                  ctx.ws_bwd, want_x, want_w, ctx.has_bias)
-            return dx, dw, db, None, None
-        if want_x and _aggregate_first_ok(ctx.sch, ctx.f16, weight, grad_out, graph.by_src, ctx.ws_bwd):
-            dx, dw, db = _backward_aggregate_first(graph, graph.by_src, norm.by_src, agg, weight, grad_out, ctx.ws_bwd, want_w,
-                                                   ctx.has_bias, overlap, ctx.k_valid)
-            return dx, dw, db, None, None
-        ws_bwd = ctx.ws_bwd if not (isinstance(ctx.ws_bwd, Planes) and ctx.ws_bwd.f16) else None
-        if want_w and not overlap:
-            dw, db = linear_bwd_weight(agg, grad_out, want_bias=ctx.has_bias, k_valid=ctx.k_valid, flags=fl)
-        if want_x:
-            dagg = linear_bwd_data(grad_out, weight, ws=ws_bwd, flags=fl)
-            if overlap:                                                        # see _SageConvFn.backward
-                dev = grad_out.device
-                main = torch.cuda.current_stream(dev)
-                side = _side_stream(dev)
-                side.wait_stream(main)
-                dw, db = linear_bwd_weight(agg, grad_out, want_bias=ctx.has_bias, shared=True, k_valid=ctx.k_valid, flags=fl)
-                with torch.cuda.stream(side):
-                    dx = segsum(graph, graph.by_src, dagg, w=norm.by_src)
-                dagg.record_stream(side)
-                dx.record_stream(main)
-                main.wait_stream(side)
-            else:
-                dx = segsum(graph, graph.by_src, dagg, w=norm.by_src)
-        return dx, dw, db, None, None
-
-
 def gcn_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
              edge_weight: Optional[torch.Tensor] = None, improved: bool = False,
              norm: Optional[GCNNorm] = None, schedule: Schedule = DEFAULT, normalize: bool = True) -> torch.Tensor:
     """PyG 1.4.2 ``GCNConv.forward`` (normalize=True) on MI355X.  Evaluated as ``(A_hat x) W + b`` when the input is not wider
-    than the output (``_GcnAggFirstFn``: the aggregation at the narrower width, dW under the backward aggregation), in PyG's
+    than the output (``_AggProjectFn``: the aggregation at the narrower width, dW under the backward aggregation), in PyG's
     literal order ``A_hat (x W) + b`` otherwise -- the same number up to fp32 rounding.
 
     ``edge_weight`` is differentiable (f32 layers; bf16 storage raises ``NotImplementedError``; a precomputed ``norm=`` is a
@@ -1323,7 +1254,9 @@ def gcn_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, bias: Optional[t
         norm = GCNNorm(as_graph(edge_index, x.size(0)), edge_weight, improved, keep_deg=w_grad) if normalize else \
             PlainWeights(edge_index, x.size(0), edge_weight)            # normalize=False: norm = edge_weight, no self loops
     if weight.size(0) <= weight.size(1):
-        out = _GcnAggFirstFn.apply(x, weight, bias, norm, schedule)
+        # (A_hat x) W + b: the aggregation at the narrower width, the aggregate saved -- dW = agg^T dOut (db fused) no longer waits
+        # for the backward aggregation and runs on the matrix cores UNDER it (C3's first layer aggregates at 178 instead of 256)
+        out = _AggProjectFn.apply(x, weight, bias, norm.graph, norm.by_dst, norm.by_src, False, False, schedule, (torch.float32,))
     else:
         out = _GcnConvFn.apply(x, weight, bias, norm)
     if w_grad:
@@ -2010,80 +1943,6 @@ def _bipartite_entry_weights(graph: BipartiteGraph, edge_weight: torch.Tensor):
     return out, ew
 
 
-class _SageBipartiteFn(torch.autograd.Function):
-    """``out = mean_{e: j -> i}(w_e x_src[j]) @ W + b`` over a ``BipartiteGraph`` -- the structure of ``_SageConvFn`` on two id
-    spaces: aggregation (hub-streamed where the side has a plan) writing the row scales of its output, the projection on two fp16
-    pieces per operand where ``_f16x2`` / ``segsum_scales_ok`` allow, and the backward aggregate-first
-    (``dX_src = (A^T D^-1 dOut) W^T`` over ``by_src``) under the same conditions, per-op otherwise; dW beside the transposed
-    aggregation on the side stream by ``_SageConvFn``'s rule."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, graph: BipartiteGraph, w_entry=None, relu: bool = False, sch: Schedule = DEFAULT):
-        d = graph.by_dst
-        ctx.graph, ctx.relu, ctx.sch = graph, relu, sch
-        ctx.w_src = w_entry[1] if w_entry else None
-        ctx.has_bias = bias is not None
-        w_dst = w_entry[0] if w_entry else None
-        f16 = _f16x2(sch, d.n_rows, weight.size(0), weight.size(1), x.dtype) and segsum_scales_ok(d, x)
-        ctx.f16 = f16
-        if f16:
-            agg = torch.empty((d.n_rows, x.size(1)), dtype=x.dtype, device=x.device)
-            scales = torch.empty(d.n_rows, dtype=torch.float32, device=x.device)
-            hub = hub_plan_for(graph, d, x, agg) if not w_entry else None
-            segsum(graph, d, x, w=w_dst, mean=True, out=agg, scales_out=scales, hub=hub)
-            wsf, ctx.ws_bwd = prepare_weight(weight, backward=ctx.needs_input_grad[0], f16=True)
-            out = linear_fwd(agg, weight, bias, relu=relu, ws=wsf, a_scales=scales)
-        else:
-            fl = _gflags(sch)
-            agg = segsum(graph, d, x, w=w_dst, mean=True, hub=hub_plan_for(graph, d, x) if not w_entry else None)
-            wsf, ctx.ws_bwd = (None, None) if fl else prepare_weight(weight, backward=ctx.needs_input_grad[0])
-            out = linear_fwd(agg, weight, bias, relu=relu, ws=wsf, flags=fl)
-        ctx.save_for_backward(agg, weight, *([out] if relu else []))
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        agg, weight = ctx.saved_tensors[:2]
-        graph: BipartiteGraph = ctx.graph
-        grad_out = _f32c(grad_out, "grad_out")
-        want_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
-        want_x = ctx.needs_input_grad[0]
-        overlap = want_w and want_x and _overlaps(ctx.sch, grad_out.size(0))
-        fl = _gflags(ctx.sch)
-        if ctx.relu:
-            grad_out = relu_backward(grad_out, ctx.saved_tensors[2])
-        dx = dw = db = None
-        if want_x:
-            ts = graph.by_src
-            if (_aggregate_first_ok(ctx.sch, ctx.f16, weight, grad_out, ts, ctx.ws_bwd)
-                    and f16x2_shape(ts.n_rows, grad_out.size(1), weight.size(0))):
-                hub = hub_plan_for(graph, ts, grad_out) if ctx.w_src is None else None
-                w_t = mean_bwd_weights(graph, ts if hub is None else hub.light, ctx.w_src)
-                dx, dw, db = _backward_aggregate_first(graph, ts, w_t, agg, weight, grad_out, ctx.ws_bwd, want_w, ctx.has_bias, overlap,
-                                                       hub=hub)
-                return dx, dw, db, None, None, None, None
-        ws_bwd = ctx.ws_bwd if not (isinstance(ctx.ws_bwd, Planes) and ctx.ws_bwd.f16) else None
-        if want_w and not overlap:
-            dw, db = linear_bwd_weight(agg, grad_out, want_bias=ctx.has_bias, flags=fl)
-        if want_x:
-            dagg = linear_bwd_data(grad_out, weight, rowscale=graph.inv_count(), ws=ws_bwd, flags=fl)       # D^-1 dOut W^T  [N_dst, F]
-            hub = hub_plan_for(graph, ts, dagg) if ctx.w_src is None else None
-            if overlap:
-                dev = grad_out.device
-                main = torch.cuda.current_stream(dev)
-                side = _side_stream(dev)
-                side.wait_stream(main)
-                dw, db = linear_bwd_weight(agg, grad_out, want_bias=ctx.has_bias, shared=True, flags=fl)
-                with torch.cuda.stream(side):
-                    dx = segsum(graph, ts, dagg, w=ctx.w_src, mean=False, hub=hub)
-                dagg.record_stream(side)
-                dx.record_stream(main)
-                main.wait_stream(side)
-            else:
-                dx = segsum(graph, ts, dagg, w=ctx.w_src, mean=False, hub=hub)
-        return dx, dw, db, None, None, None, None
-
-
 def _root_weights(graph: BipartiteGraph, side: CSRSide, ew: Optional[torch.Tensor]) -> torch.Tensor:
     """per-entry weights of ``BipartiteGraph.root_side``: ``inv_count[i]`` (times the edge's weight) for an edge entry whose target
     is i, 1 for a root entry -- ``npi_entry_col_scale`` over the table ``[inv_count ; ones]``; without edge weights kept on the side"""
@@ -2184,7 +2043,8 @@ def sage_conv_bipartite(x, edge_index, weight: torch.Tensor, bias: Optional[torc
         if relu:
             out = torch.relu(out)
         return l2_normalize(out) if normalize else out
-    out = _SageBipartiteFn.apply(x_src, weight, bias, graph, w_entry, relu, schedule)
+    w_dst, w_src = w_entry or (None, None)
+    out = _AggProjectFn.apply(x_src, weight, bias, graph, w_dst, w_src, True, relu, schedule, ())
     if w_grad:
         out = _with_edge_weight_grad(out, edge_weight, x_in, weight, graph, "sage", relu)
     return l2_normalize(out) if normalize else out

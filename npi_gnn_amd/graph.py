@@ -316,7 +316,7 @@ class CSRGraph:
         ``symmetric``: the producer of the edge list vouches that it holds every edge in both directions (the device-side
         subgraph extraction emits both, src/classes.py:701-704, and filter_adj keeps the property; ``GraphBatch.symmetric``).
         Then row j of the by-source CSR holds the same neighbours as row j of the by-target CSR -- in another order -- and an
-        UNWEIGHTED transposed aggregation can walk the by-target side: no second sort (functional._SageConvFn)."""
+        UNWEIGHTED transposed aggregation can walk the by-target side: no second sort (functional._AggProjectFn)."""
         if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
             raise ValueError("edge_index must be a LongTensor of shape [2, E]")
         require_gpu(edge_index)

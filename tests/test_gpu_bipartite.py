@@ -446,3 +446,36 @@ def test_square_calls_keep_their_bits(dev):
         sage((x, x), graph)
     with pytest.raises(TypeError):
         gat((x, x), graph)
+
+
+# ---- square and rectangular layers are one code path -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["64to32", "256-f16x2-overlap", "256-f16x2-overlap-edge-weight"])
+@pytest.mark.parametrize("relu", [False, True])
+def test_square_graph_and_pair_form_give_the_same_bits(dev, case, relu):
+    """``sage_conv`` over the edge list as it is (``CSRGraph(self_loops=False, keep_equal=True)``) and ``sage_conv_bipartite`` over
+    the same list with ``size = (n, n)`` run one function (``functional._AggProjectFn``) over the same two sorted sides.  The square
+    call may take the whole-layer entry points (the 64 -> 32 case does), which the pair form never takes; those issue the same
+    launches as the per-op calls, and every kernel is deterministic -- so out, dX, dW and db are the same bits.  The 256 -> 256
+    cases run the fp16 x 2 forward, the aggregate-first backward and the two-stream fork."""
+    n, E = 2000, 12000
+    Fi, Fo = (64, 32) if case == "64to32" else (256, 256)
+    sch = npi.Schedule() if case == "64to32" else npi.Schedule(f16x2_min_rows=128, overlap_min_rows=0)
+    g = torch.Generator().manual_seed(17)
+    ei = torch.randint(0, n, (2, E), generator=g).to(dev)
+    x = torch.randn(n, Fi, generator=g).to(dev)
+    W = (torch.randn(Fi, Fo, generator=g) / Fi ** 0.5).to(dev)
+    b = torch.randn(Fo, generator=g).to(dev)
+    go = torch.randn(n, Fo, generator=g).to(dev)
+    ew = (torch.rand(E, generator=g) + 0.5).to(dev) if case.endswith("edge-weight") else None
+    res = []
+    for form in ("square", "pair"):
+        xg, Wg, bg = (t.clone().requires_grad_(True) for t in (x, W, b))
+        if form == "square":
+            out = npi.sage_conv(xg, npi.CSRGraph(ei, n, self_loops=False, keep_equal=True), Wg, bg, edge_weight=ew, relu=relu, schedule=sch)
+        else:
+            out = npi.sage_conv_bipartite((xg, None), npi.BipartiteGraph(ei, (n, n)), Wg, bg, edge_weight=ew, relu=relu, schedule=sch)
+        out.backward(go)
+        res.append((out.detach(), xg.grad, Wg.grad, bg.grad))
+    for name, a, c in zip(("out", "dX", "dW", "db"), *res):
+        print(f"   {case} relu={relu} {name}: max |diff| {float((a - c).abs().max()):.2e}")
+        assert torch.equal(a, c), name
