@@ -685,6 +685,58 @@ int npi_subgraph_fill(const int32_t* ptr, const int32_t* nbr, const uint8_t* ok,
 int npi_subgraph_features(const float* feat, int64_t ldf, int64_t Ff, const int32_t* node_id, const int64_t* batch,
                           const int32_t* node_off, int64_t B, int64_t n, float* x, int64_t ldx, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Neighbour sampling: the producer of the (x_src, None) / size= / res_n_id arguments of the bipartite layers.  Replaces, one hop
+ * per sequence of calls, PyG 1.4.2 `torch_geometric.data.NeighborSampler.__produce_bipartite_data_flow__`:
+ * `torch_cluster.neighbor_sampler(n_id, cumdeg, size)`, `torch.unique` over the sampled sources and the `tmp[n_id] = arange`
+ * relabelling, all of which run on the CPU there.
+ *
+ * Input: the by-target CSR of the edge list AS IT IS (npi_csr_build_ex with key = edge_index[1], val = edge_index[0],
+ * add_self_loops = 0, build_flags = 0): rowptr[N+1], col[nnz] = source, eid[nnz] = column of edge_index.  targets[n]: int64 global
+ * ids of the hop's target list; an id outside [0, N) is never dereferenced: it gets no entry and raises NPI_STATUS_BAD_TARGET_ID.
+ *
+ * THE RULE.  Target v has d = rowptr[v+1] - rowptr[v] in-edges; its budget is k = min(d, budget) for an integer budget >= 1, or
+ * k = min(d, ceil((double)frac * d)) for budget == 0 and a fraction 0 < frac <= 1 (the torch_cluster rule).  Position p of the row
+ * (0 <= p < d) gets the 64-bit key (h32(seed, hop, v, p) << 32) | p, with all arithmetic in wrapping uint64:
+ *     mix64(z) : z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *     base     = mix64( mix64(seed + 0x9E3779B97F4A7C15 * (hop + 1))  ^  (v * 0xD6E8FEB86659FD93) )
+ *     h32      = mix64(base + 0x9E3779B97F4A7C15 * (p + 1)) >> 32
+ * (splitmix64: one stream per (seed, hop, v), its p-th output, upper half).  The sample of v is the k positions with the SMALLEST
+ * keys -- a uniform draw without replacement; p makes every key distinct -- emitted in ascending p; targets are emitted in list
+ * order.  The result is a pure function of (seed, hop, v, the row): bitwise reproducible, independent of the other targets of the
+ * call, of the launch geometry and of timing.  The random bits are not PyG's; the distribution and the structure are.
+ *
+ *   npi_sample_counts        : cnt[t] = k of targets[t] (int32); clears status[0] first (status may be NULL).  The caller turns cnt
+ *                              into offsets[n+1] (int64 exclusive sums, offsets[0] = 0).
+ *   npi_sample_select        : for every target its k entries at offsets[t] .. offsets[t+1]: out_src = col[pos] (global source
+ *                              id), out_eid = eid[pos], out_tgt = t.  n_out: the length the caller gave the three arrays; offsets
+ *                              that do not fit it or a row (offsets of another call) write nothing for that target and raise
+ *                              NPI_STATUS_BAD_SAMPLE_SIZES.
+ *   npi_sample_relabel_count : marks the sampled sources (the first min(offsets[n], n_out) entries of out_src) -- and, with
+ *                              add_self_loops != 0, the targets -- in scratch[N] (int32, ALL ZERO on entry, 16-byte aligned), counts
+ *                              them per chunk into workspace[npi_sample_workspace_elems(N)] and writes info[0] = number of distinct
+ *                              ids U, info[1] = number of sampled entries E.  The caller reads info (the one host read of a hop:
+ *                              U and E size the outputs below).
+ *   npi_sample_relabel       : n_id[U] = the marked ids in ascending order (PyG's `unique(sorted=False)` leaves the order open);
+ *                              edge_src[E] = index of out_src in n_id, edge_dst[E] = out_tgt, e_id[E] = out_eid (all int64, the
+ *                              rows of Block.edge_index and Block.e_id); res_n_id[n] = index of targets[t] in n_id (NULL without
+ *                              self loops; -1 for an id out of range).  U other than the count of the marks raises
+ *                              NPI_STATUS_BAD_SAMPLE_SIZES and writes within U.  Leaves scratch ALL ZERO again.
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_STATUS_BAD_TARGET_ID 16
+#define NPI_STATUS_BAD_SAMPLE_SIZES 32
+int npi_sample_counts(const int32_t* rowptr, int64_t N, const int64_t* targets, int64_t n, int64_t budget, float frac,
+                      int32_t* cnt, int32_t* status, void* stream);
+int npi_sample_select(const int32_t* rowptr, const int32_t* col, const int32_t* eid, int64_t N, const int64_t* targets, int64_t n,
+                      const int64_t* offsets, int64_t seed, int64_t hop, int32_t* out_src, int32_t* out_eid, int32_t* out_tgt,
+                      int64_t n_out, int32_t* status, void* stream);
+int64_t npi_sample_workspace_elems(int64_t N);
+int npi_sample_relabel_count(const int32_t* out_src, const int64_t* offsets, int64_t n, int64_t n_out, const int64_t* targets,
+                             int add_self_loops, int32_t* scratch, int64_t N, int32_t* workspace, int32_t* info, void* stream);
+int npi_sample_relabel(int32_t* scratch, int64_t N, const int32_t* workspace, const int32_t* out_src, const int32_t* out_eid,
+                       const int32_t* out_tgt, int64_t E, const int64_t* targets, int64_t n, int64_t U, int64_t* n_id,
+                       int64_t* edge_src, int64_t* edge_dst, int64_t* e_id, int64_t* res_n_id, int32_t* status, void* stream);
+
 /* Evaluation loop (reference src/methods.py:87-105 compares one element per Python
  * iteration, one device sync each).  counts[4] += [TP, FN, TN, FP] for pred = first arg-max of scores[i, 0..C):
  * pred 1 & y 1 -> TP, pred 1 & y 0 -> FP, pred 0 & y 1 -> FN, anything else -> TN (the reference's else

@@ -23,7 +23,9 @@ NPI_GEMM_WORKSPACE_PREPARED = 8   # the workspace already holds npi_linear_prepa
 NPI_GEMM_SPLIT_F16X2 = 16         # two fp16 pieces per operand, three matrix products per tile pair (needs the row scales of A)
 NPI_PREPARE_F16X2 = 4             # npi_linear_prepare(which | this): the fp16 x 2 planes of the weight matrix
 NPI_STATUS_BAD_ROW_ID = 8         # status bit of npi_rows_gather: a row id outside the source table
-NPI_HUB_MAX = 128                 # hubs per plan (npi_hub_plan; mask words of NPI_HUB_MAX / 32 per source row)
+NPI_STATUS_BAD_TARGET_ID = 16     # status bit of npi_sample_counts: a target id outside [0, N)
+NPI_STATUS_BAD_SAMPLE_SIZES = 32  # status bit of npi_sample_select / npi_sample_relabel: offsets / counts of another call
+NPI_HUB_MAX = 128                # hubs per plan (npi_hub_plan; mask words of NPI_HUB_MAX / 32 per source row)
 
 
 def NPI_GEMM_RESERVE_CUS(n: int) -> int:
@@ -137,6 +139,11 @@ PROTOTYPES = {
     "npi_subgraph_sizes": (c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "npi_subgraph_fill": (c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "npi_subgraph_features": (c_int, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _P]),
+    "npi_sample_counts": (c_int, [_P, _I, _P, _I, _I, c_float, _P, _P, _P]),
+    "npi_sample_select": (c_int, [_P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "npi_sample_workspace_elems": (_I, [_I]),
+    "npi_sample_relabel_count": (c_int, [_P, _P, _I, _I, _P, c_int, _P, _I, _P, _P, _P]),
+    "npi_sample_relabel": (c_int, [_P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -52,6 +52,12 @@ def raise_on_status(values) -> None:
     if any(int(v) & _lib.NPI_STATUS_BAD_ROW_ID for v in values):
         raise IndexError("res_n_id holds a row id outside [0, N_src): the row was gathered as zeros (npi_rows_gather; torch's "
                          "index_select raises here)")
+    if any(int(v) & _lib.NPI_STATUS_BAD_TARGET_ID for v in values):
+        raise IndexError("NeighborSampler: a target id outside [0, num_nodes): it was dropped (no entry sampled for it; "
+                         "npi_sample_counts)")
+    if any(int(v) & _lib.NPI_STATUS_BAD_SAMPLE_SIZES for v in values):
+        raise ValueError("npi_sample_select / npi_sample_relabel: the offsets or counts they were given belong to another call; "
+                         "the entries concerned were not written")
     if any(int(v) & 4 for v in values):
         raise ValueError("InteractionGraph.batch: the n_nodes / n_pairs it was given do not belong to its keys (the device counted "
                          "other totals); that batch holds placeholders only (node 0 / graph 0 rows, padding edges, zero features).  "

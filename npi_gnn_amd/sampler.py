@@ -1,0 +1,260 @@
+"""Neighbour sampling on the MI355X: PyG 1.4.2's ``torch_geometric.data.NeighborSampler`` in its bipartite form, producing
+``DataFlow`` blocks for the pair form of ``SAGEConv`` / ``GATConv``::
+
+    sampler = npi.NeighborSampler(edge_index, num_nodes, size=[25, 10], num_hops=2, batch_size=1024, shuffle=True, seed=0)
+    for flow in sampler(subset):                      # subset: None (all nodes), a LongTensor of ids or a bool mask
+        x = feat[flow[0].n_id]
+        for block in flow:                            # outermost hop first
+            x = conv((x, None), block.graph(), size=block.size, res_n_id=block.res_n_id)
+        loss = crit(x, y[flow.n_id])
+
+The reference walks the hops on the CPU (``torch_cluster.neighbor_sampler`` + ``torch.unique``); here every hop is three launches
+over the by-target CSR of the edge list as it is (``npi_sample_counts``, ``npi_sample_select``, ``npi_sample_relabel_count`` /
+``npi_sample_relabel``; ``include/npi_gnn.h`` states the sampling rule).  The sample of a node is a pure function of
+``(seed, epoch, hop, node, its row)``: it does not depend on the other nodes of the batch, so a run can be replayed exactly
+(``sampler.epoch``).  The random bits are not PyG's; the distribution -- uniform without replacement, at most ``size[l]``
+in-neighbours per node of hop ``l`` -- and every field of ``Block`` / ``DataFlow`` are.
+
+ONE host read per hop: the number of distinct source ids and of sampled edges fix the shapes of the block's tensors (as
+``InteractionGraph.batch`` reads its totals).  A fractional ``size`` costs a second one (the edge total is not bounded by
+``size * targets``).  Never inside a stream capture; CPU tensors raise ``NpiError`` -- there is no CPU fallback.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Union
+
+import torch
+
+from . import graph as _graph
+from ._lib import NpiError, check, load, ptr, require_gpu, stream_ptr
+from .graph import BipartiteGraph, build_side
+
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z: int) -> int:
+    z &= _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def epoch_seed(seed: int, epoch: int) -> int:
+    """The ``seed`` argument of ``npi_sample_select`` for one epoch, as a signed 64-bit integer: a splitmix64 step over
+    ``seed`` and ``epoch`` (every hop of every batch of the epoch uses it; the hop index is a separate argument of the key)."""
+    z = _mix64(_mix64(int(seed)) + 0x9E3779B97F4A7C15 * (int(epoch) + 1))
+    return z - (1 << 64) if z >= (1 << 63) else z
+
+
+def epoch_batches(n: int, batch_size: int, shuffle: bool, drop_last: bool, seed: int, epoch: int) -> List[torch.Tensor]:
+    """Positions ``[0, n)`` of one epoch cut into batches (host LongTensors): in order, or -- ``shuffle`` -- by
+    ``torch.randperm`` under a ``torch.Generator`` seeded from ``(seed, epoch)``.  ``drop_last`` drops a short last batch."""
+    n, batch_size = int(n), int(batch_size)
+    if batch_size < 1:
+        raise ValueError("batch_size must be at least 1")
+    if shuffle:
+        g = torch.Generator()
+        g.manual_seed(epoch_seed(seed, epoch) & ((1 << 63) - 1))
+        order = torch.randperm(n, generator=g)
+    else:
+        order = torch.arange(n)
+    out = list(torch.split(order, batch_size)) if n else []
+    if drop_last and out and out[-1].numel() < batch_size:
+        out.pop()
+    return out
+
+
+class Block:
+    """One hop of a ``DataFlow`` (PyG 1.4.2 ``torch_geometric.data.sampler.Block``): ``n_id`` the global ids of the block's sources
+    (ascending), ``res_n_id`` the position of every target in ``n_id`` (None without ``add_self_loops``), ``e_id`` the sampled
+    columns of the original ``edge_index``, ``edge_index`` ``[2, E_s]`` with LOCAL ids (row 0 into ``n_id``, row 1 into the hop's
+    target list), ``size = (N_src, N_dst)``."""
+
+    __slots__ = ("n_id", "res_n_id", "e_id", "edge_index", "size", "_graph")
+
+    def __init__(self, n_id, res_n_id, e_id, edge_index, size):
+        self.n_id, self.res_n_id, self.e_id, self.edge_index, self.size = n_id, res_n_id, e_id, edge_index, tuple(size)
+        self._graph = None
+
+    def graph(self) -> BipartiteGraph:
+        """``BipartiteGraph(edge_index, size)``, built on first use and kept (what the layers aggregate over)."""
+        if self._graph is None:
+            self._graph = BipartiteGraph(self.edge_index, self.size)
+        return self._graph
+
+    def __repr__(self):
+        return f"Block(size={self.size}, edges={int(self.edge_index.size(1))})"
+
+
+class DataFlow:
+    """The blocks of one batch (PyG 1.4.2 ``DataFlow``): ``n_id`` the batch's targets, ``flow[0]`` the OUTERMOST hop (whose
+    ``n_id`` gathers the input features), ``flow[len(flow) - 1]`` the hop next to the batch; iteration runs in that order, and
+    every block's target list is the next block's ``n_id``."""
+
+    def __init__(self, n_id: torch.Tensor, flow: str = "source_to_target"):
+        self.n_id, self.flow = n_id, flow
+        self.__last_n_id__ = n_id
+        self.blocks: List[Block] = []
+
+    @property
+    def batch_size(self) -> int:
+        return int(self.n_id.size(0))
+
+    def append(self, n_id, res_n_id, e_id, edge_index) -> None:
+        self.blocks.append(Block(n_id, res_n_id, e_id, edge_index, (int(n_id.size(0)), int(self.__last_n_id__.size(0)))))
+        self.__last_n_id__ = n_id
+
+    def __len__(self) -> int:
+        return len(self.blocks)
+
+    def __getitem__(self, idx: int) -> Block:
+        return self.blocks[::-1][idx]
+
+    def __iter__(self):
+        return iter(self.blocks[::-1])
+
+    def to(self, device):
+        if torch.device(device) != self.n_id.device:
+            raise NpiError("DataFlow.to: the blocks live on the GPU they were sampled on")
+        return self
+
+    def __repr__(self):
+        sizes = [self.blocks[-1 - i].size[0] for i in range(len(self))] + [self.batch_size]
+        return "DataFlow(" + " <- ".join(str(s) for s in reversed(sizes)) + ")"
+
+
+def _hop_budget(s) -> tuple:
+    """(integer budget, fraction) of one ``size`` entry, as ``npi_sample_counts`` takes them"""
+    if isinstance(s, bool) or not isinstance(s, (int, float)):
+        raise ValueError(f"NeighborSampler: size entries are ints >= 1 or floats in (0, 1], got {s!r}")
+    if isinstance(s, int):
+        if s < 1:
+            raise ValueError(f"NeighborSampler: an integer size must be at least 1, got {s}")
+        return s, 0.0
+    if not (0.0 < s <= 1.0):
+        raise ValueError(f"NeighborSampler: a float size is a fraction in (0, 1], got {s}")
+    return 0, float(s)
+
+
+class NeighborSampler:
+    """PyG 1.4.2 ``NeighborSampler(data, size, num_hops, batch_size, shuffle, drop_last, bipartite=True, add_self_loops,
+    flow='source_to_target')`` over ``edge_index`` ``[2, E]`` (a GPU LongTensor; PyG layout) of a graph of ``num_nodes`` nodes.
+
+    ``size``: a number or one per hop, hop 0 being the one next to the batch: an int keeps at most that many in-neighbours of a
+    node, a float in (0, 1] the fraction ``ceil(size * degree)``.  ``add_self_loops``: every target is also a source of its
+    block and ``Block.res_n_id`` says where (what ``SAGEConv(concat=True)`` and ``GATConv``'s ``x_dst`` need); no edge is added.
+    ``seed``: with ``sampler.epoch`` (the count of the epoch the next call runs; readable and settable) it fixes the shuffle and
+    every sample.  ``sampler(subset)`` is one epoch: a generator of ``DataFlow``\\ s; it counts ``epoch`` up when it is called.
+    Only the bipartite data flow and ``flow='source_to_target'`` exist."""
+
+    def __init__(self, edge_index: torch.Tensor, num_nodes: int, size: Union[int, float, Sequence], num_hops: int = 1,
+                 batch_size: int = 1, shuffle: bool = False, drop_last: bool = False, bipartite: bool = True,
+                 add_self_loops: bool = False, flow: str = "source_to_target", seed: int = 0):
+        if not bipartite:
+            raise ValueError("NeighborSampler: bipartite=False (the subgraph data flow) is not available; only bipartite=True")
+        if flow != "source_to_target":
+            raise ValueError(f"NeighborSampler: flow={flow!r} is not available; only flow='source_to_target'")
+        num_hops = int(num_hops)
+        if num_hops < 1:
+            raise ValueError("NeighborSampler: num_hops must be at least 1")
+        sizes = list(size) if isinstance(size, (list, tuple)) else [size] * num_hops
+        if len(sizes) != num_hops:
+            raise ValueError(f"NeighborSampler: size has {len(sizes)} entries for num_hops={num_hops}")
+        self._budgets = [_hop_budget(s) for s in sizes]
+        if int(batch_size) < 1:
+            raise ValueError("NeighborSampler: batch_size must be at least 1")
+        if not isinstance(edge_index, torch.Tensor) or edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
+            raise ValueError("edge_index must be a LongTensor of shape [2, E]")
+        self.device = require_gpu(edge_index)
+        self.edge_index, self.num_nodes = edge_index, int(num_nodes)
+        if not 0 <= self.num_nodes < 2 ** 31 - 1:
+            raise ValueError("NeighborSampler: num_nodes out of range")
+        self.size, self.num_hops, self.batch_size = sizes, num_hops, int(batch_size)
+        self.shuffle, self.drop_last, self.add_self_loops = bool(shuffle), bool(drop_last), bool(add_self_loops)
+        self.flow, self.seed, self.epoch = flow, int(seed), 0
+        N = self.num_nodes
+        # by-target CSR of the edge list as it is: no loop added or removed, eid = the edge's column
+        self.side = build_side(edge_index[1].contiguous(), edge_index[0].contiguous(), N, N, self_loops=False, drop_equal=False)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        self._scratch = torch.zeros(max(N, 1), **i32)         # zero between calls: npi_sample_relabel leaves it so
+        self._ws = torch.empty(int(load().npi_sample_workspace_elems(N)), **i32)
+
+    # ---- one hop ----------------------------------------------------------------------------------------------------------------------
+    def sample_hop(self, targets: torch.Tensor, hop: int, seed: int):
+        """One hop back from ``targets`` (int64 global ids on the device) with the budget of ``size[hop]`` and the key seed
+        ``seed``: ``(n_id, res_n_id, e_id, edge_index)`` of the block.  One host read (two for a fractional size)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise NpiError("NeighborSampler: sampling reads sizes back from the device and cannot run inside a stream capture")
+        lib, dev, side, N = load(), self.device, self.side, self.num_nodes
+        require_gpu(targets)
+        targets = targets.to(torch.int64).contiguous()
+        n = int(targets.numel())
+        budget, frac = self._budgets[hop]
+        st = stream_ptr(dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        i64 = dict(dtype=torch.int64, device=dev)
+        cnt = torch.empty(max(n, 1), **i32)
+        status = torch.empty(1, **i32)
+        check(lib.npi_sample_counts(ptr(side.rowptr), N, ptr(targets), n, budget, frac, ptr(cnt), ptr(status), st), "npi_sample_counts")
+        offsets = torch.zeros(n + 1, **i64)
+        if n:
+            torch.cumsum(cnt[:n], 0, out=offsets[1:])
+        cap = n * budget if budget else int(offsets[-1].item())     # a fraction: the total is not bounded by the budget
+        if cap > 2 ** 31 - 1:
+            raise OverflowError("NeighborSampler: more than 2^31 - 1 sampled edges in one hop; use smaller batches")
+        out = torch.empty((3, max(cap, 1)), **i32)                  # source id (global), edge id, local target index
+        check(lib.npi_sample_select(ptr(side.rowptr), ptr(side.col), ptr(side.eid), N, ptr(targets), n, ptr(offsets), int(seed), int(hop),
+                                    ptr(out[0]), ptr(out[1]), ptr(out[2]), cap, ptr(status), st), "npi_sample_select")
+        info = torch.empty(2, **i32)
+        loops = 1 if self.add_self_loops else 0
+        check(lib.npi_sample_relabel_count(ptr(out[0]), ptr(offsets), n, cap, ptr(targets), loops, ptr(self._scratch), N, ptr(self._ws),
+                                           ptr(info), st), "npi_sample_relabel_count")
+        # the host read of the hop; the status words nobody has looked at yet ride along (graph.pending_status)
+        pending = _graph.pending_status(dev)
+        vals = torch.cat([info, status] + pending).tolist()
+        U, E = vals[0], vals[1]
+        n_id = torch.empty(U, **i64)
+        ei = torch.empty((2, E), **i64)
+        e_id = torch.empty(E, **i64)
+        res = torch.empty(n, **i64) if self.add_self_loops else None
+        check(lib.npi_sample_relabel(ptr(self._scratch), N, ptr(self._ws), ptr(out[0]), ptr(out[1]), ptr(out[2]), E, ptr(targets), n, U,
+                                     ptr(n_id), ptr(ei[0]) if E else 0, ptr(ei[1]) if E else 0, ptr(e_id), ptr(res), ptr(status), st),
+              "npi_sample_relabel")
+        _graph.raise_on_status(vals[2:])                            # (after the scratch has been cleaned again)
+        _graph.note_status(status)                                  # npi_sample_relabel's own bit: read with the next hop's sizes
+        return n_id, res, e_id, ei
+
+    def sample(self, targets: torch.Tensor, seed: Optional[int] = None) -> DataFlow:
+        """The ``DataFlow`` of one batch of target ids; ``seed``: the key seed (default: that of the current epoch)."""
+        seed = epoch_seed(self.seed, self.epoch) if seed is None else int(seed)
+        targets = targets.to(device=self.device, dtype=torch.int64).contiguous()
+        flow = DataFlow(targets, self.flow)
+        n_id = targets
+        for hop in range(self.num_hops):
+            n_id, res, e_id, ei = self.sample_hop(n_id, hop, seed)
+            flow.append(n_id, res, e_id, ei)
+        return flow
+
+    # ---- one epoch --------------------------------------------------------------------------------------------------------------------
+    def subset_ids(self, subset) -> torch.Tensor:
+        dev = self.device
+        if subset is None:
+            return torch.arange(self.num_nodes, dtype=torch.int64, device=dev)
+        subset = subset.to(dev)
+        if subset.dtype in (torch.bool, torch.uint8):
+            return subset.nonzero().view(-1)
+        return subset.to(torch.int64).view(-1)
+
+    def __call__(self, subset=None):
+        """One epoch over ``subset``: a generator of ``DataFlow``\\ s.  The epoch's number is taken -- and ``epoch`` counted up --
+        now, not at the first ``next()``."""
+        epoch = self.epoch
+        self.epoch = epoch + 1
+        ids = self.subset_ids(subset)
+        seed = epoch_seed(self.seed, epoch)
+        batches = epoch_batches(int(ids.numel()), self.batch_size, self.shuffle, self.drop_last, self.seed, epoch)
+
+        def run():
+            for pos in batches:
+                yield self.sample(ids[pos.to(self.device)], seed)
+        return run()

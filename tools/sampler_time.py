@@ -1,0 +1,170 @@
+#!/usr/bin/env python3
+"""Timings of ``npi.NeighborSampler`` on one MI355X (EXPERIMENTS.md): one epoch-shaped run on the benchmark's synthetic C4 graph
+(``npi_gnn_amd/synth.py``: 1M nodes, 20M directed edges, Zipf hubs), 1024 targets per batch, ``size=[25, 10]``, two hops,
+``add_self_loops=True``, 100 batches after a warm-up.
+
+Per batch it reports the device time of each entry point (HIP events around the call, summed over the two hops: counts, select,
+relabel = relabel_count + relabel) and the wall time of the whole ``DataFlow`` (host clock around ``sampler.sample`` ending in a
+synchronise: it includes the host reads that size the tensors).
+
+Beside it: the numpy restatement of the sampling rule of ``include/npi_gnn.h`` on the first ``--numpy-batches`` of the same batches
+(host, one Python iteration per target; its blocks are compared with the device's while it is at it).  There is NO torch-ops
+composition on the GPU to put beside it: a draw without replacement per row needs a ``randperm`` per row, which torch does not
+have -- the numpy figure is the comparison.
+
+usage: python tools/sampler_time.py [--batches 100] [--numpy-batches 3] [--json OUT]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import npi_gnn_amd as npi                                     # noqa: E402
+from npi_gnn_amd import sampler as S                          # noqa: E402
+from npi_gnn_amd.synth import bipartite_edge_index            # noqa: E402
+
+U64 = np.uint64
+GAMMA = U64(0x9E3779B97F4A7C15)
+
+
+def mix64(z):
+    z = np.asarray(z, dtype=U64)
+    with np.errstate(over="ignore"):
+        z = (z ^ (z >> U64(30))) * U64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> U64(27))) * U64(0x94D049BB133111EB)
+        return z ^ (z >> U64(31))
+
+
+def numpy_hop(rowptr, col, eid, targets, k, hop, seed, loops):
+    """one block by the rule, in numpy: (n_id, e_id, edge_index)"""
+    one = lambda i: np.array([int(i) & ((1 << 64) - 1)], dtype=U64)            # noqa: E731
+    with np.errstate(over="ignore"):
+        hop_base = mix64(one(seed) + GAMMA * one(hop + 1))
+    src, e_id, tgt = [], [], []
+    for t, v in enumerate(targets):
+        s, d = int(rowptr[v]), int(rowptr[v + 1] - rowptr[v])
+        if d <= k:
+            pos = np.arange(d)
+        else:
+            p = np.arange(d, dtype=U64)
+            with np.errstate(over="ignore"):
+                base = mix64(hop_base ^ (one(v) * U64(0xD6E8FEB86659FD93)))
+                keys = ((mix64(base + GAMMA * (p + U64(1))) >> U64(32)) << U64(32)) | p
+            pos = np.sort(np.argpartition(keys, k)[:k])
+        src.append(col[s + pos])
+        e_id.append(eid[s + pos])
+        tgt.append(np.full(len(pos), t, dtype=np.int64))
+    src, e_id, tgt = np.concatenate(src), np.concatenate(e_id), np.concatenate(tgt)
+    n_id = np.unique(np.concatenate([src, targets]) if loops else src)
+    return n_id, e_id, np.stack([np.searchsorted(n_id, src), tgt])
+
+
+class TimedLib:
+    """the C-ABI library with HIP events around the sampling entry points"""
+
+    def __init__(self, lib):
+        self._lib, self.events = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("npi_sample_") or name.endswith("_elems"):
+            return fn
+
+        def timed(*args):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            rc = fn(*args)
+            e1.record()
+            self.events.append((name, e0, e1))
+            return rc
+        return timed
+
+    def take(self):
+        torch.cuda.synchronize()
+        out = {}
+        for name, e0, e1 in self.events:
+            out[name] = out.get(name, 0.0) + e0.elapsed_time(e1)
+        self.events = []
+        return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--numpy-batches", type=int, default=3)
+    ap.add_argument("--nodes", type=int, default=1_000_000)
+    ap.add_argument("--edges", type=int, default=20_000_000)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda")
+    sizes, bs = [25, 10], 1024
+    ei_host = bipartite_edge_index(args.nodes, args.edges, seed=20260310)
+    ei = ei_host.to(dev)
+    t0 = time.perf_counter()
+    sampler = npi.NeighborSampler(ei, args.nodes, size=sizes, num_hops=2, batch_size=bs, shuffle=True, add_self_loops=True, seed=0)
+    torch.cuda.synchronize()
+    print(f"sampler construction (one CSR build of {args.edges} edges): {1e3 * (time.perf_counter() - t0):.1f} ms", flush=True)
+    deg = (sampler.side.rowptr[1:] - sampler.side.rowptr[:-1])
+    print(f"in-degree: max {int(deg.max())}, rows above 2048 entries {int((deg > 2048).sum())}", flush=True)
+    seed = S.epoch_seed(0, 0)
+    order = S.epoch_batches(args.nodes, bs, True, False, 0, 0)[: args.warmup + args.batches]
+    timed = TimedLib(S.load())
+    S.load = lambda: timed                                   # the sampler module's handle on the library, for this process only
+    rows, flows = [], []
+    for i, pos in enumerate(order):
+        targets = pos.to(dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        flow = sampler.sample(targets, seed)
+        torch.cuda.synchronize()
+        wall = 1e3 * (time.perf_counter() - t0)
+        ev = timed.take()
+        if i >= args.warmup:
+            rows.append({"counts_ms": ev["npi_sample_counts"], "select_ms": ev["npi_sample_select"],
+                         "relabel_ms": ev["npi_sample_relabel_count"] + ev["npi_sample_relabel"], "data_flow_wall_ms": wall,
+                         "sources_outer": flow[0].size[0], "edges": sum(int(b.e_id.numel()) for b in flow)})
+            if len(flows) < args.numpy_batches:
+                flows.append((pos.numpy(), flow))
+    res = {k: {"median": statistics.median(r[k] for r in rows), "min": min(r[k] for r in rows), "max": max(r[k] for r in rows)}
+           for k in rows[0]}
+    res["batches"] = len(rows)
+    print(json.dumps(res, indent=1), flush=True)
+    # the numpy restatement on the same batches
+    dst = ei_host[1].numpy()
+    t0 = time.perf_counter()
+    perm = np.argsort(dst, kind="stable")
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(dst, minlength=args.nodes))])
+    col = ei_host[0].numpy()[perm]
+    print(f"numpy: by-target CSR (stable argsort) {time.perf_counter() - t0:.1f} s", flush=True)
+    np_ms = []
+    for targets, flow in flows:
+        t0 = time.perf_counter()
+        n_id = targets
+        blocks = []
+        for hop, k in enumerate(sizes):
+            blk = numpy_hop(rowptr, col, perm, n_id, k, hop, seed, True)
+            blocks.append(blk)
+            n_id = blk[0]
+        np_ms.append(1e3 * (time.perf_counter() - t0))
+        for blk, dev_blk in zip(blocks, [flow[1], flow[0]]):
+            same = (np.array_equal(blk[0], dev_blk.n_id.cpu().numpy()) and np.array_equal(blk[1], dev_blk.e_id.cpu().numpy())
+                    and np.array_equal(blk[2], dev_blk.edge_index.cpu().numpy()))
+            if not same:
+                raise SystemExit("the device's block differs from the numpy restatement")
+    if np_ms:
+        res["numpy_data_flow_ms"] = {"median": statistics.median(np_ms), "batches": len(np_ms)}
+        print(f"numpy restatement, whole DataFlow: median {statistics.median(np_ms):.0f} ms over {len(np_ms)} batches "
+              "(blocks equal to the device's)", flush=True)
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        json.dump(res, open(args.json, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
