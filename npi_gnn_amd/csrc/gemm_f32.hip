@@ -108,9 +108,6 @@ struct Stage {
 };
 
 // storage element types of the EDGE kernel: float, or bf16 carried as uint16_t (f32 MFMA accumulation)
-typedef uint16_t bf16_t;
-__device__ __forceinline__ float ld1(const float* p) { return *p; }
-__device__ __forceinline__ float ld1(const bf16_t* p) { return __uint_as_float((uint32_t)*p << 16); }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float4 ld4(const bf16_t* p) {
     const uint2 v = *reinterpret_cast<const uint2*>(p);
@@ -118,12 +115,7 @@ __device__ __forceinline__ float4 ld4(const bf16_t* p) {
                        __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
 }
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
-__device__ __forceinline__ void st1(bf16_t* p, float v) { *p = __builtin_bit_cast(bf16_t, (__bf16)v); }
-__device__ __forceinline__ float elem_f32(float v) { return v; }
-__device__ __forceinline__ float elem_f32(bf16_t v) { return __uint_as_float((uint32_t)v << 16); }
-template <typename T> __device__ __forceinline__ T elem_from_f32(float v);
-template <> __device__ __forceinline__ float elem_from_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ bf16_t elem_from_f32<bf16_t>(float v) { return __builtin_bit_cast(bf16_t, (__bf16)v); }
+__device__ __forceinline__ void st1(bf16_t* p, float v) { *p = from_f32<bf16_t>(v); }
 
 // guarded load of staging slot p (EDGE kernel): rows beyond rmax / k beyond kmax read as zero
 template <int MODE_KCONTIG, int ROWS, bool VEC4, typename T>
@@ -138,10 +130,10 @@ __device__ __forceinline__ float4 guarded_load(const T* __restrict__ base, int64
             const T* src = base + (int64_t)r * ld + k;
             if (VEC4) { if (k < kmax) v = ld4(src); }
             else {
-                if (k + 0 < kmax) v.x = ld1(src + 0);
-                if (k + 1 < kmax) v.y = ld1(src + 1);
-                if (k + 2 < kmax) v.z = ld1(src + 2);
-                if (k + 3 < kmax) v.w = ld1(src + 3);
+                if (k + 0 < kmax) v.x = to_f32(src[0]);
+                if (k + 1 < kmax) v.y = to_f32(src[1]);
+                if (k + 2 < kmax) v.z = to_f32(src[2]);
+                if (k + 3 < kmax) v.w = to_f32(src[3]);
             }
         }
     } else {
@@ -149,10 +141,10 @@ __device__ __forceinline__ float4 guarded_load(const T* __restrict__ base, int64
             const T* src = base + (int64_t)k * ld + r;
             if (VEC4) { if (r < rmax) v = ld4(src); }
             else {
-                if (r + 0 < rmax) v.x = ld1(src + 0);
-                if (r + 1 < rmax) v.y = ld1(src + 1);
-                if (r + 2 < rmax) v.z = ld1(src + 2);
-                if (r + 3 < rmax) v.w = ld1(src + 3);
+                if (r + 0 < rmax) v.x = to_f32(src[0]);
+                if (r + 1 < rmax) v.y = to_f32(src[1]);
+                if (r + 2 < rmax) v.z = to_f32(src[2]);
+                if (r + 3 < rmax) v.w = to_f32(src[3]);
             }
         }
     }
@@ -239,7 +231,7 @@ __device__ __forceinline__ void store_tile(T* __restrict__ C, int64_t ldc, int M
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int c = nw + j * 32 + li;
-        bv[j] = (ep.bias != nullptr) ? ld1(reinterpret_cast<const T*>(ep.bias) + (GUARD ? min(c, N - 1) : c)) : 0.f;
+        bv[j] = (ep.bias != nullptr) ? to_f32(reinterpret_cast<const T*>(ep.bias)[GUARD ? min(c, N - 1) : c]) : 0.f;
     }
     const bool relu_on = ep.relu != 0;
     T* __restrict__ cbase = C + (int64_t)(mw + 4 * lh) * ldc + (nw + li);
@@ -516,9 +508,9 @@ dw_finish_kernel(const float* __restrict__ slabs, int64_t slab_stride, int nslab
                 cv[u] = dC_rem[(int64_t)m * lddc + c];
             }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) s = (m0 + u < n_rem) ? fmaf(elem_f32(av[u]), elem_f32(cv[u]), s) : s;
+            for (int u = 0; u < 8; ++u) s = (m0 + u < n_rem) ? fmaf(to_f32(av[u]), to_f32(cv[u]), s) : s;
         }
-        dW[(int64_t)r * lddw + c] = elem_from_f32<TS>(s);
+        dW[(int64_t)r * lddw + c] = from_f32<TS>(s);
         return;
     }
     if (db == nullptr) return;
@@ -549,9 +541,9 @@ dw_finish_kernel(const float* __restrict__ slabs, int64_t slab_stride, int nslab
 #pragma unroll
             for (int u = 0; u < 8; ++u) cv[u] = dC_rem[(int64_t)min(m0 + u, n_rem - 1) * lddc + c];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) r += m0 + u < n_rem ? elem_f32(cv[u]) : 0.f;
+            for (int u = 0; u < 8; ++u) r += m0 + u < n_rem ? to_f32(cv[u]) : 0.f;
         }
-        db[c] = elem_from_f32<TS>(r);
+        db[c] = from_f32<TS>(r);
     }
 }
 

@@ -41,6 +41,18 @@ __device__ __forceinline__ T* uniform_ptr(T* p) {
     return reinterpret_cast<T*>(((uint64_t)hi << 32) | lo);
 }
 
+// storage element types: float, or bf16 carried as uint16_t (f32 accumulation either way)
+typedef uint16_t bf16_t;
+__device__ __forceinline__ float to_f32(float v) { return v; }
+__device__ __forceinline__ float to_f32(bf16_t v) { return __uint_as_float((uint32_t)v << 16); }
+template <typename T> __device__ __forceinline__ T from_f32(float v);
+template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
+template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) {
+    return __builtin_bit_cast(bf16_t, (__bf16)v);          // v_cvt_pk_bf16_f32: RNE, NaN stays NaN
+}
+
+__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
+
 // fp16 x 2 projection (NPI_GEMM_SPLIT_F16X2, gemm_f32.hip): power-of-two scale for a row / column whose largest magnitude is m,
 // m * scale in [2^14, 2^15), clamped so that scale and 1 / scale are normal f32 (2^-126 .. 2^126).  A row with no magnitude -- all
 // zero, or an Inf / NaN maximum (which then propagates as in the bf16 split) -- takes the clamp maximum 2^126, the scale of the

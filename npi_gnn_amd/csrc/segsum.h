@@ -16,6 +16,30 @@ enum { W_NONE = 0, W_ARRAY = 1, W_GAT_DST = 2, W_GAT_SRC = 3, W_GAT_SRC_PRE = 4,
 constexpr bool is_fused_mode(int m) { return m == W_GAT_SRC_FUSED || (m >= W_GAT_SRC_FUSED_H2 && m <= W_GAT_SRC_FUSED_H8); }
 constexpr int fused_heads(int m) { return m == W_GAT_SRC_FUSED_H2 ? 2 : m == W_GAT_SRC_FUSED_H4 ? 4 : m == W_GAT_SRC_FUSED_H8 ? 8 : 1; }
 
+// What segsum.hip's row epilogue, lane geometry, launch bounds and dispatch ask about a weight mode, each property named once
+struct ModeTraits {
+    bool plain_add;          // no weight at all: acc += x instead of fma
+    bool lane_weight;        // the lane that owns an entry of a 64-entry block fetches (or computes) its weight, then it is broadcast
+    bool per_head;           // a GAT mode: a lane knows the head of its columns, a row has constants to fetch when it opens
+    bool row_norm;           // a finished row is scaled by 1 / (s[row] + 1e-16)
+    bool softmax;            // online softmax: the item computes the scores, every partial row carries (max, sum exp)
+    int fused_heads;         // fused backward (dz next to the aggregation): its compile-time head count; 0 = not a fused backward
+    bool rank1;              // rank-1 terms of the attention-score gradient in the row epilogue
+    bool row_scales;         // may also write the finished rows' power-of-two scales (the EXACT == 2 kernels exist for these only)
+};
+constexpr ModeTraits mode_traits(int m) {
+    //                                        add    lane   head   norm   smax  fused rank1  scales
+    return m == W_NONE            ? ModeTraits{true,  false, false, false, false, 0, false, true}
+         : m == W_ARRAY           ? ModeTraits{false, true,  false, false, false, 0, false, true}
+         : m == W_GAT_DST         ? ModeTraits{false, false, true,  true,  false, 0, false, false}
+         : m == W_GAT_DST_PRE     ? ModeTraits{false, true,  true,  true,  false, 0, false, false}
+         : m == W_GAT_DST_FUSED   ? ModeTraits{false, false, true,  false, true,  0, false, true}
+         : m == W_GAT_SRC         ? ModeTraits{false, false, true,  false, false, 0, true,  false}
+         : m == W_GAT_SRC_PRE     ? ModeTraits{false, true,  true,  false, false, 0, true,  false}
+         : is_fused_mode(m)       ? ModeTraits{false, true,  true,  false, false, fused_heads(m), false, true}
+                                  : ModeTraits{false, false, false, false, false, 0, false, false};
+}
+
 struct SegParams {
     const int32_t* rowptr;
     const int32_t* col;

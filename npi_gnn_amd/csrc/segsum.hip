@@ -43,16 +43,6 @@ constexpr bool TWO_PART = true;
 constexpr int SEG_THREADS = 256;
 constexpr int SEG_WAVES = SEG_THREADS / WAVE;
 
-// storage element types: float, or bf16 carried as uint16_t (f32 accumulation either way)
-typedef uint16_t bf16_t;
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ float to_f32(bf16_t v) { return __uint_as_float((uint32_t)v << 16); }
-template <typename T> __device__ __forceinline__ T from_f32(float v);
-template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) {
-    return __builtin_bit_cast(bf16_t, (__bf16)v);          // v_cvt_pk_bf16_f32: RNE, NaN stays NaN
-}
-
 template <typename T, int VEC> struct vec_of;
 template <> struct vec_of<float, 1> { using type = float; };
 template <> struct vec_of<float, 2> { using type = float2; };
@@ -85,22 +75,7 @@ __device__ __forceinline__ void unpack_row(const typename vec_of<T, VEC>::type& 
     }
 }
 template <int VEC, typename T>
-__device__ __forceinline__ void load_row(const T* __restrict__ p, float (&d)[VEC]) {
-    using V = typename vec_of<T, VEC>::type;
-    V v = *reinterpret_cast<const V*>(p);
-    if constexpr (sizeof(T) == 4) {
-        if constexpr (VEC == 1) { d[0] = v; }
-        if constexpr (VEC == 2) { d[0] = v.x; d[1] = v.y; }
-        if constexpr (VEC == 4) { d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w; }
-    } else {
-        if constexpr (VEC == 1) { d[0] = to_f32((bf16_t)v); }
-        if constexpr (VEC == 2) { d[0] = __uint_as_float(v << 16); d[1] = __uint_as_float(v & 0xffff0000u); }
-        if constexpr (VEC == 4) {
-            d[0] = __uint_as_float(v.x << 16); d[1] = __uint_as_float(v.x & 0xffff0000u);
-            d[2] = __uint_as_float(v.y << 16); d[3] = __uint_as_float(v.y & 0xffff0000u);
-        }
-    }
-}
+__device__ __forceinline__ void load_row(const T* __restrict__ p, float (&d)[VEC]) { unpack_row<VEC, T>(load_raw<VEC, T>(p), d); }
 template <int VEC, typename T>
 __device__ __forceinline__ void store_row(T* __restrict__ p, const float (&d)[VEC]) {
     using V = typename vec_of<T, VEC>::type;
@@ -120,8 +95,6 @@ __device__ __forceinline__ void store_row(T* __restrict__ p, const float (&d)[VE
     *reinterpret_cast<V*>(p) = v;
 }
 
-__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
-
 // rows in flight per wavefront: ~32 VGPRs of outstanding loads
 template <int VEC, int NCH> struct inflight { static constexpr int value = (32 / (VEC * NCH)) > 8 ? 8 : ((32 / (VEC * NCH)) < 2 ? 2 : (32 / (VEC * NCH))); };
 
@@ -130,14 +103,14 @@ template <int VEC, int NCH, int WMODE, int EXACT>
 struct Lanes {
     bool act[NCH];
     int foff[NCH];
-    int hd[NCH];       // head of this lane's columns in chunk c (GAT modes)
+    int hd[NCH];       // head of this lane's columns in chunk c (per_head modes)
     __device__ __forceinline__ void init(const SegParams& P) {
         const int lane = lane_id();
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             foff[c] = (c * WAVE + lane) * VEC;
             act[c] = EXACT ? true : (foff[c] < P.F);
-            hd[c] = (WMODE >= W_GAT_DST && act[c]) ? foff[c] / P.C : 0;
+            hd[c] = (mode_traits(WMODE).per_head && act[c]) ? foff[c] / P.C : 0;
         }
     }
 };
@@ -160,7 +133,8 @@ __device__ __forceinline__ float wave_max(float v) {
     return bcast_f(v, WAVE - 1);
 }
 // wave-wide sum in the same fixed DPP order (deterministic): the partial dots of the fused GATConv forward's scores
-__device__ __forceinline__ float wave_sum(float v) {
+// (gat.hip's wave_sum_xor adds in butterfly order: not interchangeable bit for bit)
+__device__ __forceinline__ float wave_sum_dpp(float v) {
 #define NPI_DPP_ADD(CTRL, ROWS) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWS, 0xf, false))
     NPI_DPP_ADD(0x111, 0xf);
     NPI_DPP_ADD(0x112, 0xf);
@@ -188,13 +162,14 @@ __device__ __forceinline__ float wave_max_nonneg_lane63(float v) {
 }
 
 // scale, bias and epilogue of a finished row r, then the store
-// (m_val, s_val: W_GAT_DST_FUSED only -- the row's softmax statistics, complete; every other mode passes zeros)
+// (m_val, s_val: the online softmax only -- the row's softmax statistics, complete; every other mode passes zeros)
 template <typename T, int VEC, int NCH, int WMODE, int EXACT>
 __device__ __forceinline__ void finish_row(const SegParams& P, const Lanes<VEC, NCH, WMODE, EXACT>& L,
                                            const float (&acc)[NCH][VEC], int r, int row_len, float m_val = 0.f, float s_val = 0.f) {
     T* __restrict__ dst = reinterpret_cast<T*>(P.out) + (int64_t)r * P.ldo;
     const T* __restrict__ bias = reinterpret_cast<const T*>(P.bias);
-    if constexpr (WMODE == W_GAT_DST_FUSED) {
+    constexpr ModeTraits MT = mode_traits(WMODE);
+    if constexpr (MT.softmax) {
         if (lane_id() == 0) {                                // an empty row: m = 0, s = 0, as the statistics pass leaves it
             P.m_out[r] = row_len > 0 ? m_val : 0.f;
             P.s_out[r] = row_len > 0 ? s_val : 0.f;
@@ -205,15 +180,15 @@ __device__ __forceinline__ void finish_row(const SegParams& P, const Lanes<VEC, 
         if (!L.act[c]) continue;
         float sc = 1.f;
         if (P.mean) sc = 1.f / (float)max(row_len, 1);       // scatter_mean's divisor (a launch argument, not a template one)
-        if (WMODE == W_GAT_DST || WMODE == W_GAT_DST_PRE) sc = 1.f / (P.s[(int64_t)r * P.H + L.hd[c]] + 1e-16f);
-        if (WMODE == W_GAT_DST_FUSED) sc = 1.f / ((row_len > 0 ? s_val : 0.f) + 1e-16f);
+        if (MT.row_norm) sc = 1.f / (P.s[(int64_t)r * P.H + L.hd[c]] + 1e-16f);
+        if (MT.softmax) sc = 1.f / ((row_len > 0 ? s_val : 0.f) + 1e-16f);
         float t[VEC];
 #pragma unroll
         for (int q = 0; q < VEC; ++q) {
             t[q] = fmaf(acc[c][q], sc, bias ? to_f32(bias[L.foff[c] + q]) : 0.f);
             if (P.relu) t[q] = (t[q] < 0.f) ? 0.f : t[q];            // keeps NaN, like torch.relu
         }
-        if ((WMODE == W_GAT_SRC || WMODE == W_GAT_SRC_PRE) && P.g_dst != nullptr) {
+        if (MT.rank1 && P.g_dst != nullptr) {
             const int h = L.hd[c];
             const float gd = P.g_dst[(int64_t)r * P.H + h], gs = P.g_src[(int64_t)r * P.H + h];
             const float* __restrict__ at = P.att + (int64_t)h * 2 * P.C + (L.foff[c] - h * P.C);
@@ -258,7 +233,6 @@ __device__ __forceinline__ void finish_row(const SegParams& P, const Lanes<VEC, 
 // parts of the entry stream, so that rows gathering cache-resident hub rows and rows gathering from HBM are in flight
 // together, was measured at C4: 2.43-2.46 / 2.56 / 3.02 ms against 2.41-2.45 -- the phases do not overlap; not kept.)
 static unsigned seg_grid(int n_items) { return (unsigned)ceil_div(n_items, SEG_WAVES); }
-__device__ __forceinline__ int item_block(int b, int) { return b; }
 
 
 // ---- rows cut by an item boundary: resolved INSIDE the launch ------------------------------------------------------------------
@@ -867,7 +841,7 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
                     for (int q = 0; q < VEC; ++q) dt[u] = fmaf(v[u][0][q], at_src[q], dt[u]);
                 }
 #pragma unroll
-                for (int u = 0; u < U; ++u) dt[u] = wave_sum(dt[u]);
+                for (int u = 0; u < U; ++u) dt[u] = wave_sum_dpp(dt[u]);
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const int k = kb + j + u;
@@ -976,7 +950,7 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
                 float dt = 0.f;
 #pragma unroll
                 for (int q = 0; q < VEC; ++q) dt = fmaf(v[0][q], at_src[q], dt);
-                dt = wave_sum(dt);
+                dt = wave_sum_dpp(dt);
                 const float z = rs_a[0] + dt;
                 const float e = z > 0.f ? z : z * P.slope;
                 if (e > m_run) {
@@ -1104,7 +1078,8 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
 template <int VEC, int NCH, int WMODE, int EXACT> struct seg_min_waves {
     // (EXACT == 2: the variant that also writes the finished rows' power-of-two scales -- 70 registers, 7 waves; measured at C4
     // against the 8-wave one: no difference in the launch, EXPERIMENTS A34)
-    static constexpr int value = (NCH == 1 && WMODE <= W_ARRAY && EXACT) ? (EXACT == 2 ? 7 : 8) : (NCH == 1 && WMODE == W_GAT_DST_FUSED) ? 6 : 1;
+    static constexpr int value = (NCH == 1 && !mode_traits(WMODE).per_head && EXACT) ? (EXACT == 2 ? 7 : 8)
+                               : (NCH == 1 && mode_traits(WMODE).softmax) ? 6 : 1;
 };
 
 template <typename T, int VEC, int NCH, int WMODE, int EXACT>
@@ -1118,14 +1093,14 @@ segsum_kernel(SegParams P) {
     if (threadIdx.x < SEG_WAVES) { s_meta[threadIdx.x].head_row = -1; s_meta[threadIdx.x].tail_row = -1; }   // "no partial"
     __syncthreads();
     const int wave = uniform_i(threadIdx.x >> 6);           // wave-uniform: LDS addresses derived from it stay in SGPRs
-    const int item = uniform_i(item_block(blockIdx.x, gridDim.x) * SEG_WAVES + wave);
+    const int item = uniform_i(blockIdx.x * SEG_WAVES + wave);
     Lanes<VEC, NCH, WMODE, EXACT> L;
     L.init(P);
     if (item < P.n_items) segsum_item<T, VEC, NCH, WMODE, EXACT>(P, L, item, &s_part[wave][0][0], s_meta + wave);
     auto finish = [&](const float (&acc)[NCH][VEC], int r, int row_len, float m_, float s_) {
         finish_row<T, VEC, NCH, WMODE, EXACT>(P, L, acc, r, row_len, m_, s_);
     };
-    resolve_block<VEC, NCH, ROWF, WMODE == W_GAT_DST_FUSED>(P, L, finish, s_part, s_meta, &s_arrived);
+    resolve_block<VEC, NCH, ROWF, mode_traits(WMODE).softmax>(P, L, finish, s_part, s_meta, &s_arrived);
 }
 
 // Narrow rows (F <= 32 VEC: hidden = 128 or 64 in f32, the reference's own model width): one row is only
@@ -1133,7 +1108,7 @@ segsum_kernel(SegParams P) {
 // g = lane / (64 / G) fetches entry G j + g -- and every group keeps its own partial sum of the open row.
 // Entries are still added in entry order (group 0, a possible row close, group 1, ...); at a row close
 // the G partials are folded across the lane groups (xor shuffles) and group 0 stores.  Same items and the same in-launch
-// resolution of cut rows as the wide path (the lanes of group 0 own the columns); W_NONE / W_ARRAY only.
+// resolution of cut rows as the wide path (the lanes of group 0 own the columns); the modes without a head (unweighted, per-entry weights) only.
 template <int VEC> struct GroupLanes { bool act[1]; int foff[1]; };
 
 template <typename T, int VEC, int G, int WMODE>
@@ -1208,7 +1183,7 @@ __device__ __forceinline__ void segsum_group_item(const SegParams& P, const int 
         const int nb = min(WAVE, k1 - kb);
         const int cv = (lane < nb) ? P.col[kb + lane] : 0;
         float wv = 1.f;
-        if (WMODE == W_ARRAY) wv = (lane < nb) ? P.w[kb + lane] : 0.f;
+        if (mode_traits(WMODE).lane_weight) wv = (lane < nb) ? P.w[kb + lane] : 0.f;
         for (int j = 0; j < nb; j += U * G) {
             float v[U][VEC];
             typename vec_of<T, VEC>::type raw[U];
@@ -1217,7 +1192,7 @@ __device__ __forceinline__ void segsum_group_item(const SegParams& P, const int 
             for (int u = 0; u < U; ++u) {
                 const int e = j + u * G + grp;             // this lane group's entry of wave instruction u
                 const int cu = __shfl(cv, min(e, nb - 1), WAVE);
-                we[u] = (WMODE == W_ARRAY) ? __shfl(wv, min(e, nb - 1), WAVE) : 1.f;
+                we[u] = mode_traits(WMODE).lane_weight ? __shfl(wv, min(e, nb - 1), WAVE) : 1.f;
                 raw[u] = zero_of<typename vec_of<T, VEC>::type>();
                 if (act && e < nb) raw[u] = load_raw<VEC, T>(((TWO_PART && cu >= split) ? x2T + (int64_t)(cu - split) * P.ldx : xT + (int64_t)cu * P.ldx) + foff);
             }
@@ -1233,7 +1208,7 @@ __device__ __forceinline__ void segsum_group_item(const SegParams& P, const int 
                     if (grp == g) {
 #pragma unroll
                         for (int q = 0; q < VEC; ++q)
-                            acc[q] = (WMODE == W_NONE) ? (acc[q] + v[u][q]) : fmaf(we[u], v[u][q], acc[q]);
+                            acc[q] = mode_traits(WMODE).plain_add ? (acc[q] + v[u][q]) : fmaf(we[u], v[u][q], acc[q]);
                     }
                 }
             }
@@ -1266,7 +1241,7 @@ segsum_group_kernel(SegParams P) {
     __syncthreads();
     const int wave = uniform_i(threadIdx.x >> 6);           // wave-uniform: LDS addresses derived from it stay in SGPRs
     const int lane = lane_id();
-    const int item = uniform_i(item_block(blockIdx.x, gridDim.x) * SEG_WAVES + wave);
+    const int item = uniform_i(blockIdx.x * SEG_WAVES + wave);
     if (item < P.n_items) segsum_group_item<T, VEC, G, WMODE>(P, item, &s_part[wave][0][0], s_meta + wave);
     GroupLanes<VEC> L;
     L.foff[0] = (lane % LG) * VEC;
@@ -1283,66 +1258,68 @@ segsum_group_kernel(SegParams P) {
     resolve_block<VEC, 1, ROWF>(P, L, finish, s_part, s_meta, &s_arrived);
 }
 
+// Only the kernels the dispatch below can select are instantiated: the GAT modes run on 16-byte f32 lanes alone (segsum_run
+// refuses anything else), the fused backward and the online softmax on one chunk per lane, and the kernels that also write row
+// scales (EXACT == 2) exist for the modes whose callers can ask for them.
+template <typename T, int VEC, int NCH, int WMODE, int EXACT> constexpr bool seg_has_kernel() {
+    constexpr ModeTraits MT = mode_traits(WMODE);
+    return !(EXACT == 2 && !MT.row_scales) && !(MT.per_head && !(VEC == 4 && sizeof(T) == 4)) &&
+           !((MT.fused_heads > 0 || MT.softmax) && NCH != 1);
+}
+
 template <typename T, int VEC, int NCH, int WMODE, int EXACT>
-static void launch_one(const SegParams& P, hipStream_t stream) {
-    dim3 grid(seg_grid(P.n_items)), block(SEG_THREADS);
-    segsum_kernel<T, VEC, NCH, WMODE, EXACT><<<grid, block, 0, stream>>>(P);
+static int launch_one(const SegParams& P, hipStream_t stream) {
+    if constexpr (seg_has_kernel<T, VEC, NCH, WMODE, EXACT>()) {
+        dim3 grid(seg_grid(P.n_items)), block(SEG_THREADS);
+        segsum_kernel<T, VEC, NCH, WMODE, EXACT><<<grid, block, 0, stream>>>(P);
+        return check_launch("npi_segsum");
+    } else {
+        if (mode_traits(WMODE).fused_heads > 0) set_error("npi_gat_backward_fused: needs heads * out_channels <= 256");
+        else if (mode_traits(WMODE).softmax) set_error("npi_gat_aggregate_fused: needs one head of at most 256 channels");
+        else set_error("npi_segsum: no kernel for weight mode %d on these rows", WMODE);
+        return NPI_ERR_ARG;
+    }
 }
 
 template <typename T, int VEC, int G, int WMODE>
-static void launch_group(const SegParams& P, hipStream_t stream) {
+static int launch_group(const SegParams& P, hipStream_t stream) {
     dim3 grid(seg_grid(P.n_items)), block(SEG_THREADS);
     segsum_group_kernel<T, VEC, G, WMODE><<<grid, block, 0, stream>>>(P);
-}
-template <typename T, int VEC, int G>
-static int launch_group_modes(const SegParams& P, int wmode, int mean, hipStream_t stream) {
-    if (wmode == W_NONE) launch_group<T, VEC, G, W_NONE>(P, stream);
-    else                 launch_group<T, VEC, G, W_ARRAY>(P, stream);
     return check_launch("npi_segsum");
 }
 
 template <typename T, int VEC, int NCH, int EXACT>
-static int launch_segsum(const SegParams& P, int wmode, int mean, hipStream_t stream) {
+static int launch_segsum(const SegParams& P, int wmode, hipStream_t stream) {
     if constexpr (NCH == 1 && !EXACT) {
         // narrow rows: several entries per wave instruction
-        if (wmode <= W_ARRAY) {
-            if (P.F <= 16 * VEC) return launch_group_modes<T, VEC, 4>(P, wmode, mean, stream);
-            if (P.F <= 32 * VEC) return launch_group_modes<T, VEC, 2>(P, wmode, mean, stream);
+        if (!mode_traits(wmode).per_head) {
+            const bool plain = wmode == W_NONE;
+            if (P.F <= 16 * VEC) return plain ? launch_group<T, VEC, 4, W_NONE>(P, stream) : launch_group<T, VEC, 4, W_ARRAY>(P, stream);
+            if (P.F <= 32 * VEC) return plain ? launch_group<T, VEC, 2, W_NONE>(P, stream) : launch_group<T, VEC, 2, W_ARRAY>(P, stream);
         }
     }
-    if (wmode == W_NONE) launch_one<T, VEC, NCH, W_NONE, EXACT>(P, stream);
-    else if (wmode == W_ARRAY) launch_one<T, VEC, NCH, W_ARRAY, EXACT>(P, stream);
-    else if (wmode == W_GAT_DST) {
-        if constexpr (VEC == 4 && sizeof(T) == 4) launch_one<T, VEC, NCH, W_GAT_DST, EXACT>(P, stream);
-    } else if (wmode == W_GAT_DST_PRE) {
-        if constexpr (VEC == 4 && sizeof(T) == 4) launch_one<T, VEC, NCH, W_GAT_DST_PRE, EXACT>(P, stream);
-    } else if (wmode == W_GAT_DST_FUSED) {
-        if constexpr (VEC == 4 && sizeof(T) == 4 && NCH == 1) launch_one<T, VEC, NCH, W_GAT_DST_FUSED, EXACT>(P, stream);
-        else {
-            set_error("npi_gat_aggregate_fused: needs one head of at most 256 channels");
-            return NPI_ERR_ARG;
-        }
-    } else if (wmode == W_GAT_SRC_PRE) {
-        if constexpr (VEC == 4 && sizeof(T) == 4) launch_one<T, VEC, NCH, W_GAT_SRC_PRE, EXACT>(P, stream);
-    } else if (is_fused_mode(wmode)) {
-        if constexpr (VEC == 4 && sizeof(T) == 4 && NCH == 1) {
-            dim3 grid(seg_grid(P.n_items)), block(SEG_THREADS);
-            if (wmode == W_GAT_SRC_FUSED) segsum_kernel<T, VEC, NCH, W_GAT_SRC_FUSED, EXACT><<<grid, block, 0, stream>>>(P);
-            else if (wmode == W_GAT_SRC_FUSED_H2) segsum_kernel<T, VEC, NCH, W_GAT_SRC_FUSED_H2, EXACT><<<grid, block, 0, stream>>>(P);
-            else if (wmode == W_GAT_SRC_FUSED_H4) segsum_kernel<T, VEC, NCH, W_GAT_SRC_FUSED_H4, EXACT><<<grid, block, 0, stream>>>(P);
-            else segsum_kernel<T, VEC, NCH, W_GAT_SRC_FUSED_H8, EXACT><<<grid, block, 0, stream>>>(P);
-        } else {
-            set_error("npi_gat_backward_fused: needs heads * out_channels <= 256");
-            return NPI_ERR_ARG;
-        }
-    } else {
-        if constexpr (VEC == 4 && sizeof(T) == 4) launch_one<T, VEC, NCH, W_GAT_SRC, EXACT>(P, stream);
+    switch (wmode) {
+#define NPI_SEG_MODE(W) case W: return launch_one<T, VEC, NCH, W, EXACT>(P, stream)
+        NPI_SEG_MODE(W_NONE);
+        NPI_SEG_MODE(W_ARRAY);
+        NPI_SEG_MODE(W_GAT_DST);
+        NPI_SEG_MODE(W_GAT_DST_PRE);
+        NPI_SEG_MODE(W_GAT_DST_FUSED);
+        NPI_SEG_MODE(W_GAT_SRC);
+        NPI_SEG_MODE(W_GAT_SRC_PRE);
+        NPI_SEG_MODE(W_GAT_SRC_FUSED);
+        NPI_SEG_MODE(W_GAT_SRC_FUSED_H2);
+        NPI_SEG_MODE(W_GAT_SRC_FUSED_H4);
+        NPI_SEG_MODE(W_GAT_SRC_FUSED_H8);
+#undef NPI_SEG_MODE
+        default: break;
     }
-    return check_launch("npi_segsum");
+    set_error("npi_segsum: unknown weight mode %d", wmode);
+    return NPI_ERR_ARG;
 }
 
 template <typename T, int VEC>
-static int dispatch_nch(const SegParams& P, int wmode, int mean, hipStream_t stream) {
+static int dispatch_nch(const SegParams& P, int wmode, hipStream_t stream) {
     const int per = WAVE * VEC;
     const int nch = (int)ceil_div(P.F, per);
     // the unguarded (EXACT) variant exists for 16-byte lanes only -- hidden = 256 / 512 / 768 / 1024, the widths the HBM
@@ -1351,11 +1328,11 @@ static int dispatch_nch(const SegParams& P, int wmode, int mean, hipStream_t str
 #define NPI_SEG_CASE(NC)                                                                    \
     case NC:                                                                                \
         if constexpr (VEC == 4 && NC == 1 && sizeof(T) == 4) {                              \
-            if (exact && P.scale_out != nullptr && (wmode <= W_ARRAY || is_fused_mode(wmode) || wmode == W_GAT_DST_FUSED)) \
-                return launch_segsum<T, VEC, NC, 2>(P, wmode, mean, stream);                \
+            if (exact && P.scale_out != nullptr && mode_traits(wmode).row_scales)           \
+                return launch_segsum<T, VEC, NC, 2>(P, wmode, stream);                      \
         }                                                                                   \
-        if constexpr (VEC == 4) { if (exact) return launch_segsum<T, VEC, NC, 1>(P, wmode, mean, stream); } \
-        return launch_segsum<T, VEC, NC, 0>(P, wmode, mean, stream)
+        if constexpr (VEC == 4) { if (exact) return launch_segsum<T, VEC, NC, 1>(P, wmode, stream); } \
+        return launch_segsum<T, VEC, NC, 0>(P, wmode, stream)
     switch (nch) {
         NPI_SEG_CASE(1);
         NPI_SEG_CASE(2);
@@ -1391,7 +1368,7 @@ int segsum_run(SegParams P, int wmode, int mean, int64_t nnz_max, int dtype, hip
                (((uintptr_t)P.carry % (4 * v)) == 0);
     };
     const int vec = aligned(4) ? 4 : (aligned(2) ? 2 : 1);
-    if (wmode >= W_GAT_DST) {
+    if (mode_traits(wmode).per_head) {
         if (dtype != NPI_F32 || vec != 4 || P.C % 4 != 0 || F > 4 * WAVE * 4) {
             set_error("npi_gat_aggregate: needs f32, 16-B aligned rows, out_channels %% 4 == 0 and heads*out_channels <= 1024");
             return NPI_ERR_ARG;
@@ -1408,13 +1385,13 @@ int segsum_run(SegParams P, int wmode, int mean, int64_t nnz_max, int dtype, hip
         Q.out = reinterpret_cast<float*>(out + f0 * es);
         Q.bias = bias ? reinterpret_cast<const float*>(bias + f0 * es) : nullptr;
         if (dtype == NPI_BF16) {
-            if (vec == 4) rc = dispatch_nch<bf16_t, 4>(Q, wmode, mean, stream);
-            else if (vec == 2) rc = dispatch_nch<bf16_t, 2>(Q, wmode, mean, stream);
-            else rc = dispatch_nch<bf16_t, 1>(Q, wmode, mean, stream);
+            if (vec == 4) rc = dispatch_nch<bf16_t, 4>(Q, wmode, stream);
+            else if (vec == 2) rc = dispatch_nch<bf16_t, 2>(Q, wmode, stream);
+            else rc = dispatch_nch<bf16_t, 1>(Q, wmode, stream);
         } else {
-            if (vec == 4) rc = dispatch_nch<float, 4>(Q, wmode, mean, stream);
-            else if (vec == 2) rc = dispatch_nch<float, 2>(Q, wmode, mean, stream);
-            else rc = dispatch_nch<float, 1>(Q, wmode, mean, stream);
+            if (vec == 4) rc = dispatch_nch<float, 4>(Q, wmode, stream);
+            else if (vec == 2) rc = dispatch_nch<float, 2>(Q, wmode, stream);
+            else rc = dispatch_nch<float, 1>(Q, wmode, stream);
         }
     }
     return rc;
