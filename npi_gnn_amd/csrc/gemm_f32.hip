@@ -1940,36 +1940,34 @@ gemm_bf16_ws_kernel(Bf16Args a) {
     }
 }
 
-static bool vec4_ok(const void* p, int64_t ld, int64_t inner_extent, int es = 4) {
+static bool vec4_ok(const void* p, int64_t ld, int64_t inner_extent, int es) {
     return ((uintptr_t)p % (4 * es) == 0) && (ld % 4 == 0) && (inner_extent % 4 == 0);
 }
 
+// Multiprocessors of the current device, asked once; 0 when the query fails
+static int queried_cus() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? n : 0;
+    }();
+    return cus;
+}
+// CUs of the current device in whole XCDs (256 on MI355X, and when nobody can say): the persistent kernels launch one workgroup per CU
+static int device_cus() {
+    const int n = queried_cus();
+    return n < 8 ? 256 : (n / 8) * 8;
+}
 // Workgroups of the dW GEMM (reduction over the nodes, split into slabs).  Two regimes:
 //   alone   : ~4 workgroups per CU (1,024): fastest when nothing else runs (1.30 ms at C4);
 //   shared  : about three workgroups per four CUs -- as a light resident it leaves room for the backward
 //             aggregation to co-run on every CU (functional.py, OVERLAP_STREAMS).  Step time at C4 by workgroup
 //             count: 128: 7.50, 160-224: 7.11-7.12, 256: 7.22, 384: 7.38, 512: 7.55 ms; alone that grid takes 1.77 ms.
 // The caller says which one applies (npi_linear_bwd_weight_ex's `shared`).
-// CUs of the current device (256 on MI355X), asked once: the persistent kernels launch one workgroup per CU
-static int device_cus() {
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8)
-            n = 256;
-        return (n / 8) * 8;
-    }();
-    return cus;
-}
 static int64_t dw_workgroups(bool shared) {
     if (!shared) return 1024;
-    static const int64_t ctas = [] {
-        long v = 0;
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) v = (3 * cus) / 4;
-        if (v > 1024) v = 1024;                          // the workspace is sized for the 1,024-workgroup plan
-        return (int64_t)(v > 0 ? v : 192);
-    }();
-    return ctas;
+    const int64_t v = (3 * queried_cus()) / 4;
+    if (v > 1024) return 1024;                               // the workspace is sized for the 1,024-workgroup plan
+    return v > 0 ? v : 192;
 }
 static int pick_splits(int64_t M, int64_t tiles, bool shared) {
     int64_t want = ceil_div(dw_workgroups(shared), tiles);
@@ -1977,172 +1975,216 @@ static int pick_splits(int64_t M, int64_t tiles, bool shared) {
     int64_t s = want < maxs ? want : maxs;
     return (int)(s < 1 ? 1 : s);
 }
-
-// Cover the (M x N) output with the FAST kernel on full tiles and the 128x128 EDGE kernel on the
-// two ragged strips.  `splits` slabs along the contraction; the fast path needs K % BK == 0.
-// dtype_in: storage of A and B; dtype_out: storage of C and bias.  bf16 runs the guarded kernel only.
-template <int AMODE, int BMODE>
-// `mode`: 0 = exact-f32 MFMA kernels, 1 = bf16 matrix cores where the tile shape allows (3-way split for f32 storage).
-// `scratch`: caller memory for the re-laid weight matrix (npi_linear_workspace_bytes).  Nothing is allocated here: a shape that
-// takes the matrix-core kernels without it is an error (ABI 3; the entry points require the workspace).
-// `k_valid` > 0 (AMODE 0, f32): A has a.K columns of which only the first k_valid are data, the rest ZERO, and B has only
-// k_valid rows (NPI_GEMM_A_ZERO_PADDED): the split kernel runs on a.K with the weight planes zero-extended, everything
-// else (guarded strips, the exact kernels) on k_valid.
-static int launch_gemm(bool v4, GemmArgs a, int splits, hipStream_t stream, int dtype_in = NPI_F32, int dtype_out = NPI_F32,
-                       int mode = 1, void* scratch = nullptr, int k_valid = 0, bool prepared = false, int reserve_cus = 0,
-                       const float* a_scales = nullptr) {
-    // `a_scales` (NPI_GEMM_SPLIT_F16X2): the power-of-two scale of every row of A (npi_row_scales): the split kernel then runs its
-    // fp16 x 2 variant -- three matrix products per tile pair instead of six, the same f32-level accuracy -- on fp16 weight planes
-    // `reserve_cus`: the persistent kernels take that many workgroups fewer than CUs (a multiple of 8: one per XCD), so that a
-    // kernel resident beside them -- a collective's -- holds CUs they do not wait for (NPI_GEMM_RESERVE_CUS)
+// Grid of a persistent kernel over `ntiles` tiles: one workgroup per CU, a multiple of 8 (XCDs).  `reserve_cus`: that many
+// workgroups fewer than CUs (a multiple of 8: one per XCD), so that a kernel resident beside them -- a collective's -- holds
+// CUs they do not wait for (NPI_GEMM_RESERVE_CUS)
+static int persistent_grid(int64_t ntiles, int reserve_cus) {
     const int cu_slots = device_cus() - ((reserve_cus < 0 ? 0 : reserve_cus > 128 ? 128 : reserve_cus) / 8) * 8;
-    // `prepared`: `scratch` already holds the re-laid weight matrix of THIS B / K / N / BMODE (npi_linear_prepare): no
-    // preparation launch in front of the GEMM
-    const bool bf16_in = dtype_in == NPI_BF16 && dtype_out == NPI_F32;          // dW of the bf16 path: bf16 operands, f32 slabs
-    // (a 128 x 256 tile of the exact-f32 kernel, one workgroup per CU, measured 3-10 % SLOWER than 128 x 128 at C4 in round 1:
-    // 1.49 / 1.32 / 1.67 ms vs 1.41 / 1.28 / 1.52 ms -- not built)
-    const int kv = k_valid > 0 ? k_valid : a.K;
-    if (kv != a.K) {
-        const bool can_split = AMODE == 0 && v4 && (a.K % BK == 0) && dtype_in == NPI_F32 && dtype_out == NPI_F32 && splits == 1 &&
-                               mode != 0 && a.ep.colsum == nullptr && a.M >= 128 && a.N >= 128 && ((uintptr_t)a.C % 16 == 0) &&
-                               (a.ldc % 4 == 0) && ((uintptr_t)a.ep.bias % 16 == 0);
-        if (!can_split) { a.K = kv; a.kchunk = (int)align_up(kv, BK); }          // the pad columns are zero: dropping them is exact
+    return (int)(ntiles < cu_slots ? ((ntiles + 7) / 8) * 8 : cu_slots);
+}
+
+// How one GEMM is to run: what its entry point made of the flags and of the operands' layout (GemmArgs says what is computed)
+struct GemmCall {
+    bool v4;                             // both operands take 16-byte loads (vec4_ok)
+    int splits = 1;                      // slabs along the contraction
+    int dtype_in = NPI_F32, dtype_out = NPI_F32;     // storage of A and B; of C and bias
+    bool exact = false;                  // NPI_GEMM_EXACT_F32: the f32 MFMA kernels only; otherwise the bf16 matrix cores where the
+                                         // tile shape allows (3-way split for f32 storage)
+    void* planes = nullptr;              // caller memory for the re-laid weight matrix (npi_linear_workspace_bytes): nothing is
+                                         // allocated here, a shape that takes the matrix-core kernels without it is an error
+    int k_valid = 0;                     // > 0 (NPI_GEMM_A_ZERO_PADDED; AMODE 0, f32): only the first k_valid of A's a.K columns are
+                                         // data, the rest ZERO, and B has k_valid rows: the split kernel runs on a.K with the
+                                         // weight planes zero-extended, everything else on k_valid
+    bool prepared = false;               // npi_linear_prepare filled `planes` for THIS B / K / N / BMODE: no preparation launch
+    int reserve_cus = 0;                 // see persistent_grid
+    const float* row_scales = nullptr;   // NPI_GEMM_SPLIT_F16X2: the power-of-two scale of every row of A (npi_row_scales): the split
+                                         // kernel runs on fp16 x 2 planes, three matrix products per tile pair instead of six
+    hipStream_t stream;
+    bool f32() const { return dtype_in == NPI_F32 && dtype_out == NPI_F32; }
+    bool bf16() const { return dtype_in == NPI_BF16 && dtype_out == NPI_BF16; }
+    bool bf16_to_f32() const { return dtype_in == NPI_BF16 && dtype_out == NPI_F32; }     // dW of the bf16 path: f32 slabs
+};
+
+// The kernels that cover an (M x N) output, in 128 x 128 tiles:
+enum class GemmPath {
+    Bf16Persistent,    // bf16 storage on the bf16 MFMA pipeline (K % 64 == 0, 16-byte aligned rows), the whole output
+    SplitPersistent,   // f32 storage as bf16 x 3 / fp16 x 2 planes on the matrix cores; a guarded strip right of the last full column tile
+    FastAndStrips,     // the exact FAST kernel on the full tiles, the guarded EDGE kernel on the two ragged strips
+    OneGuarded,        // a ragged output whose tiles all fit the chip at once: ONE guarded launch
+    StripsOnly,        // no full tile, a K tail or unaligned operands: the guarded kernel on everything
+};
+struct GemmPlan {
+    GemmPath path;
+    int K, kchunk, kv;      // contraction of the unguarded kernels, after the zero-pad decision; kv: of the guarded one (rows B has)
+    int fm, fn, tm, tn;     // full tiles (0 unless the operands serve the unguarded kernels); all tiles, ragged ones included
+    int split_tm;           // row tiles of the persistent kernels: all of them, the last one starts at M - 128
+    int col_tiles, grid;    // their column tiles, `wide_n`: 256 wide (each A element is split once); their workgroups
+    bool wide_n, f16;
+    const char* error; int status;      // null, or why the call is refused: an epilogue the path cannot serve, no `planes`
+};
+// Decides, launches nothing (its one look at the device is the cached CU count behind persistent_grid).  `a_rows`: AMODE 0, the only layout of A the persistent kernels read.
+// (a 128 x 256 tile of the exact-f32 kernel, one workgroup per CU, measured 3-10 % SLOWER than 128 x 128 at C4 in round 1:
+// 1.49 / 1.32 / 1.67 ms vs 1.41 / 1.28 / 1.52 ms -- not built)
+static GemmPlan plan_gemm(const GemmArgs& a, const GemmCall& c, bool a_rows) {
+    GemmPlan p{};
+    p.K = a.K, p.kchunk = a.kchunk, p.kv = c.k_valid > 0 ? c.k_valid : a.K;
+    p.tm = (int)ceil_div(a.M, 128), p.tn = (int)ceil_div(a.N, 128);
+    const auto refuse = [&](int status, const char* why) { p.error = why, p.status = status; return p; };
+    const auto fast_ok = [&](int K) { return c.v4 && (K % BK == 0) && (K > 0) && (c.f32() || c.bf16_to_f32()); };
+    const bool persistent_ok = a_rows && c.splits == 1 && !c.exact && a.ep.colsum == nullptr && (a.ldc % 4 == 0);
+    const bool c16 = ((uintptr_t)a.C % 16 == 0) && ((uintptr_t)a.ep.bias % 16 == 0);
+    const auto split_ok = [&](int K) { return fast_ok(K) && a.M >= 128 && a.N >= 128 && persistent_ok && c16; };
+    if (p.kv != a.K && !(c.f32() && split_ok(a.K))) p.K = p.kv, p.kchunk = (int)align_up(p.kv, BK);      // zero columns: dropping them is exact
+    p.fm = fast_ok(p.K) ? a.M / 128 : 0, p.fn = fast_ok(p.K) ? a.N / 128 : 0, p.wide_n = (a.N % 256 == 0);
+    const auto persistent = [&](GemmPath path, int col_tiles, const char* no_planes) {
+        p.path = path, p.split_tm = p.tm, p.col_tiles = col_tiles;
+        p.grid = persistent_grid((int64_t)p.split_tm * col_tiles, c.reserve_cus);
+        return c.planes == nullptr ? refuse(NPI_ERR_WORKSPACE, no_planes) : p;
+    };
+    if (persistent_ok && c.bf16() && p.K % 64 == 0 && a.N % 128 == 0 && a.M >= 128 && (a.lda % 8 == 0) && ((uintptr_t)a.A % 16 == 0) &&
+        ((uintptr_t)a.C % 8 == 0))
+        return persistent(GemmPath::Bf16Persistent, p.wide_n ? a.N / 256 : a.N / 128,
+                          "gemm: the bf16 matrix-core kernel needs the caller's workspace (npi_linear_workspace_bytes)");
+    const bool split = split_ok(p.K);
+    if (a.ep.r2_row0 != nullptr && !(split && a.N % 128 == 0 && p.kv == p.K && a.ep.bias == nullptr))
+        return refuse(NPI_ERR_ARG, "gemm: the rank-2 epilogue needs the split kernel over the whole output (npi_linear_bwd_data_rank2_supported)");
+    if (a.ep.sc0 != nullptr && !(split && (a.N == 128 || a.N == 256) && p.kv == p.K && a.ep.r2_row0 == nullptr))
+        return refuse(NPI_ERR_ARG, "gemm: the row-dot epilogue needs the split kernel with one column tile (npi_linear_fwd_scores_supported)");
+    if (split) {
+        p.f16 = c.row_scales != nullptr && p.kv == p.K;      // (zero-padded operands keep the bf16 x 3 planes)
+        return persistent(GemmPath::SplitPersistent, p.wide_n ? a.N / 256 : p.fn,
+                          "gemm: the split kernel needs the caller's workspace (npi_linear_workspace_bytes)");
     }
-    const bool fast_ok = v4 && (a.K % BK == 0) && (a.K > 0) && ((dtype_in == NPI_F32 && dtype_out == NPI_F32) || bf16_in);
-    const int bm = 128, bn = 128;
-    const int fm = fast_ok ? a.M / bm : 0, fn = fast_ok ? a.N / bn : 0;    // full tiles
-    // bf16 storage: interior tiles on the bf16 MFMA pipeline (K % 64 == 0, 16-byte aligned rows); the rest guarded
-    const bool bf16_ws = AMODE == 0 && splits == 1 && dtype_in == NPI_BF16 && dtype_out == NPI_BF16 && a.ep.colsum == nullptr &&
-                         a.K % 64 == 0 && a.N % 128 == 0 && a.M >= 128 && (a.lda % 8 == 0) && (a.ldc % 4 == 0) &&
-                         ((uintptr_t)a.A % 16 == 0) && ((uintptr_t)a.C % 8 == 0) && mode != 0;
-    if (bf16_ws) {
-        uint16_t* blocks = reinterpret_cast<uint16_t*>(scratch);
-        const int64_t nel = (int64_t)a.N * a.K;
-        if (blocks == nullptr) {
-            set_error("gemm: the bf16 matrix-core kernel needs the caller's workspace (npi_linear_workspace_bytes)");
-            return NPI_ERR_WORKSPACE;
-        }
-        if (!(prepared && scratch != nullptr))
-            bf16_blocks_kernel<<<(unsigned)ceil_div(nel, 256), 256, 0, stream>>>(reinterpret_cast<const uint16_t*>(a.B), a.ldb, a.K, a.N, BMODE, blocks);
-        const int bfm = (int)ceil_div(a.M, 128);             // the last row tile starts at M - 128: no guarded strip launch
-        const bool wide_n = (a.N % 256 == 0);
-        const int btn = wide_n ? a.N / 256 : a.N / 128;
-        Bf16Args ba{reinterpret_cast<const uint16_t*>(a.A), a.lda, blocks, reinterpret_cast<uint16_t*>(a.C), a.ldc, a.M, a.N, a.K,
-                    reinterpret_cast<const uint16_t*>(a.ep.bias), a.ep.rowscale, a.ep.relu, bfm, btn};
-        const int64_t ntiles = (int64_t)bfm * btn;
-        const int grid = (int)(ntiles < cu_slots ? ((ntiles + 7) / 8) * 8 : cu_slots);
-        if (wide_n) gemm_bf16_ws_kernel<4><<<grid, WS_THREADS, 0, stream>>>(ba);
-        else        gemm_bf16_ws_kernel<2><<<grid, WS_THREADS, 0, stream>>>(ba);
-        return NPI_OK;
-    }
-    const bool split = fast_ok && AMODE == 0 && splits == 1 && mode != 0 && a.ep.colsum == nullptr &&
-                       ((uintptr_t)a.C % 16 == 0) && (a.ldc % 4 == 0) && ((uintptr_t)a.ep.bias % 16 == 0);
-    int split_tm = 0;                                        // m-tiles the split kernel covered (all of them, when it ran)
-    if (a.ep.r2_row0 != nullptr && !(fm > 0 && fn > 0 && split && a.N % 128 == 0 && kv == a.K && a.ep.bias == nullptr)) {
-        set_error("gemm: the rank-2 epilogue needs the split kernel over the whole output (npi_linear_bwd_data_rank2_supported)");
-        return NPI_ERR_ARG;
-    }
-    if (a.ep.sc0 != nullptr && !(fm > 0 && fn > 0 && split && (a.N == 128 || a.N == 256) && kv == a.K && a.ep.r2_row0 == nullptr)) {
-        set_error("gemm: the row-dot epilogue needs the split kernel with one column tile (npi_linear_fwd_scores_supported)");
-        return NPI_ERR_ARG;
-    }
-    if (fm > 0 && fn > 0 && split) {
-        // the three bf16 planes of B live in the caller's workspace (W is small: 3 * 2 * K * N bytes)
-        uint16_t* planes = reinterpret_cast<uint16_t*>(scratch);
-        const int64_t nel = (int64_t)a.N * a.K;
-        if (planes == nullptr) {
-            set_error("gemm: the split kernel needs the caller's workspace (npi_linear_workspace_bytes)");
-            return NPI_ERR_WORKSPACE;
-        }
-        const bool f16 = a_scales != nullptr && kv == a.K;   // (zero-padded operands keep the bf16 x 3 planes)
-        if (!(prepared && scratch != nullptr)) {
-            if (f16) split_planes_f16_kernel<<<(unsigned)a.N, 256, 0, stream>>>(a.B, a.ldb, a.K, a.N, BMODE, planes, f16_inv_of(planes, a.K, a.N));
-            else split_planes_kernel<<<(unsigned)ceil_div(nel, 256), 256, 0, stream>>>(a.B, a.ldb, a.K, a.N, BMODE, planes, kv);
-        }
-        const bool wide_n = (a.N % 256 == 0);                // 128 x 256 tiles: each A element is split once
-        const int tn = wide_n ? a.N / 256 : fn;
-        split_tm = (int)ceil_div(a.M, 128);                  // a ragged last m-tile overlaps its neighbour (TileWalk::row0)
-        SplitArgs sa{a.A, a.lda, planes, a.C, a.ldc, a.M, a.N, a.K, a.ep, split_tm, tn, f16 ? a_scales : nullptr,
-                     f16 ? f16_inv_of(planes, a.K, a.N) : nullptr};
-        const int64_t ntiles = (int64_t)split_tm * tn;
-        const int grid = (int)(ntiles < cu_slots ? ((ntiles + 7) / 8) * 8 : cu_slots);      // one workgroup per CU, multiple of 8 (XCDs)
-        if (f16) {
-            if (a.ep.r2_row0 != nullptr) {
-                if (wide_n) gemm_split_ws_kernel<4, 1, true><<<grid, WS_THREADS, 0, stream>>>(sa);
-                else        gemm_split_ws_kernel<2, 1, true><<<grid, WS_THREADS, 0, stream>>>(sa);
-            } else if (a.ep.sc0 != nullptr) {
-                if (wide_n) gemm_split_ws_kernel<4, 2, true><<<grid, WS_THREADS, 0, stream>>>(sa);
-                else        gemm_split_ws_kernel<2, 2, true><<<grid, WS_THREADS, 0, stream>>>(sa);
-            } else {
-                if (wide_n) gemm_split_ws_kernel<4, 0, true><<<grid, WS_THREADS, 0, stream>>>(sa);
-                else        gemm_split_ws_kernel<2, 0, true><<<grid, WS_THREADS, 0, stream>>>(sa);
-            }
-        } else if (a.ep.r2_row0 != nullptr) {
-            if (wide_n) gemm_split_ws_kernel<4, 1><<<grid, WS_THREADS, 0, stream>>>(sa);
-            else        gemm_split_ws_kernel<2, 1><<<grid, WS_THREADS, 0, stream>>>(sa);
-        } else if (a.ep.sc0 != nullptr) {
-            if (wide_n) gemm_split_ws_kernel<4, 2><<<grid, WS_THREADS, 0, stream>>>(sa);
-            else        gemm_split_ws_kernel<2, 2><<<grid, WS_THREADS, 0, stream>>>(sa);
-        } else {
-            if (wide_n) gemm_split_ws_kernel<4><<<grid, WS_THREADS, 0, stream>>>(sa);
-            else        gemm_split_ws_kernel<2><<<grid, WS_THREADS, 0, stream>>>(sa);
-        }
-    }
-    // edge strips in 128 x 128 tiles
-    const int tm = (int)ceil_div(a.M, 128), tn = (int)ceil_div(a.N, 128);
     // a ragged output the matrix-core-bf16 kernels did not take (the reference's 178-wide first layer): when ALL its tiles fit
     // the chip at once, ONE guarded launch covers it -- the unguarded kernel on the full tiles plus a launch per ragged strip were
     // three launches of 20-29 us each for a [1,992 x 178] output, each of them a single round of latency
-    const bool one_guarded = split_tm == 0 && fm > 0 && fn > 0 && (a.M % bm != 0 || a.N % bn != 0) &&
-                             (int64_t)tm * tn * splits <= 256;
-    if (split_tm == 0 && fm > 0 && fn > 0 && !one_guarded) {
-        GemmArgs f = a;
-        f.tm0 = 0; f.tn0 = 0;
-        if (bf16_in)   gemm_fast_kernel<AMODE, BMODE, 2, 2, bf16_t><<<dim3(fn, fm, splits), GEMM_THREADS, 0, stream>>>(f);
-        else           gemm_fast_kernel<AMODE, BMODE, 2, 2><<<dim3(fn, fm, splits), GEMM_THREADS, 0, stream>>>(f);
+    const bool ragged = a.M % 128 != 0 || a.N % 128 != 0;
+    p.path = p.fm == 0 || p.fn == 0 ? GemmPath::StripsOnly
+             : ragged && (int64_t)p.tm * p.tn * c.splits <= 256 ? GemmPath::OneGuarded : GemmPath::FastAndStrips;
+    return p;
+}
+
+// One selection point per kernel family: every instantiation the library holds is named here, once.
+using GemmKernel = void (*)(GemmArgs);
+using SplitKernel = void (*)(SplitArgs);
+using DwKernel = void (*)(DwArgs);
+static SplitKernel split_kernel_of(bool wide_n, int epi, bool f16) {          // epi: 0 plain, 1 rank-2, 2 row dots
+    static constexpr SplitKernel kernels[2][3][2] = {
+        {{gemm_split_ws_kernel<2, 0, false>, gemm_split_ws_kernel<2, 0, true>},
+         {gemm_split_ws_kernel<2, 1, false>, gemm_split_ws_kernel<2, 1, true>},
+         {gemm_split_ws_kernel<2, 2, false>, gemm_split_ws_kernel<2, 2, true>}},
+        {{gemm_split_ws_kernel<4, 0, false>, gemm_split_ws_kernel<4, 0, true>},
+         {gemm_split_ws_kernel<4, 1, false>, gemm_split_ws_kernel<4, 1, true>},
+         {gemm_split_ws_kernel<4, 2, false>, gemm_split_ws_kernel<4, 2, true>}}};
+    return kernels[wide_n][epi][f16];
+}
+template <int AMODE, int BMODE>
+static GemmKernel edge_kernel_of(const GemmCall& c) {
+    static constexpr GemmKernel kernels[3][2] = {
+        {gemm_edge_kernel<AMODE, BMODE, false, float, float>, gemm_edge_kernel<AMODE, BMODE, true, float, float>},
+        {gemm_edge_kernel<AMODE, BMODE, false, bf16_t, float>, gemm_edge_kernel<AMODE, BMODE, true, bf16_t, float>},
+        {gemm_edge_kernel<AMODE, BMODE, false, bf16_t, bf16_t>, gemm_edge_kernel<AMODE, BMODE, true, bf16_t, bf16_t>}};
+    return kernels[c.bf16() ? 2 : c.dtype_in == NPI_BF16 ? 1 : 0][c.v4];
+}
+static DwKernel dw_kernel_of(bool wide_n, bool bf16_in, bool f16) {
+    static constexpr DwKernel kernels[2][3] = {
+        {gemm_dw_split_kernel<2, false, false>, gemm_dw_split_kernel<2, false, true>, gemm_dw_split_kernel<2, true, false>},
+        {gemm_dw_split_kernel<4, false, false>, gemm_dw_split_kernel<4, false, true>, gemm_dw_split_kernel<4, true, false>}};
+    return kernels[wide_n][bf16_in ? 2 : f16 ? 1 : 0];
+}
+// The launchers: `a` carries the plan's K / kchunk.  `bmode`: the layout of B the preparation kernels read.
+static void launch_bf16_persistent(const GemmArgs& a, const GemmCall& c, const GemmPlan& p, int bmode) {
+    uint16_t* blocks = reinterpret_cast<uint16_t*>(c.planes);
+    if (!c.prepared)
+        bf16_blocks_kernel<<<(unsigned)ceil_div((int64_t)a.N * a.K, 256), 256, 0, c.stream>>>(reinterpret_cast<const uint16_t*>(a.B), a.ldb,
+                                                                                               a.K, a.N, bmode, blocks);
+    Bf16Args ba{reinterpret_cast<const uint16_t*>(a.A), a.lda, blocks, reinterpret_cast<uint16_t*>(a.C), a.ldc, a.M, a.N, a.K,
+                reinterpret_cast<const uint16_t*>(a.ep.bias), a.ep.rowscale, a.ep.relu, p.split_tm, p.col_tiles};
+    (p.wide_n ? gemm_bf16_ws_kernel<4> : gemm_bf16_ws_kernel<2>)<<<p.grid, WS_THREADS, 0, c.stream>>>(ba);
+}
+static void launch_split_persistent(const GemmArgs& a, const GemmCall& c, const GemmPlan& p, int bmode) {
+    // the three bf16 planes of B live in the caller's workspace (W is small: 3 * 2 * K * N bytes)
+    uint16_t* planes = reinterpret_cast<uint16_t*>(c.planes);
+    float* inv = p.f16 ? f16_inv_of(planes, a.K, a.N) : nullptr;
+    if (!c.prepared) {
+        if (p.f16) split_planes_f16_kernel<<<(unsigned)a.N, 256, 0, c.stream>>>(a.B, a.ldb, a.K, a.N, bmode, planes, inv);
+        else split_planes_kernel<<<(unsigned)ceil_div((int64_t)a.N * a.K, 256), 256, 0, c.stream>>>(a.B, a.ldb, a.K, a.N, bmode, planes, p.kv);
     }
-    const bool fast_ran = fm > 0 && fn > 0 && !one_guarded;
-    const int em = split_tm > 0 ? split_tm : (fast_ran ? fm * bm / 128 : 0);       // first edge tile row
-    const int en = fast_ran ? fn * bn / 128 : 0;                                    // first edge tile column
-    auto edge = [&](int tm0, int tn0, int nm, int nn) {
-        if (nm <= 0 || nn <= 0) return;
-        GemmArgs e = a;
-        e.tm0 = tm0; e.tn0 = tn0;
-        if (kv != a.K) { e.K = kv; e.kchunk = (int)align_up(kv, BK); }          // B has kv rows only
-        const dim3 g(nn, nm, splits);
-        if (dtype_in == NPI_BF16 && dtype_out == NPI_BF16) {
-            if (v4) gemm_edge_kernel<AMODE, BMODE, true, bf16_t, bf16_t><<<g, GEMM_THREADS, 0, stream>>>(e);
-            else    gemm_edge_kernel<AMODE, BMODE, false, bf16_t, bf16_t><<<g, GEMM_THREADS, 0, stream>>>(e);
-        } else if (dtype_in == NPI_BF16) {
-            if (v4) gemm_edge_kernel<AMODE, BMODE, true, bf16_t, float><<<g, GEMM_THREADS, 0, stream>>>(e);
-            else    gemm_edge_kernel<AMODE, BMODE, false, bf16_t, float><<<g, GEMM_THREADS, 0, stream>>>(e);
-        } else {
-            if (v4) gemm_edge_kernel<AMODE, BMODE, true><<<g, GEMM_THREADS, 0, stream>>>(e);
-            else    gemm_edge_kernel<AMODE, BMODE, false><<<g, GEMM_THREADS, 0, stream>>>(e);
-        }
-    };
-    if (em > 0 && en > 0) {
-        edge(em, 0, tm - em, tn);        // bottom strip (all columns)
-        edge(0, en, em, tn - en);        // right strip (full rows only)
-    } else {
-        edge(0, 0, tm, tn);
+    SplitArgs sa{a.A, a.lda, planes, a.C, a.ldc, a.M, a.N, a.K, a.ep, p.split_tm, p.col_tiles, p.f16 ? c.row_scales : nullptr, inv};
+    const int epi = a.ep.r2_row0 != nullptr ? 1 : a.ep.sc0 != nullptr ? 2 : 0;
+    split_kernel_of(p.wide_n, epi, p.f16)<<<p.grid, WS_THREADS, 0, c.stream>>>(sa);
+}
+template <int AMODE, int BMODE>
+static void launch_fast(GemmArgs a, const GemmCall& c, const GemmPlan& p) {
+    a.tm0 = 0, a.tn0 = 0;
+    const GemmKernel kernel = c.bf16_to_f32() ? gemm_fast_kernel<AMODE, BMODE, 2, 2, bf16_t> : gemm_fast_kernel<AMODE, BMODE, 2, 2, float>;
+    kernel<<<dim3(p.fn, p.fm, c.splits), GEMM_THREADS, 0, c.stream>>>(a);
+}
+// the guarded kernel on the nm x nn tiles from (tm0, tn0) on
+template <int AMODE, int BMODE>
+static void launch_strip(GemmArgs a, const GemmCall& c, int tm0, int tn0, int nm, int nn) {
+    a.tm0 = tm0, a.tn0 = tn0;
+    if (nm > 0 && nn > 0) edge_kernel_of<AMODE, BMODE>(c)<<<dim3(nn, nm, c.splits), GEMM_THREADS, 0, c.stream>>>(a);
+}
+// C = A B as GemmArgs describes it, on the path plan_gemm picks.  The unguarded kernels need K % BK == 0.
+template <int AMODE, int BMODE>
+static int launch_gemm(GemmArgs a, const GemmCall& c) {
+    const GemmPlan p = plan_gemm(a, c, AMODE == 0);
+    if (p.error != nullptr) return set_error("%s", p.error), p.status;
+    a.K = p.K, a.kchunk = p.kchunk;
+    GemmArgs g = a;                                          // the guarded kernel: B has kv rows only
+    if (p.kv != p.K) { g.K = p.kv; g.kchunk = (int)align_up(p.kv, BK); }
+    switch (p.path) {
+    case GemmPath::Bf16Persistent: launch_bf16_persistent(a, c, p, BMODE); break;
+    case GemmPath::SplitPersistent:
+        launch_split_persistent(a, c, p, BMODE);
+        launch_strip<AMODE, BMODE>(g, c, 0, p.fn, p.tm, p.tn - p.fn);                // right strip
+        break;
+    case GemmPath::FastAndStrips:
+        launch_fast<AMODE, BMODE>(a, c, p);
+        launch_strip<AMODE, BMODE>(g, c, p.fm, 0, p.tm - p.fm, p.tn);                // bottom strip (all columns)
+        launch_strip<AMODE, BMODE>(g, c, 0, p.fn, p.fm, p.tn - p.fn);                // right strip (full rows only)
+        break;
+    case GemmPath::OneGuarded:
+    case GemmPath::StripsOnly: launch_strip<AMODE, BMODE>(g, c, 0, 0, p.tm, p.tn); break;
     }
     return NPI_OK;
 }
 
 }  // namespace npi
-
 using namespace npi;
 
 static inline const float* fp(const void* p) { return reinterpret_cast<const float*>(p); }
 static inline const void* advance(const void* p, int64_t elems, int es) { return reinterpret_cast<const char*>(p) + elems * es; }
 
-
-// per-call arithmetic of the *_ex entry points -> launch_gemm's mode
-// (no process-wide default any more: 0 = the 3-way bf16 split wherever the shape takes it, NPI_GEMM_EXACT_F32 = the f32 MFMA kernels)
-static int gemm_mode_of(int flags) { return (flags & NPI_GEMM_EXACT_F32) ? 0 : 1; }
+// per-call arithmetic of the *_ex entry points -> GemmCall::exact
+// (no process-wide default any more: the 3-way bf16 split wherever the shape takes it, NPI_GEMM_EXACT_F32 = the f32 MFMA kernels)
+static bool exact_of(int flags) { return (flags & NPI_GEMM_EXACT_F32) != 0; }
 static bool scratch_ok(void* ws, int64_t ws_bytes, int64_t K, int64_t N) {
     return ws != nullptr && ws_bytes >= npi_linear_workspace_bytes(K, N) && ((uintptr_t)ws % 16) == 0;
+}
+
+// What the four data-GEMM entry points (npi_linear_fwd_ex, npi_linear_bwd_data_ex, npi_linear_fwd_scores,
+// npi_linear_bwd_data_rank2) ask of their arguments, in the order their status codes depend on
+struct LinearCheck {
+    const char* who;                     // the public entry point: every message names it
+    int64_t M, K, N; int dtype;
+    bool pointers, leading_dims;         // every operand the call needs is there; every leading dimension covers its row
+    bool aligned;                        // (entry points without a guarded path) 16-byte aligned operands
+    void* ws; int64_t ws_bytes, ws_K;    // the weight workspace, for a [ws_K, N] matrix
+};
+constexpr int LINEAR_EMPTY = 1;          // no rows: done, and the pointers are not looked at (not an NPI_* status)
+static int check_linear(const LinearCheck& c) {
+    const auto fail = [&](int status, const char* what) { return set_error("%s: %s", c.who, what), status; };
+    if (!(c.M >= 0 && c.K > 0 && c.N > 0)) return fail(NPI_ERR_ARG, "bad size");
+    if (!(c.M < 0x7fffffff && c.K < 0x7fffffff && c.N < 0x7fffffff)) return fail(NPI_ERR_ARG, "size > int32");
+    if (c.dtype != NPI_F32 && c.dtype != NPI_BF16) return fail(NPI_ERR_ARG, "bad dtype");
+    if (c.M == 0) return LINEAR_EMPTY;
+    if (!c.pointers) return fail(NPI_ERR_ARG, "null pointer");
+    if (!c.leading_dims) return fail(NPI_ERR_ARG, "leading dimension too small (with NPI_GEMM_A_ZERO_PADDED: lda >= K rounded up to 128)");
+    if (!c.aligned) return fail(NPI_ERR_ARG, "operands must be 16-byte aligned with leading dimensions % 4 == 0");
+    if (!scratch_ok(c.ws, c.ws_bytes, c.ws_K, c.N)) return fail(NPI_ERR_WORKSPACE, "workspace too small or not 16-byte aligned");
+    return NPI_OK;
 }
 
 extern "C" int64_t npi_linear_workspace_bytes(int64_t K, int64_t N) {
@@ -2224,36 +2266,28 @@ extern "C" int npi_linear_fwd_ex(const void* A, int64_t lda, const void* W, int6
                                   const float* rowscale, void* C, int64_t ldc, int64_t M, int64_t K,
                                   int64_t N, int relu, int dtype, int flags, void* workspace, int64_t workspace_bytes,
                                   const float* a_scales, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     const bool f16 = (flags & NPI_GEMM_SPLIT_F16X2) != 0;
     NPI_REQUIRE(!f16 || (a_scales != nullptr && dtype == NPI_F32 && !(flags & (NPI_GEMM_EXACT_F32 | NPI_GEMM_A_ZERO_PADDED))),
                 "npi_linear_fwd_ex: NPI_GEMM_SPLIT_F16X2 needs a_scales (npi_row_scales), f32 storage, and excludes "
                 "NPI_GEMM_EXACT_F32 / NPI_GEMM_A_ZERO_PADDED");
-    NPI_REQUIRE(M >= 0 && K > 0 && N > 0, "npi_linear_fwd: bad size");
-    NPI_REQUIRE(M < 0x7fffffff && K < 0x7fffffff && N < 0x7fffffff, "npi_linear_fwd: size > int32");
-    NPI_REQUIRE(dtype == NPI_F32 || dtype == NPI_BF16, "npi_linear_fwd: bad dtype");
-    if (M == 0) return NPI_OK;
-    NPI_REQUIRE(A && W && C, "npi_linear_fwd: null pointer");
-    NPI_REQUIRE(lda >= K && ldw >= N && ldc >= N, "npi_linear_fwd: leading dimension too small");
     // A stored with zero pad columns up to a multiple of 128 (a 178-wide aggregate kept 256 wide): the bf16 matrix-core
     // kernel runs on the padded width with the weight planes zero-extended instead of the guarded kernel on 178
     const bool padded = (flags & NPI_GEMM_A_ZERO_PADDED) != 0 && dtype == NPI_F32 && K % 128 != 0;
     const int64_t Kp = padded ? align_up(K, 128) : K;
-    NPI_REQUIRE(lda >= Kp, "npi_linear_fwd: NPI_GEMM_A_ZERO_PADDED needs lda >= K rounded up to 128");
-    if (!scratch_ok(workspace, workspace_bytes, Kp, N)) {
-        set_error("npi_linear_fwd_ex: workspace too small or not 16-byte aligned");
-        return NPI_ERR_WORKSPACE;
-    }
+    const int rc = check_linear({.who = "npi_linear_fwd_ex", .M = M, .K = K, .N = N, .dtype = dtype, .pointers = A && W && C,
+                                 .leading_dims = lda >= Kp && ldw >= N && ldc >= N, .aligned = true, .ws = workspace,
+                                 .ws_bytes = workspace_bytes, .ws_K = Kp});
+    if (rc != NPI_OK) return rc == LINEAR_EMPTY ? NPI_OK : rc;
+    const bool prepared = (flags & NPI_GEMM_WORKSPACE_PREPARED) != 0;
+    NPI_REQUIRE(!prepared || !padded, "npi_linear_fwd_ex: NPI_GEMM_WORKSPACE_PREPARED excludes NPI_GEMM_A_ZERO_PADDED");
     const int es = dtype == NPI_BF16 ? 2 : 4;
     GemmArgs a{fp(A), lda, fp(W), ldw, (float*)C, ldc, (int)M, (int)N, (int)Kp, (int)align_up(Kp, BK), 0, 0, 0,
                Epilogue{fp(bias), rowscale, relu, nullptr}};
-    const bool prepared = (flags & NPI_GEMM_WORKSPACE_PREPARED) != 0;
-    NPI_REQUIRE(!prepared || (workspace != nullptr && !padded), "npi_linear_fwd_ex: NPI_GEMM_WORKSPACE_PREPARED needs the workspace "
-                "npi_linear_prepare filled and excludes NPI_GEMM_A_ZERO_PADDED");
-    const int rc = launch_gemm<0, 0>(vec4_ok(A, lda, Kp, es) && vec4_ok(W, ldw, N, es), a, 1, stream, dtype, dtype,
-                                     gemm_mode_of(flags), workspace, padded ? (int)K : 0, prepared, NPI_GEMM_RESERVED_CUS_OF(flags),
-                                     f16 ? a_scales : nullptr);
-    return rc != NPI_OK ? rc : check_launch("npi_linear_fwd");
+    const int status = launch_gemm<0, 0>(a, {.v4 = vec4_ok(A, lda, Kp, es) && vec4_ok(W, ldw, N, es), .dtype_in = dtype, .dtype_out = dtype,
+                                             .exact = exact_of(flags), .planes = workspace, .k_valid = padded ? (int)K : 0,
+                                             .prepared = prepared, .reserve_cus = NPI_GEMM_RESERVED_CUS_OF(flags),
+                                             .row_scales = f16 ? a_scales : nullptr, .stream = (hipStream_t)stream_});
+    return status != NPI_OK ? status : check_launch("npi_linear_fwd_ex");
 }
 
 // dA[M,K] = rowscale * (dC[M,N] @ W[K,N]^T): GEMM with "K" = N (contracted), output width K
@@ -2261,33 +2295,26 @@ extern "C" int npi_linear_bwd_data_ex(const void* dC, int64_t lddc, const void* 
                                        const float* rowscale, void* dA, int64_t ldda, int64_t M, int64_t K,
                                        int64_t N, int dtype, int flags, void* workspace, int64_t workspace_bytes,
                                        const float* dc_scales, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     const bool f16 = (flags & NPI_GEMM_SPLIT_F16X2) != 0;
     NPI_REQUIRE(!f16 || (dc_scales != nullptr && dtype == NPI_F32 && !(flags & NPI_GEMM_EXACT_F32)),
                 "npi_linear_bwd_data_ex: NPI_GEMM_SPLIT_F16X2 needs dc_scales (npi_row_scales of dC), f32 storage, and excludes "
                 "NPI_GEMM_EXACT_F32");
-    NPI_REQUIRE(M >= 0 && K > 0 && N > 0, "npi_linear_bwd_data: bad size");
-    NPI_REQUIRE(M < 0x7fffffff && K < 0x7fffffff && N < 0x7fffffff, "npi_linear_bwd_data: size > int32");
-    NPI_REQUIRE(dtype == NPI_F32 || dtype == NPI_BF16, "npi_linear_bwd_data: bad dtype");
-    if (M == 0) return NPI_OK;
-    NPI_REQUIRE(dC && W && dA, "npi_linear_bwd_data: null pointer");
-    NPI_REQUIRE(lddc >= N && ldw >= N && ldda >= K, "npi_linear_bwd_data: leading dimension too small");
-    if (!scratch_ok(workspace, workspace_bytes, K, N)) {
-        set_error("npi_linear_bwd_data_ex: workspace too small or not 16-byte aligned");
-        return NPI_ERR_WORKSPACE;
-    }
+    const int rc = check_linear({.who = "npi_linear_bwd_data_ex", .M = M, .K = K, .N = N, .dtype = dtype, .pointers = dC && W && dA,
+                                 .leading_dims = lddc >= N && ldw >= N && ldda >= K, .aligned = true, .ws = workspace,
+                                 .ws_bytes = workspace_bytes, .ws_K = K});
+    if (rc != NPI_OK) return rc == LINEAR_EMPTY ? NPI_OK : rc;
     const int es = dtype == NPI_BF16 ? 2 : 4;
     // B(k = n_contract, n = k_out) = W[k_out * ldw + n_contract]  -> BMODE 1
     GemmArgs a{fp(dC), lddc, fp(W), ldw, (float*)dA, ldda, (int)M, (int)K, (int)N, (int)align_up(N, BK), 0, 0, 0,
                Epilogue{nullptr, rowscale, 0, nullptr}};
-    const bool prepared = (flags & NPI_GEMM_WORKSPACE_PREPARED) != 0;
-    NPI_REQUIRE(!prepared || workspace != nullptr, "npi_linear_bwd_data_ex: NPI_GEMM_WORKSPACE_PREPARED needs the workspace "
-                "npi_linear_prepare filled");
-    const int rc = launch_gemm<0, 1>(vec4_ok(dC, lddc, N, es) && vec4_ok(W, ldw, N, es), a, 1, stream, dtype, dtype,
-                                     gemm_mode_of(flags), workspace, 0, prepared, NPI_GEMM_RESERVED_CUS_OF(flags),
-                                     f16 ? dc_scales : nullptr);
-    return rc != NPI_OK ? rc : check_launch("npi_linear_bwd_data");
+    const int status = launch_gemm<0, 1>(a, {.v4 = vec4_ok(dC, lddc, N, es) && vec4_ok(W, ldw, N, es), .dtype_in = dtype, .dtype_out = dtype,
+                                             .exact = exact_of(flags), .planes = workspace,
+                                             .prepared = (flags & NPI_GEMM_WORKSPACE_PREPARED) != 0,
+                                             .reserve_cus = NPI_GEMM_RESERVED_CUS_OF(flags), .row_scales = f16 ? dc_scales : nullptr,
+                                             .stream = (hipStream_t)stream_});
+    return status != NPI_OK ? status : check_launch("npi_linear_bwd_data_ex");
 }
+
 // C = A W and, from the accumulators on their way out, sc0[m] = <C[m, :], att[:N]>, sc1[m] = <C[m, :], att[N:]>: GATConv's
 // h = x W with the two attention scores of every node in the GEMM's store epilogue (one head) instead of a pass over h
 extern "C" int npi_linear_fwd_scores_supported(int64_t M, int64_t K, int64_t N) {
@@ -2300,22 +2327,19 @@ extern "C" int npi_linear_fwd_scores_supported(int64_t M, int64_t K, int64_t N) 
 extern "C" int npi_linear_fwd_scores(const float* A, int64_t lda, const float* W, int64_t ldw, const float* att, float* C,
                                          int64_t ldc, float* sc0, float* sc1, int64_t M, int64_t K, int64_t N, void* workspace,
                                          int64_t workspace_bytes, const float* a_scales, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     NPI_REQUIRE(npi_linear_fwd_scores_supported(M, K, N), "npi_linear_fwd_scores: shape outside the split kernel's one-column-"
                 "tile coverage (M >= 128, K >= 64, K % 32 == 0, N = 128 or 256)");
-    NPI_REQUIRE(A && W && att && C && sc0 && sc1, "npi_linear_fwd_scores: null pointer");
-    NPI_REQUIRE(lda >= K && ldw >= N && ldc >= N, "npi_linear_fwd_scores: leading dimension too small");
-    NPI_REQUIRE(vec4_ok(A, lda, K, 4) && vec4_ok(W, ldw, N, 4) && ((uintptr_t)C % 16 == 0) && (ldc % 4 == 0),
-                "npi_linear_fwd_scores: operands must be 16-byte aligned with leading dimensions % 4 == 0");
-    if (!scratch_ok(workspace, workspace_bytes, K, N)) {
-        set_error("npi_linear_fwd_scores: workspace too small or not 16-byte aligned");
-        return NPI_ERR_WORKSPACE;
-    }
+    const int rc = check_linear({.who = "npi_linear_fwd_scores", .M = M, .K = K, .N = N, .dtype = NPI_F32,
+                                 .pointers = A && W && att && C && sc0 && sc1, .leading_dims = lda >= K && ldw >= N && ldc >= N,
+                                 .aligned = vec4_ok(A, lda, K, 4) && vec4_ok(W, ldw, N, 4) && ((uintptr_t)C % 16 == 0) && (ldc % 4 == 0),
+                                 .ws = workspace, .ws_bytes = workspace_bytes, .ws_K = K});
+    if (rc != NPI_OK) return rc == LINEAR_EMPTY ? NPI_OK : rc;
     GemmArgs a{A, lda, W, ldw, C, ldc, (int)M, (int)N, (int)K, (int)align_up(K, BK), 0, 0, 0,
                Epilogue{nullptr, nullptr, 0, nullptr, nullptr, nullptr, att, att + N, sc0, sc1}};
-    const int rc = launch_gemm<0, 0>(true, a, 1, stream, NPI_F32, NPI_F32, 1, workspace, 0, false, 0, a_scales);
-    return rc != NPI_OK ? rc : check_launch("npi_linear_fwd_scores");
+    const int status = launch_gemm<0, 0>(a, {.v4 = true, .planes = workspace, .row_scales = a_scales, .stream = (hipStream_t)stream_});
+    return status != NPI_OK ? status : check_launch("npi_linear_fwd_scores");
 }
+
 // dA = dC W^T + row0 (x) col0 + row1 (x) col1, the rank-2 term added in the split kernel's store epilogue (GATConv backward:
 // the attention terms g_dst (x) W att_dst + g_src (x) W att_src of dX, without a read-modify-write pass over d hfeat)
 extern "C" int npi_linear_bwd_data_rank2_supported(int64_t M, int64_t K, int64_t N) {
@@ -2328,21 +2352,18 @@ extern "C" int npi_linear_bwd_data_rank2(const float* dC, int64_t lddc, const fl
                                              const float* row1, const float* col0, const float* col1, float* dA, int64_t ldda,
                                              int64_t M, int64_t K, int64_t N, void* workspace, int64_t workspace_bytes,
                                              const float* dc_scales, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     NPI_REQUIRE(npi_linear_bwd_data_rank2_supported(M, K, N), "npi_linear_bwd_data_rank2: shape outside the split kernel's "
                 "full coverage (M >= 128, K % 128 == 0, N % 32 == 0)");
-    NPI_REQUIRE(dC && W && dA && row0 && row1 && col0 && col1, "npi_linear_bwd_data_rank2: null pointer");
-    NPI_REQUIRE(lddc >= N && ldw >= N && ldda >= K, "npi_linear_bwd_data_rank2: leading dimension too small");
-    NPI_REQUIRE(vec4_ok(dC, lddc, N, 4) && vec4_ok(W, ldw, N, 4) && ((uintptr_t)dA % 16 == 0) && (ldda % 4 == 0),
-                "npi_linear_bwd_data_rank2: operands must be 16-byte aligned with leading dimensions % 4 == 0");
-    if (!scratch_ok(workspace, workspace_bytes, K, N)) {
-        set_error("npi_linear_bwd_data_rank2: workspace too small or not 16-byte aligned");
-        return NPI_ERR_WORKSPACE;
-    }
+    const int rc = check_linear({.who = "npi_linear_bwd_data_rank2", .M = M, .K = K, .N = N, .dtype = NPI_F32,
+                                 .pointers = dC && W && dA && row0 && row1 && col0 && col1,
+                                 .leading_dims = lddc >= N && ldw >= N && ldda >= K,
+                                 .aligned = vec4_ok(dC, lddc, N, 4) && vec4_ok(W, ldw, N, 4) && ((uintptr_t)dA % 16 == 0) && (ldda % 4 == 0),
+                                 .ws = workspace, .ws_bytes = workspace_bytes, .ws_K = K});
+    if (rc != NPI_OK) return rc == LINEAR_EMPTY ? NPI_OK : rc;
     GemmArgs a{dC, lddc, W, ldw, dA, ldda, (int)M, (int)K, (int)N, (int)align_up(N, BK), 0, 0, 0,
                Epilogue{nullptr, nullptr, 0, nullptr, row0, row1, col0, col1}};
-    const int rc = launch_gemm<0, 1>(true, a, 1, stream, NPI_F32, NPI_F32, 1, workspace, 0, false, 0, dc_scales);
-    return rc != NPI_OK ? rc : check_launch("npi_linear_bwd_data_rank2");
+    const int status = launch_gemm<0, 1>(a, {.v4 = true, .planes = workspace, .row_scales = dc_scales, .stream = (hipStream_t)stream_});
+    return status != NPI_OK ? status : check_launch("npi_linear_bwd_data_rank2");
 }
 
 extern "C" int64_t npi_colsum_workspace_elems(int64_t M, int64_t N) {
@@ -2364,47 +2385,48 @@ extern "C" int npi_colsum(const float* X, int64_t ldx, int64_t M, int64_t N, flo
         return NPI_ERR_WORKSPACE;
     }
     dim3 cg((unsigned)ceil_div(N, 256), (unsigned)nchunks);
-    if (vec4_ok(X, ldx, N)) colsum_partial_kernel<true><<<cg, 256, 0, stream>>>(X, ldx, (int)M, (int)N, rows, workspace);
+    if (vec4_ok(X, ldx, N, 4)) colsum_partial_kernel<true><<<cg, 256, 0, stream>>>(X, ldx, (int)M, (int)N, rows, workspace);
     else                    colsum_partial_kernel<false><<<cg, 256, 0, stream>>>(X, ldx, (int)M, (int)N, rows, workspace);
     slab_reduce_kernel<float><<<(unsigned)ceil_div(N, 256), 256, 0, stream>>>(workspace, N, nchunks, 1, (int)N, N, out, N);
     return check_launch("npi_colsum");
 }
 
 // dW: the contraction runs over the nodes.  Node count is arbitrary, so the part that is a
-// multiple of BK goes through `splits` slabs (fast path) and the < BK remainder through one
-// extra slab (guarded).
-static void bwd_weight_plan(int64_t M, int64_t K, int64_t N, bool shared, int& splits, int& kchunk, int64_t& m_main) {
+// multiple of BK goes through `splits` slabs (fast path) and the < BK remainder through the
+// finishing launch (or, without a main part, one guarded slab).
+struct DwSlabPlan { int splits, kchunk; int64_t m_main; };
+static DwSlabPlan bwd_weight_plan(int64_t M, int64_t K, int64_t N, bool shared) {
     const int64_t tiles = ceil_div(K, 128) * ceil_div(N, 128);
-    m_main = (M / BK) * BK;
-    splits = pick_splits(m_main > 0 ? m_main : 1, tiles, shared);
-    kchunk = (int)(ceil_div(ceil_div(m_main > 0 ? m_main : 1, splits), BK) * BK);
+    const int64_t m_main = (M / BK) * BK;
+    const int splits = pick_splits(m_main > 0 ? m_main : 1, tiles, shared);
+    return {splits, (int)(ceil_div(ceil_div(m_main > 0 ? m_main : 1, splits), BK) * BK), m_main};
 }
 
 // Plan of the split-bf16 dW kernel (gemm_dw_split_kernel): one workgroup per CU when it has the GPU to itself, about
 // three per four CUs when it shares them with the backward aggregation; `per` nodes per slab (multiple of 16).
+struct DwSplitPlan { int nslab; int64_t per; int tiles_m, tiles_n; bool wide; };
 static bool dw_split_shape_ok(int64_t M, int64_t K, int64_t N) { return K % 128 == 0 && N % 128 == 0 && M >= 4096; }
-static void dw_split_plan(int64_t m_main, int64_t K, int64_t N, bool shared, int& nslab, int64_t& per, int& tiles_m, int& tiles_n,
-                          bool& wide) {
-    wide = (N % 256 == 0);
-    tiles_m = (int)(K / 128);
-    tiles_n = (int)(wide ? N / 256 : N / 128);
+static DwSplitPlan dw_split_plan(int64_t m_main, int64_t K, int64_t N, bool shared) {
+    DwSplitPlan p;
+    p.wide = (N % 256 == 0);
+    p.tiles_m = (int)(K / 128);
+    p.tiles_n = (int)(p.wide ? N / 256 : N / 128);
     // shared regime: the 512-thread workgroup holds 2 x 208 VGPRs per SIMD and leaves the aggregation one wave slot there, so
     // it is kept to about 3 of 8 CUs (step at C4 by workgroup count: 64: 7.86, 96: 7.11, 128: 7.15, 192: 7.25 ms)
     const int64_t wgs = shared ? dw_workgroups(true) / 2 : 256;
-    int64_t ns = wgs / ((int64_t)tiles_m * tiles_n);
+    int64_t ns = wgs / ((int64_t)p.tiles_m * p.tiles_n);
     if (ns < 1) ns = 1;
     const int64_t maxs = ceil_div(m_main, (int64_t)SK * 16);                 // at least 16 k-steps per slab
     if (ns > maxs) ns = maxs;
     if (ns > 256) ns = 256;
-    nslab = (int)ns;
-    per = ceil_div(ceil_div(m_main, ns), (int64_t)SK) * SK;
+    p.nslab = (int)ns;
+    p.per = ceil_div(ceil_div(m_main, ns), (int64_t)SK) * SK;
+    return p;
 }
 
 extern "C" int64_t npi_linear_bwd_weight_workspace_elems(int64_t M, int64_t K, int64_t N) {
     if (M < 0 || K <= 0 || N <= 0) return -1;
-    int splits, kchunk;
-    int64_t m_main;
-    bwd_weight_plan(M, K, N, /*shared=*/false, splits, kchunk, m_main);          // the regime with more slabs: enough for both
+    const int splits = bwd_weight_plan(M, K, N, /*shared=*/false).splits;         // the regime with more slabs: enough for both
     int64_t slabs = splits + 1, dbs = splits + 1;
     if (dw_split_shape_ok(M, K, N)) {                                             // the split-bf16 plan: <= 256 slabs, 2 db rows each
         if (slabs < 257) slabs = 257;
@@ -2413,7 +2435,6 @@ extern "C" int64_t npi_linear_bwd_weight_workspace_elems(int64_t M, int64_t K, i
     return slabs * K * N + dbs * N + 64;                                          // dW slabs, then db slabs
 }
 
-// dW[K,N] = A[M,K]^T @ dC[M,N] (contract over M), db[N] = colsum(dC); A, dC, dW, db stored as `dtype`
 extern "C" int64_t npi_col_scales_workspace_elems(int64_t M, int64_t K) {
     if (M < 0 || K <= 0) return -1;
     const int64_t a = ceil_div(M > 0 ? M : 1, (int64_t)colsum_rows(M)) * K;
@@ -2444,6 +2465,39 @@ extern "C" int npi_col_scales(const float* A, int64_t lda, int64_t M, int64_t K,
     return check_launch("npi_col_scales");
 }
 
+// The operands of one npi_linear_bwd_weight_ex call, as the entry point got them
+struct DwCall {
+    const void* A; int64_t lda; const void* dC; int64_t lddc; void* dW; int64_t lddw; void* db;
+    int64_t M, K, N;
+    float* workspace; hipStream_t stream;
+};
+// The finishing launch (dw_finish_kernel): the `nslab` slabs in slab order, the trailing nodes [m_done, M) and db (from `n_db`
+// slab rows) in one launch, rounded once to the storage type T
+template <typename T>
+static void launch_dw_finish(const DwCall& c, int64_t slab_stride, int nslab, const float* db_slabs, int n_db, int64_t m_done) {
+    dw_finish_kernel<T><<<dw_finish_grid(c.K, c.N, c.db != nullptr), 256, 0, c.stream>>>(
+        c.workspace, slab_stride, nslab, (int)c.K, (int)c.N, (T*)c.dW, c.lddw, db_slabs, n_db, (T*)c.db,
+        reinterpret_cast<const T*>(advance(c.A, m_done * c.lda, sizeof(T))), c.lda,
+        reinterpret_cast<const T*>(advance(c.dC, m_done * c.lddc, sizeof(T))), c.lddc, (int)(c.M - m_done));
+}
+// dW on the bf16 matrix cores (gemm_dw_split_kernel), storage T.  float: both operands split on the fly into bf16 x 3 or -- column
+// scales given -- fp16 x 2 pieces; bf16: the same kernel without the split (one plane, one MFMA per product tile).  Slabs and
+// the finish in f32.  `Ks`: the width A is read on (K rounded up to 128 for a zero-padded A: the pad rows of the slabs are zero
+// and never read).
+template <typename T>
+static int dw_split(const DwCall& c, int64_t Ks, bool shared, const float* a_cs, const float* dc_cs) {
+    const int64_t m16 = (c.M / SK) * SK;
+    const DwSplitPlan p = dw_split_plan(m16, Ks, c.N, shared);
+    float* db_slabs = c.workspace + (int64_t)(p.nslab + 1) * Ks * c.N;
+    DwArgs d{fp(c.A), c.lda, fp(c.dC), c.lddc, c.workspace, c.db ? db_slabs : nullptr, (int)Ks, (int)c.N, m16, p.per, p.tiles_m, p.tiles_n,
+             p.nslab, a_cs, dc_cs};
+    const unsigned grid = (unsigned)(ceil_div(p.nslab, 8) * 8 * p.tiles_m * p.tiles_n);      // slots of 8 slabs (one per XCD) x tiles
+    dw_kernel_of(p.wide, sizeof(T) == 2, a_cs != nullptr)<<<grid, WS_THREADS, 0, c.stream>>>(d);
+    launch_dw_finish<T>(c, Ks * c.N, p.nslab, db_slabs, 2 * p.nslab, m16);                   // (the < 16 trailing nodes)
+    return check_launch("npi_linear_bwd_weight");
+}
+
+// dW[K,N] = A[M,K]^T @ dC[M,N] (contract over M), db[N] = colsum(dC); A, dC, dW, db stored as `dtype`
 extern "C" int npi_linear_bwd_weight_ex(const void* A, int64_t lda, const void* dC, int64_t lddc,
                                         void* dW, int64_t lddw, void* db, int64_t M, int64_t K, int64_t N,
                                         float* workspace, int64_t workspace_elems, int dtype, int flags, int shared,
@@ -2464,8 +2518,8 @@ extern "C" int npi_linear_bwd_weight_ex(const void* A, int64_t lda, const void* 
         return NPI_ERR_WORKSPACE;
     }
     const int es = dtype == NPI_BF16 ? 2 : 4;
-    // A with zero pad columns up to a multiple of 128 (see npi_linear_fwd_ex): the split kernel runs on the padded width --
-    // the pad rows of its slabs are zero and never read -- instead of the guarded kernel on K
+    // A with zero pad columns up to a multiple of 128 (see npi_linear_fwd_ex): the split kernel runs on the padded width
+    // instead of the guarded kernel on K
     const bool padded = (flags & NPI_GEMM_A_ZERO_PADDED) != 0 && dtype == NPI_F32 && K % 128 != 0;
     const int64_t Kp = padded ? align_up(K, 128) : K;
     NPI_REQUIRE(lda >= Kp, "npi_linear_bwd_weight: NPI_GEMM_A_ZERO_PADDED needs lda >= K rounded up to 128");
@@ -2474,86 +2528,32 @@ extern "C" int npi_linear_bwd_weight_ex(const void* A, int64_t lda, const void* 
         return NPI_ERR_WORKSPACE;
     }
     const bool v4 = vec4_ok(A, lda, Kp, es) && vec4_ok(dC, lddc, N, es);
-    const unsigned gw = (unsigned)ceil_div(K * N, 256), gb = (unsigned)ceil_div(N, 256);
-    const unsigned gwb = dw_finish_grid(K, N, db != nullptr);
-    // ---- f32 storage on the bf16 matrix cores: both operands split on the fly (gemm_dw_split_kernel) ----
-    if (dtype == NPI_F32 && gemm_mode_of(flags) != 0 && v4 && dw_split_shape_ok(M, Kp, N)) {
-        const int64_t m16 = (M / SK) * SK;
-        int nslab, tm, tn;
-        int64_t per;
-        bool wide;
-        dw_split_plan(m16, Kp, N, shared != 0, nslab, per, tm, tn, wide);
-        float* db_slabs = workspace + (int64_t)(nslab + 1) * Kp * N;
-        DwArgs d{fp(A), lda, fp(dC), lddc, workspace, db ? db_slabs : nullptr, (int)Kp, (int)N, m16, per, tm, tn, nslab,
-                 f16 ? a_col_scales : nullptr, f16 ? dc_col_scales : nullptr};
-        const unsigned grid = (unsigned)(ceil_div(nslab, 8) * 8 * tm * tn);     // slots of 8 slabs (one per XCD) x tiles
-        if (f16) {
-            if (wide) gemm_dw_split_kernel<4, false, true><<<grid, WS_THREADS, 0, stream>>>(d);
-            else      gemm_dw_split_kernel<2, false, true><<<grid, WS_THREADS, 0, stream>>>(d);
-        } else if (wide) gemm_dw_split_kernel<4><<<grid, WS_THREADS, 0, stream>>>(d);
-        else             gemm_dw_split_kernel<2><<<grid, WS_THREADS, 0, stream>>>(d);
-        // slabs in slab order, the < 16 trailing nodes and db in one launch
-        dw_finish_kernel<float><<<gwb, 256, 0, stream>>>(workspace, Kp * N, nslab, (int)K, (int)N, (float*)dW, lddw, db_slabs, 2 * nslab,
-                                                  (float*)db, fp(advance(A, m16 * lda, es)), lda, fp(advance(dC, m16 * lddc, es)), lddc,
-                                                  (int)(M - m16));
-        return check_launch("npi_linear_bwd_weight");
-    }
-    // ---- bf16 storage: the same kernel without the split (one plane, one MFMA per product tile); slabs and the finish in f32 ----
-    if (dtype == NPI_BF16 && gemm_mode_of(flags) != 0 && v4 && dw_split_shape_ok(M, K, N)) {
-        const int64_t m16 = (M / SK) * SK;
-        int nslab, tm, tn;
-        int64_t per;
-        bool wide;
-        dw_split_plan(m16, K, N, shared != 0, nslab, per, tm, tn, wide);
-        float* db_slabs = workspace + (int64_t)(nslab + 1) * K * N;
-        DwArgs d{fp(A), lda, fp(dC), lddc, workspace, db ? db_slabs : nullptr, (int)K, (int)N, m16, per, tm, tn, nslab, nullptr, nullptr};
-        const unsigned grid = (unsigned)(ceil_div(nslab, 8) * 8 * tm * tn);
-        if (wide) gemm_dw_split_kernel<4, true><<<grid, WS_THREADS, 0, stream>>>(d);
-        else      gemm_dw_split_kernel<2, true><<<grid, WS_THREADS, 0, stream>>>(d);
-        dw_finish_kernel<bf16_t><<<gwb, 256, 0, stream>>>(workspace, K * N, nslab, (int)K, (int)N, (bf16_t*)dW, lddw, db_slabs, 2 * nslab,
-                                                         (bf16_t*)db, reinterpret_cast<const bf16_t*>(advance(A, m16 * lda, es)), lda,
-                                                         reinterpret_cast<const bf16_t*>(advance(dC, m16 * lddc, es)), lddc, (int)(M - m16));
-        return check_launch("npi_linear_bwd_weight");
-    }
-    int splits, kchunk;
-    int64_t m_main;
-    bwd_weight_plan(M, K, N, shared != 0, splits, kchunk, m_main);
-    const bool has_rem = M > m_main || m_main == 0;
-    float* db_slabs = workspace + (int64_t)(splits + 1) * K * N;
-    // output rows = K (features of A), cols = N; A(m = feature, k = node) = A[node*lda + feature]
-    // main part: nodes [0, m_main) in `splits` f32 slabs
-    if (m_main > 0) {
-        GemmArgs a{fp(A), lda, fp(dC), lddc, workspace, N, (int)K, (int)N, (int)m_main, kchunk, 0, 0, K * N,
+    const DwCall c{A, lda, dC, lddc, dW, lddw, db, M, K, N, workspace, stream};
+    const bool matrix_cores = !exact_of(flags) && v4;
+    if (dtype == NPI_F32 && matrix_cores && dw_split_shape_ok(M, Kp, N))
+        return dw_split<float>(c, Kp, shared != 0, f16 ? a_col_scales : nullptr, f16 ? dc_col_scales : nullptr);
+    if (dtype == NPI_BF16 && matrix_cores && dw_split_shape_ok(M, K, N)) return dw_split<bf16_t>(c, K, shared != 0, nullptr, nullptr);
+    // ---- the exact-f32 kernels: output rows = K (features of A), cols = N; A(m = feature, k = node) = A[node*lda + feature] ----
+    const DwSlabPlan p = bwd_weight_plan(M, K, N, shared != 0);
+    float* db_slabs = workspace + (int64_t)(p.splits + 1) * K * N;
+    const int nslab = p.m_main > 0 ? p.splits : 0;
+    // launch_gemm's status is dropped: it refuses only a persistent path without a workspace or an epilogue the path cannot
+    // serve -- AMODE 1 takes no persistent path, and these calls carry neither a rank-2 nor a row-dot epilogue
+    if (p.m_main > 0) {                                      // main part: nodes [0, m_main) in `splits` f32 slabs
+        GemmArgs a{fp(A), lda, fp(dC), lddc, workspace, N, (int)K, (int)N, (int)p.m_main, p.kchunk, 0, 0, K * N,
                    Epilogue{nullptr, nullptr, 0, db ? db_slabs : nullptr}};
-        (void)launch_gemm<1, 0>(v4, a, splits, stream, dtype, NPI_F32);          // AMODE 1 never takes the allocating path
+        (void)launch_gemm<1, 0>(a, {.v4 = v4, .splits = p.splits, .dtype_in = dtype, .dtype_out = NPI_F32, .stream = stream});
     }
-    if (dtype == NPI_F32) {
-        // slabs in slab order, the < 32 trailing nodes and db in one launch (a node count that is a multiple of 32 used to
-        // pay a zero-filling launch here, a remainder its own guarded GEMM)
-        const int ns = m_main > 0 ? splits : 0;
-        dw_finish_kernel<float><<<gwb, 256, 0, stream>>>(workspace, K * N, ns, (int)K, (int)N, (float*)dW, lddw, db_slabs, ns, (float*)db,
-                                                  fp(advance(A, m_main * lda, es)), lda, fp(advance(dC, m_main * lddc, es)), lddc,
-                                                  (int)(M - m_main));
-        return check_launch("npi_linear_bwd_weight");
-    }
-    if (M - m_main < 32 && m_main > 0) {
-        // bf16 storage, the usual case: the < 32 trailing nodes, the slab sums, db and the rounding to bf16 in the one finishing
-        // launch (rounds 1-3: a guarded GEMM for the trailing nodes and two reductions -- 4 launches per dW against 2 for f32)
-        dw_finish_kernel<bf16_t><<<gwb, 256, 0, stream>>>(workspace, K * N, splits, (int)K, (int)N, (bf16_t*)dW, lddw, db_slabs, splits,
-                                                         (bf16_t*)db, reinterpret_cast<const bf16_t*>(advance(A, m_main * lda, es)), lda,
-                                                         reinterpret_cast<const bf16_t*>(advance(dC, m_main * lddc, es)), lddc,
-                                                         (int)(M - m_main));
-        return check_launch("npi_linear_bwd_weight");
-    }
-    // bf16 storage: remainder nodes [m_main, M) into slab `splits`, then the two reductions
-    const int nslab = (m_main > 0 ? splits : 0) + (has_rem ? 1 : 0);
-    if (has_rem) {
-        GemmArgs r{fp(advance(A, m_main * lda, es)), lda, fp(advance(dC, m_main * lddc, es)), lddc,
-                   workspace + (int64_t)(m_main > 0 ? splits : 0) * K * N, N, (int)K, (int)N, (int)(M - m_main), BK, 0, 0, K * N,
-                   Epilogue{nullptr, nullptr, 0, db ? db_slabs + (int64_t)(m_main > 0 ? splits : 0) * N : nullptr}};
-        (void)launch_gemm<1, 0>(false, r, 1, stream, dtype, NPI_F32);
-    }
-    slab_reduce_kernel<bf16_t><<<gw, 256, 0, stream>>>(workspace, K * N, nslab, (int)K, (int)N, N, (bf16_t*)dW, lddw);
-    if (db) slab_reduce_kernel<bf16_t><<<gb, 256, 0, stream>>>(db_slabs, N, nslab, 1, (int)N, N, (bf16_t*)db, N);
+    // slabs in slab order, the < 32 trailing nodes and db in one launch (a node count that is a multiple of 32 used to pay a
+    // zero-filling launch here, a remainder its own guarded GEMM).  bf16 storage, the usual case, rounds there too (rounds 1-3: a
+    // guarded GEMM for the trailing nodes and two reductions -- 4 launches per dW against 2 for f32)
+    if (dtype == NPI_F32) return launch_dw_finish<float>(c, K * N, nslab, db_slabs, nslab, p.m_main), check_launch("npi_linear_bwd_weight");
+    if (p.m_main > 0) return launch_dw_finish<bf16_t>(c, K * N, nslab, db_slabs, nslab, p.m_main), check_launch("npi_linear_bwd_weight");
+    // bf16 storage, fewer than 32 nodes: all of them into slab 0 on the guarded kernel, then the two reductions (which round)
+    GemmArgs r{fp(A), lda, fp(dC), lddc, workspace, N, (int)K, (int)N, (int)M, BK, 0, 0, K * N,
+               Epilogue{nullptr, nullptr, 0, db ? db_slabs : nullptr}};
+    (void)launch_gemm<1, 0>(r, {.v4 = false, .dtype_in = dtype, .dtype_out = NPI_F32, .stream = stream});
+    slab_reduce_kernel<bf16_t><<<(unsigned)ceil_div(K * N, 256), 256, 0, stream>>>(workspace, K * N, 1, (int)K, (int)N, N, (bf16_t*)dW, lddw);
+    if (db) slab_reduce_kernel<bf16_t><<<(unsigned)ceil_div(N, 256), 256, 0, stream>>>(db_slabs, N, 1, 1, (int)N, N, (bf16_t*)db, N);
     return check_launch("npi_linear_bwd_weight");
 }

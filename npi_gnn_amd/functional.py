@@ -310,6 +310,30 @@ def prepare_weight(weight: torch.Tensor, backward: bool = True, f16: bool = Fals
     return Planes(ws[:one], f16), (Planes(ws[one:], f16) if backward else None)
 
 
+def _linear_out(out: Optional[torch.Tensor], rows: int, cols: int, like: torch.Tensor, what: str) -> torch.Tensor:
+    """the ``out=`` of ``linear_fwd`` / ``linear_bwd_data``: a new ``[rows, cols]`` tensor, or the caller's once it is that"""
+    if out is None:
+        return torch.empty((rows, cols), dtype=like.dtype, device=like.device)
+    if out.shape != (rows, cols) or out.dtype != like.dtype or out.stride(1) != 1 or out.device != like.device:
+        raise ValueError(f"{what}: out must be [{rows}, {cols}] {like.dtype} with unit column stride on the operands' device")
+    return out
+
+
+def _linear_call(flags: Optional[int], reserve_cus: int, scales: Optional[torch.Tensor], ws, *, f16_ok: bool, K: int, N: int, dev,
+                 what: str):
+    """what ``linear_fwd`` / ``linear_bwd_data`` make of their arithmetic arguments: ``(flags, scales or None, workspace tensor)``.
+    ``f16_ok``: storage and shape serve the fp16 x 2 kernel (row scales given for anything else are dropped); ``ws``: the prepared
+    copy to read (a ``Planes`` of the matching kind), or None for a scratch workspace of ``[K, N]``."""
+    fl = int(flags or 0) | NPI_GEMM_RESERVE_CUS(reserve_cus)
+    if scales is not None and (not f16_ok or fl & NPI_GEMM_EXACT_F32):
+        scales = None                                           # (storage / flags the fp16 x 2 kernel does not serve)
+    if scales is not None:
+        fl |= NPI_GEMM_SPLIT_F16X2
+    if ws is not None:
+        return fl | NPI_GEMM_WORKSPACE_PREPARED, scales, _planes_for(ws, scales is not None, what)
+    return fl, scales, _gemm_workspace(K, N, dev)
+
+
 def linear_fwd(a: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
                rowscale: Optional[torch.Tensor] = None, relu: bool = False, flags: Optional[int] = None,
                out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None, reserve_cus: int = 0,
@@ -328,25 +352,14 @@ def linear_fwd(a: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
         bias = _fc(bias, "bias", a)
     M, Ka = a.shape
     K, N = weight.shape
-    fl = int(flags or 0) | NPI_GEMM_RESERVE_CUS(reserve_cus)
-    if Ka != K:
-        if Ka != _pad128(K) or a.dtype != torch.float32:
-            raise ValueError(f"a has {Ka} columns, weight {K} rows (a zero-padded a must be f32 and {_pad128(K)} wide)")
-        fl |= NPI_GEMM_A_ZERO_PADDED
-    if out is None:
-        out = torch.empty((M, N), dtype=a.dtype, device=dev)
-    elif out.shape != (M, N) or out.dtype != a.dtype or out.stride(1) != 1 or out.device != a.device:
-        raise ValueError(f"linear_fwd: out must be [{M}, {N}] {a.dtype} with unit column stride on the operands' device")
+    if Ka != K and (Ka != _pad128(K) or a.dtype != torch.float32):
+        raise ValueError(f"a has {Ka} columns, weight {K} rows (a zero-padded a must be f32 and {_pad128(K)} wide)")
+    out = _linear_out(out, M, N, a, "linear_fwd")
     _check_scales(a_scales, M, "linear_fwd")
-    if a_scales is not None and (a.dtype != torch.float32 or Ka != K or fl & NPI_GEMM_EXACT_F32):
-        a_scales = None                                         # (storage / flags the fp16 x 2 kernel does not serve)
-    if a_scales is not None:
-        fl |= NPI_GEMM_SPLIT_F16X2
-    if ws is not None and Ka == K:
-        ws = _planes_for(ws, a_scales is not None, "linear_fwd")
-        fl |= NPI_GEMM_WORKSPACE_PREPARED
-    else:
-        ws = _gemm_workspace(Ka, N, dev)
+    padded = Ka != K                                            # neither a prepared copy nor fp16 x 2 serves a zero-padded a
+    fl, a_scales, ws = _linear_call(int(flags or 0) | (NPI_GEMM_A_ZERO_PADDED if padded else 0), reserve_cus, a_scales,
+                                    None if padded else ws, f16_ok=a.dtype == torch.float32 and not padded, K=Ka, N=N, dev=dev,
+                                    what="linear_fwd")
     with _gemm_events("fwd", 2.0 * M * K * N, dev):
         check(load().npi_linear_fwd_ex(ptr(a), a.stride(0), ptr(weight), weight.stride(0), ptr(bias), ptr(rowscale),
                                         ptr(out), out.stride(0), M, K, N, 1 if relu else 0, _code(a),
@@ -366,23 +379,10 @@ def linear_bwd_data(dc: torch.Tensor, weight: torch.Tensor,
     weight = _fc(weight, "weight", dc)
     M, N = dc.shape
     K = weight.size(0)
-    if out is None:
-        da = torch.empty((M, K), dtype=dc.dtype, device=dev)
-    else:
-        if out.shape != (M, K) or out.dtype != dc.dtype or out.stride(1) != 1 or out.device != dc.device:
-            raise ValueError(f"linear_bwd_data: out must be [{M}, {K}] {dc.dtype} with unit column stride on the operands' device")
-        da = out
-    fl = int(flags or 0) | NPI_GEMM_RESERVE_CUS(reserve_cus)
+    da = _linear_out(out, M, K, dc, "linear_bwd_data")
     _check_scales(dc_scales, M, "linear_bwd_data")
-    if dc_scales is not None and (dc.dtype != torch.float32 or fl & NPI_GEMM_EXACT_F32):
-        dc_scales = None
-    if dc_scales is not None:
-        fl |= NPI_GEMM_SPLIT_F16X2
-    if ws is not None:
-        ws = _planes_for(ws, dc_scales is not None, "linear_bwd_data")
-        fl |= NPI_GEMM_WORKSPACE_PREPARED
-    else:
-        ws = _gemm_workspace(K, N, dev)
+    fl, dc_scales, ws = _linear_call(flags, reserve_cus, dc_scales, ws, f16_ok=dc.dtype == torch.float32, K=K, N=N, dev=dev,
+                                     what="linear_bwd_data")
     with _gemm_events("bwd_data", 2.0 * M * K * N, dev):
         check(load().npi_linear_bwd_data_ex(ptr(dc), dc.stride(0), ptr(weight), weight.stride(0), ptr(rowscale),
                                              ptr(da), da.stride(0), M, K, N, _code(dc),
