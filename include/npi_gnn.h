@@ -737,6 +737,53 @@ int npi_sample_relabel(int32_t* scratch, int64_t N, const int32_t* workspace, co
                        const int32_t* out_tgt, int64_t E, const int64_t* targets, int64_t n, int64_t U, int64_t* n_id,
                        int64_t* edge_src, int64_t* edge_dst, int64_t* e_id, int64_t* res_n_id, int32_t* status, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Neighbour sampling, the ONE-ID-SPACE data flow: the producer of the sampled subgraph that the square layers (SAGEConv, GCNConv,
+ * GATConv over a CSRGraph, GraphBatch) run over.  Replaces PyG 1.4.2 `torch_geometric.data.NeighborSampler.__produce_subgraph__`
+ * (`bipartite=False`), which walks the hops with `torch_cluster.neighbor_sampler`, concatenates their `n_id` / `e_id`, takes
+ * `n_id.unique(sorted=False)`, relabels both edge ends through `tmp[n_id] = arange`, merges equal pairs with
+ * `idx = src * num_nodes + dst; idx.unique()` and `scatter_`s one `e_id` per pair, all on the CPU.
+ *
+ * SEMANTICS.  For a batch b_id[n] (int64 global ids, repeats allowed), budgets size[0 .. L) and a key seed s:
+ *   T_0 = b_id; hop l samples the in-edges of every node of T_l by THE RULE above with (seed, hop) = (s, l) and the budget size[l];
+ *   T_{l+1} = the distinct sources sampled at hop l, ascending (targets are NOT carried over; add_self_loops plays no part).
+ * These hops ARE the blocks of the bipartite data flow with add_self_loops = 0 for the same seed and batch: the caller runs
+ * npi_sample_counts / npi_sample_select (/ npi_sample_relabel for T_{l+1}) per hop and hands the concatenation of the hops'
+ * sampled entries -- src_g, dst_g (global ids of both ends), eid (column of the edge list), int32, E entries -- to the two calls
+ * below.  Results:
+ *   n_id        the distinct ids of b_id u T_1 u ... u T_L, ASCENDING (PyG's unique(sorted=False) leaves the order open); a batch
+ *               node without in-edges is in it, isolated.  num_nodes = U = its length.
+ *   sub_b_id[t] the position of b_id[t] in n_id (repeats repeat; -1 for an id outside [0, N), which is never dereferenced and raises
+ *               NPI_STATUS_BAD_TARGET_ID).
+ *   edge_index  the sampled edges of all hops with both ends relabelled into n_id positions, equal (src_local, dst_local) pairs
+ *               merged into one column -- a pair repeats when its target is a target of two hops, for parallel edges of a multigraph
+ *               and for a repeated batch id -- in ASCENDING (src_local, dst_local) order (the order of PyG's idx.unique() on the
+ *               CPU).  (v, v) columns of the edge list are ordinary edges and stay.  Nothing sampled: no column.
+ *   e_id        for each column the SMALLEST edge-list column among the merged ones (PyG's scatter_ leaves open which survives).
+ * A pure function of (seed, batch, graph): bitwise reproducible, independent of launch geometry and timing (no float, no
+ * order-dependent atomic: idempotent marks, stable sorts, a minimum).
+ *
+ *   npi_sample_union    : marks every src_g / dst_g / b_id in scratch[N] (int32, ALL ZERO on entry, 16-byte aligned; the sampler's),
+ *                         counts the marks per chunk into workspace[npi_sample_workspace_elems(N)], writes info[0] = U and
+ *                         info[1] = E, n_id[0 .. U) (n_id_cap: the length the caller gave n_id; U <= min(N, n + E) always holds for
+ *                         hops as above, so that bound sizes it without a host read), src_l[E] / dst_l[E] = the positions of the
+ *                         two ends in n_id (int32; -1 for an id outside [0, N)), sub_b_id[n].  More marks than n_id_cap: writes
+ *                         within it and raises NPI_STATUS_BAD_SAMPLE_SIZES.  status[0] (may be NULL) is OR-ed into, never cleared.
+ *                         Leaves scratch ALL ZERO again.
+ *   npi_sample_coalesce : two stable radix sorts of the E entries on the bits that U - 1 needs (dst_l, then src_l, carrying the
+ *                         entry index), run heads, their scan, and the compaction: edge_src / edge_dst / e_id[0 .. E_u) (int64; the
+ *                         caller sizes them with the bound E) and info[0] = E_u.  workspace: npi_sample_coalesce_workspace_bytes(E)
+ *                         bytes, 16-byte aligned.  Ids must lie in [0, U) (npi_sample_union's).
+ * Both allocate nothing, keep no state and do nothing (return 0) for empty input (E == 0 and, for the union, n == 0).  The caller
+ * reads (U, E_u) once, with the status word, and trims.
+ * ------------------------------------------------------------------------------------------ */
+int npi_sample_union(const int32_t* src_g, const int32_t* dst_g, int64_t E, const int64_t* b_id, int64_t n, int32_t* scratch,
+                     int64_t N, int32_t* workspace, int64_t n_id_cap, int64_t* n_id, int32_t* src_l, int32_t* dst_l,
+                     int64_t* sub_b_id, int32_t* info, int32_t* status, void* stream);
+int64_t npi_sample_coalesce_workspace_bytes(int64_t E);
+int npi_sample_coalesce(const int32_t* src_l, const int32_t* dst_l, const int32_t* eid, int64_t E, int64_t U, int64_t* edge_src,
+                        int64_t* edge_dst, int64_t* e_id, int32_t* info, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Evaluation loop (reference src/methods.py:87-105 compares one element per Python
  * iteration, one device sync each).  counts[4] += [TP, FN, TN, FP] for pred = first arg-max of scores[i, 0..C):
  * pred 1 & y 1 -> TP, pred 1 & y 0 -> FP, pred 0 & y 1 -> FN, anything else -> TN (the reference's else

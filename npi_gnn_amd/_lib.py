@@ -23,8 +23,8 @@ NPI_GEMM_WORKSPACE_PREPARED = 8   # the workspace already holds npi_linear_prepa
 NPI_GEMM_SPLIT_F16X2 = 16         # two fp16 pieces per operand, three matrix products per tile pair (needs the row scales of A)
 NPI_PREPARE_F16X2 = 4             # npi_linear_prepare(which | this): the fp16 x 2 planes of the weight matrix
 NPI_STATUS_BAD_ROW_ID = 8         # status bit of npi_rows_gather: a row id outside the source table
-NPI_STATUS_BAD_TARGET_ID = 16     # status bit of npi_sample_counts: a target id outside [0, N)
-NPI_STATUS_BAD_SAMPLE_SIZES = 32  # status bit of npi_sample_select / npi_sample_relabel: offsets / counts of another call
+NPI_STATUS_BAD_TARGET_ID = 16     # status bit of npi_sample_counts / npi_sample_union: a target (batch) id outside [0, N)
+NPI_STATUS_BAD_SAMPLE_SIZES = 32  # status bit of npi_sample_select / _relabel / _union: offsets / counts / capacity of another call
 NPI_HUB_MAX = 128                # hubs per plan (npi_hub_plan; mask words of NPI_HUB_MAX / 32 per source row)
 
 
@@ -144,6 +144,9 @@ PROTOTYPES = {
     "npi_sample_workspace_elems": (_I, [_I]),
     "npi_sample_relabel_count": (c_int, [_P, _P, _I, _I, _P, c_int, _P, _I, _P, _P, _P]),
     "npi_sample_relabel": (c_int, [_P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "npi_sample_union": (c_int, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "npi_sample_coalesce_workspace_bytes": (_I, [_I]),
+    "npi_sample_coalesce": (c_int, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
 }
 
 _lib = None

@@ -356,6 +356,53 @@ static void radix_sort_pairs(uint32_t*& keys_a, uint32_t*& keys_b, int32_t*& val
     }
 }
 
+// ---- merging the equal (source, target) pairs of a sampled subgraph (npi_sample_coalesce; the sampler's other kernels: sample.hip) ------
+// Replaces the `idx = src * num_nodes + dst; idx.unique()` + `scatter_` lines of PyG 1.4.2 NeighborSampler.__produce_subgraph__.  LSD over
+// the pair: the stable sort by target first, then the stable sort by source; val = the entry's index, so equal pairs stay in entry order.
+__global__ void coalesce_keys_kernel(const int32_t* __restrict__ dst_l, int64_t E, uint32_t* __restrict__ keys, int32_t* __restrict__ vals) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= E) return;
+    keys[i] = (uint32_t)dst_l[i];
+    vals[i] = (int32_t)i;
+}
+__global__ void coalesce_rekey_kernel(const int32_t* __restrict__ src_l, const int32_t* __restrict__ vals, int64_t E,
+                                      uint32_t* __restrict__ keys) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < E) keys[p] = (uint32_t)src_l[vals[p]];
+}
+// dst_s[p] = the target of the entry sorted to p (its source: the sort's key); head[p] = 1 where a run of equal pairs starts
+__global__ void coalesce_heads_kernel(const uint32_t* __restrict__ src_s, const int32_t* __restrict__ vals, const int32_t* __restrict__ dst_l,
+                                      int64_t E, int32_t* __restrict__ dst_s, int32_t* __restrict__ head) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= E) return;
+    const int32_t d = dst_l[vals[p]];
+    dst_s[p] = d;
+    head[p] = (p == 0 || src_s[p - 1] != src_s[p] || dst_l[vals[p - 1]] != d) ? 1 : 0;
+}
+// pos = the exclusive scan of head.  The head of a run writes the pair and the smallest eid of its run (runs are short: a pair
+// repeats once per hop it was sampled in and once per parallel edge); info[0] = the number of runs
+__global__ void coalesce_compact_kernel(const uint32_t* __restrict__ src_s, const int32_t* __restrict__ dst_s, const int32_t* __restrict__ vals,
+                                        const int32_t* __restrict__ pos, const int32_t* __restrict__ eid, int64_t E,
+                                        int64_t* __restrict__ edge_src, int64_t* __restrict__ edge_dst, int64_t* __restrict__ e_id,
+                                        int32_t* __restrict__ info) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= E) return;
+    const uint32_t s = src_s[p];
+    const int32_t d = dst_s[p];
+    const bool head = p == 0 || src_s[p - 1] != s || dst_s[p - 1] != d;
+    const int64_t q = pos[p];                                    // q <= p < E: within the caller's bound
+    if (p == E - 1) info[0] = (int32_t)(q + (head ? 1 : 0));
+    if (!head) return;
+    int32_t m = eid[vals[p]];
+    for (int64_t r = p + 1; r < E && src_s[r] == s && dst_s[r] == d; ++r) {
+        const int32_t e = eid[vals[r]];
+        m = e < m ? e : m;
+    }
+    edge_src[q] = (int64_t)(int32_t)s;
+    edge_dst[q] = d;
+    e_id[q] = m;
+}
+
 // ---- TopKPooling selection for graphs of ANY size (pool.hip sorts a graph's scores in LDS: up to 16,384 nodes) -----------
 // Two stable radix sorts of the whole batch: by score (descending; the sort is stable over the node index, so equal scores
 // keep the lower index first -- torch.sort(descending=True, stable) order, as the LDS kernel), then by graph id: position
@@ -478,6 +525,51 @@ extern "C" int npi_csr_build_ex(const int64_t* key_nodes, const int64_t* val_nod
     int64_t n_items = num_items_of(nnz_max, item_edges);
     item_rows_kernel<<<(unsigned)ceil_div(n_items + 1, 256), 256, 0, stream>>>(rowptr, N, n_items, (int)item_edges, item_row);
     return check_launch("npi_csr_build");
+}
+
+extern "C" int64_t npi_sample_coalesce_workspace_bytes(int64_t E) {
+    if (E < 0 || E >= (int64_t)0x7fffffff) return -1;
+    return sort_layout(E, 0).total;
+}
+
+extern "C" int npi_sample_coalesce(const int32_t* src_l, const int32_t* dst_l, const int32_t* eid, int64_t E, int64_t U, int64_t* edge_src,
+                                   int64_t* edge_dst, int64_t* e_id, int32_t* info, void* workspace, int64_t workspace_bytes,
+                                   void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    NPI_REQUIRE(E >= 0 && E < (int64_t)0x7fffffff && U >= 0 && U < (int64_t)0x7fffffff, "npi_sample_coalesce: bad size");
+    if (E == 0) return NPI_OK;
+    NPI_REQUIRE(src_l && dst_l && eid && edge_src && edge_dst && e_id && info && workspace, "npi_sample_coalesce: null pointer");
+    NPI_REQUIRE(((uintptr_t)workspace & 15) == 0, "npi_sample_coalesce: workspace must be 16-byte aligned");
+    SortLayout L = sort_layout(E, 0);
+    if (workspace_bytes < L.total) {
+        set_error("npi_sample_coalesce: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)L.total);
+        return NPI_ERR_WORKSPACE;
+    }
+    char* ws = (char*)workspace;
+    uint32_t* keys_a = (uint32_t*)(ws + L.off_keys_a);
+    uint32_t* keys_b = (uint32_t*)(ws + L.off_keys_b);
+    int32_t* vals_a = (int32_t*)(ws + L.off_vals_a);
+    int32_t* vals_b = (int32_t*)(ws + L.off_vals_b);
+    int32_t* counts = (int32_t*)(ws + L.off_counts);
+    int32_t* tiles = (int32_t*)(ws + L.off_tiles);
+    int bits = 1;
+    while (((int64_t)1 << bits) < U) ++bits;             // local ids lie in [0, U)
+    const unsigned eb = (unsigned)ceil_div(E, 256);
+    coalesce_keys_kernel<<<eb, 256, 0, stream>>>(dst_l, E, keys_a, vals_a);
+    radix_sort_pairs(keys_a, keys_b, vals_a, vals_b, E, bits, L, counts, tiles, stream);
+    coalesce_rekey_kernel<<<eb, 256, 0, stream>>>(src_l, vals_a, E, keys_a);
+    radix_sort_pairs(keys_a, keys_b, vals_a, vals_b, E, bits, L, counts, tiles, stream);
+    // the sort's second pair of buffers is free now: the sorted targets and the run heads; the histogram buffer (E / 16 words) holds
+    // the scan's tile sums (E / SCAN_TILE of them)
+    int32_t* dst_s = vals_b;
+    int32_t* head = (int32_t*)keys_b;
+    const int64_t ntiles = ceil_div(E, SCAN_TILE);
+    coalesce_heads_kernel<<<eb, 256, 0, stream>>>(keys_a, vals_a, dst_l, E, dst_s, head);
+    scan_tiles_kernel<<<(unsigned)ntiles, SCAN_THREADS, 0, stream>>>(head, E, counts);
+    scan_sums_kernel<<<1, SCAN_THREADS, 0, stream>>>(counts, ntiles);
+    scan_add_kernel<<<(unsigned)ntiles, SCAN_THREADS, 0, stream>>>(head, E, counts);
+    coalesce_compact_kernel<<<eb, 256, 0, stream>>>(keys_a, dst_s, vals_a, head, eid, E, edge_src, edge_dst, e_id, info);
+    return check_launch("npi_sample_coalesce");
 }
 
 extern "C" int64_t npi_topk_sorted_workspace_bytes(int64_t N) {

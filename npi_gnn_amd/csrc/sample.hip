@@ -322,7 +322,7 @@ relabel_scan_kernel(int32_t* __restrict__ chunk_cnt, int64_t nb, const int64_t* 
     if (t == 1023) {
         chunk_cnt[nb] = (int)part[1023];                   // at most N < 2^31 marks
         info[0] = (int)part[1023];
-        int64_t E = offsets[n];
+        int64_t E = offsets != nullptr ? offsets[n] : n_out;       // (the union of the hops has no offsets: its entry count is n_out)
         E = E < n_out ? E : n_out;
         info[1] = (int)(E < 0 ? 0 : E);
     }
@@ -376,6 +376,45 @@ relabel_edges_kernel(const int32_t* __restrict__ scratch, int64_t N, const int32
             const int64_t v = targets[i];
             res_n_id[i] = (v >= 0 && v < N) ? (int64_t)scratch[v] - 1 : -1;
         }
+}
+
+// ---- the one-id-space flow: the union of the hops' entries and of the batch, relabelled on both ends -------------------------------------
+// Replaces the `n_id.unique()` / `tmp[n_id] = arange` / `tmp[...]` lines of PyG 1.4.2 NeighborSampler.__produce_subgraph__.  Same scheme
+// as a hop's relabelling (idempotent marks in the N-entry scratch, relabel_count / scan / positions as they are); only what is marked
+// and what is looked up differ.
+__global__ void __launch_bounds__(256)
+union_mark_kernel(const int32_t* __restrict__ src_g, const int32_t* __restrict__ dst_g, int64_t E, const int64_t* __restrict__ b_id,
+                  int64_t n, int32_t* __restrict__ scratch, int64_t N, int32_t* __restrict__ status) {
+    const int64_t nt = (int64_t)gridDim.x * blockDim.x, i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool bad = false;
+    for (int64_t i = i0; i < E; i += nt) {
+        const int32_t s = src_g[i], d = dst_g[i];
+        if (s >= 0 && s < N) scratch[s] = 1; else bad = true;
+        if (d >= 0 && d < N) scratch[d] = 1; else bad = true;
+    }
+    for (int64_t i = i0; i < n; i += nt) {
+        const int64_t v = b_id[i];
+        if (v >= 0 && v < N) scratch[v] = 1; else bad = true;       // dropped and reported, never dereferenced
+    }
+    if (bad && status != nullptr) atomicOr(status, STATUS_BAD_TARGET);
+}
+
+// after relabel_positions_kernel: scratch[g] - 1 = position of g in n_id
+__global__ void __launch_bounds__(256)
+union_local_kernel(const int32_t* __restrict__ scratch, int64_t N, const int32_t* __restrict__ src_g, const int32_t* __restrict__ dst_g,
+                   int64_t E, const int64_t* __restrict__ b_id, int64_t n, const int32_t* __restrict__ chunk_cnt, int64_t nb, int64_t cap,
+                   int32_t* __restrict__ src_l, int32_t* __restrict__ dst_l, int64_t* __restrict__ sub_b_id, int32_t* __restrict__ status) {
+    if (blockIdx.x == 0 && threadIdx.x == 0 && chunk_cnt[nb] > cap && status != nullptr) atomicOr(status, STATUS_BAD_OFFSETS);
+    const int64_t nt = (int64_t)gridDim.x * blockDim.x, i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t i = i0; i < E; i += nt) {
+        const int32_t s = src_g[i], d = dst_g[i];
+        src_l[i] = (s >= 0 && s < N) ? scratch[s] - 1 : -1;
+        dst_l[i] = (d >= 0 && d < N) ? scratch[d] - 1 : -1;
+    }
+    for (int64_t i = i0; i < n; i += nt) {
+        const int64_t v = b_id[i];
+        sub_b_id[i] = (v >= 0 && v < N) ? (int64_t)scratch[v] - 1 : -1;
+    }
 }
 
 }  // namespace npi
@@ -458,4 +497,27 @@ extern "C" int npi_sample_relabel(int32_t* scratch, int64_t N, const int32_t* wo
                                                                               edge_dst, e_id, res_n_id);
     if (N > 0) (void)hipMemsetAsync(scratch, 0, (size_t)N * sizeof(int32_t), stream);   // the scratch is left as it was found
     return check_launch("npi_sample_relabel");
+}
+
+extern "C" int npi_sample_union(const int32_t* src_g, const int32_t* dst_g, int64_t E, const int64_t* b_id, int64_t n, int32_t* scratch,
+                                int64_t N, int32_t* workspace, int64_t n_id_cap, int64_t* n_id, int32_t* src_l, int32_t* dst_l,
+                                int64_t* sub_b_id, int32_t* info, int32_t* status, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    NPI_REQUIRE(N >= 0 && N < 0x7fffffff && n >= 0 && n < 0x7fffffff && E >= 0 && E < 0x7fffffff && n_id_cap >= 0 && n_id_cap <= N,
+                "npi_sample_union: bad size");
+    if (E == 0 && n == 0) return NPI_OK;
+    NPI_REQUIRE(workspace && info && (N == 0 || scratch) && (n_id_cap == 0 || n_id), "npi_sample_union: null pointer");
+    NPI_REQUIRE((E == 0 || (src_g && dst_g && src_l && dst_l)) && (n == 0 || (b_id && sub_b_id)), "npi_sample_union: null pointer");
+    NPI_REQUIRE(((uintptr_t)scratch & 15) == 0, "npi_sample_union: scratch must be 16-byte aligned");
+    const int64_t nb = ceil_div(N, RELABEL_CHUNK);
+    const unsigned grid = grid_for(E > n ? E : n, 256);
+    union_mark_kernel<<<grid, 256, 0, stream>>>(src_g, dst_g, E, b_id, n, scratch, N, status);
+    if (nb > 0) relabel_count_kernel<<<(unsigned)nb, RELABEL_BLOCK, 0, stream>>>(scratch, N, workspace);
+    relabel_scan_kernel<<<1, 1024, 0, stream>>>(workspace, nb, nullptr, 0, E, info);
+    // (positions: n_id within the caller's capacity; more marks than that are reported by union_local_kernel)
+    if (nb > 0) relabel_positions_kernel<<<(unsigned)nb, RELABEL_BLOCK, 0, stream>>>(scratch, N, workspace, nb, n_id_cap, n_id, nullptr);
+    union_local_kernel<<<grid, 256, 0, stream>>>(scratch, N, src_g, dst_g, E, b_id, n, workspace, nb, n_id_cap, src_l, dst_l, sub_b_id,
+                                                 status);
+    if (N > 0) (void)hipMemsetAsync(scratch, 0, (size_t)N * sizeof(int32_t), stream);   // the scratch is left as it was found
+    return check_launch("npi_sample_union");
 }

@@ -12,7 +12,15 @@ Beside it: the numpy restatement of the sampling rule of ``include/npi_gnn.h`` o
 composition on the GPU to put beside it: a draw without replacement per row needs a ``randperm`` per row, which torch does not
 have -- the numpy figure is the comparison.
 
-usage: python tools/sampler_time.py [--batches 100] [--numpy-batches 3] [--json OUT]"""
+``--subgraph``: the one-id-space flow instead (``sampler.sample_subgraph``), same graph, batches and sizes.  Per batch: the device
+time of ``npi_sample_union`` and ``npi_sample_coalesce`` (HIP events around each call), the wall time of the stage
+``union_subgraph`` (both calls, the host read of the two sizes and the trim; ending in a synchronise) and of the whole
+``sample_subgraph`` (hops included).  Beside it, on the same hop outputs and alternating with it: the same algorithm composed from
+torch device ops -- PyG's formula (``unique`` of all ids, ``tmp[n_id] = arange``, ``idx = src * num_nodes + dst``,
+``idx.unique(return_inverse=True)``, a ``scatter_reduce`` minimum for ``e_id``) -- by the same host clock; its result is compared with
+the stage's while it is at it.
+
+usage: python tools/sampler_time.py [--batches 100] [--numpy-batches 3] [--subgraph] [--json OUT]"""
 import argparse
 import json
 import os
@@ -72,7 +80,7 @@ class TimedLib:
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if not name.startswith("npi_sample_") or name.endswith("_elems"):
+        if not name.startswith("npi_sample_") or name.endswith(("_elems", "_bytes")):
             return fn
 
         def timed(*args):
@@ -93,6 +101,56 @@ class TimedLib:
         return out
 
 
+def torch_union_coalesce(b_id, src_g, dst_g, eid, tmp):
+    """PyG 1.4.2 ``__produce_subgraph__`` behind the hops, composed from torch ops on the device (``tmp``: an N-entry LongTensor kept
+    between calls, as PyG's ``self.tmp``); the minimum instead of ``scatter_``'s whichever-comes-last, so that the result is defined"""
+    n_id = torch.unique(torch.cat([b_id, src_g, dst_g]))
+    U = n_id.numel()
+    tmp[n_id] = torch.arange(U, device=n_id.device)
+    idx = tmp[src_g] * U + tmp[dst_g]
+    idx, inv = idx.unique(return_inverse=True)
+    edge_index = torch.stack([idx // U, idx % U])
+    e_id = torch.full((idx.numel(),), 2 ** 62, dtype=torch.int64, device=idx.device).scatter_reduce_(0, inv, eid, "amin")
+    return edge_index, e_id, n_id, tmp[b_id], U
+
+
+def subgraph_mode(args, sampler, timed, order, seed, dev):
+    """the ``--subgraph`` run (module docstring)"""
+    tmp = torch.empty(args.nodes, dtype=torch.int64, device=dev)
+    rows = []
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, 1e3 * (time.perf_counter() - t0)
+    for i, pos in enumerate(order):
+        b_id = pos.to(dev)
+        _, whole = wall(lambda: sampler.sample_subgraph(b_id, seed))
+        timed.take()
+        src_g, dst_g, eid = sampler.hop_entries(b_id, seed)
+        src64, dst64, eid64 = src_g.long(), dst_g.long(), eid.long()
+        timed.take()
+        sub, stage = wall(lambda: sampler.union_subgraph(b_id, src_g, dst_g, eid))
+        ev = timed.take()
+        ref, composed = wall(lambda: torch_union_coalesce(b_id, src64, dst64, eid64, tmp))
+        same = (torch.equal(ref[0], sub.edge_index) and torch.equal(ref[1], sub.e_id) and torch.equal(ref[2], sub.n_id)
+                and torch.equal(ref[3], sub.sub_b_id) and ref[4] == sub.num_nodes)
+        if not same:
+            raise SystemExit("the stage's subgraph differs from the torch composition")
+        if i >= args.warmup:
+            rows.append({"union_ms": ev["npi_sample_union"], "coalesce_ms": ev["npi_sample_coalesce"], "stage_wall_ms": stage,
+                         "torch_composed_wall_ms": composed, "sample_subgraph_wall_ms": whole, "entries": int(src_g.numel()),
+                         "num_nodes": sub.num_nodes, "edges": int(sub.e_id.numel())})
+    res = {k: {"median": statistics.median(r[k] for r in rows), "min": min(r[k] for r in rows), "max": max(r[k] for r in rows)}
+           for k in rows[0]}
+    res["batches"] = len(rows)
+    print(json.dumps(res, indent=1), flush=True)
+    print("(every subgraph equal to the torch composition's)", flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=100)
@@ -100,6 +158,7 @@ def main():
     ap.add_argument("--numpy-batches", type=int, default=3)
     ap.add_argument("--nodes", type=int, default=1_000_000)
     ap.add_argument("--edges", type=int, default=20_000_000)
+    ap.add_argument("--subgraph", action="store_true", help="time the one-id-space flow (sample_subgraph) instead")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda")
@@ -116,6 +175,12 @@ def main():
     order = S.epoch_batches(args.nodes, bs, True, False, 0, 0)[: args.warmup + args.batches]
     timed = TimedLib(S.load())
     S.load = lambda: timed                                   # the sampler module's handle on the library, for this process only
+    if args.subgraph:
+        res = subgraph_mode(args, sampler, timed, order, seed, dev)
+        if args.json:
+            os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+            json.dump(res, open(args.json, "w"), indent=1)
+        return
     rows, flows = [], []
     for i, pos in enumerate(order):
         targets = pos.to(dev)
