@@ -558,6 +558,16 @@ int npi_gat_aggregate_fused(const int32_t* rowptr, const int32_t* col, const int
                                 int64_t split, float* out, int64_t ldo, int64_t C, const float* a_dst, const float* att,
                                 float negative_slope, const float* bias, int relu, float* m, float* s, float* carry,
                                 float* row_scales_out, void* stream);
+/* The same launch for H = 2, 4 or 8 heads of C = 32, 64 or 128 channels with H C <= 256 (the shapes npi_gat_backward_fused_heads
+ * serves): x / out rows are H C wide, a_dst, m, s are [N, H], att is the layer's [H, 2 C].  A head is a group of C / 4 lanes: the
+ * score's dot is summed inside the group in one fixed order, every lane keeps the online softmax of its own head, and the parts of a
+ * cut row carry (max, sum) per head.  x, x2, out and att must be 16-byte aligned (bias need not be), ldx and ldo multiples of 4.  H == 1 forwards
+ * to npi_gat_aggregate_fused; row_scales_out must be NULL unless H == 1.  Any other shape returns NPI_ERR_ARG before a launch. */
+int npi_gat_aggregate_fused_heads(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* item_row,
+                                  int64_t item_edges, int64_t N, int64_t nnz_max, const float* x, int64_t ldx, const float* x2,
+                                  int64_t split, float* out, int64_t ldo, int64_t H, int64_t C, const float* a_dst,
+                                  const float* att, float negative_slope, const float* bias, int relu, float* m, float* s,
+                                  float* carry, float* row_scales_out, void* stream);
 int64_t npi_gat_rowdot_colsum_workspace_elems(int64_t N, int64_t H, int64_t C);
 /* `F.relu(conv(x))` fused (npi_gat_aggregate_scores with relu != 0 applies the ReLU in the row epilogue): b is then the ReLU
  * OUTPUT, and this form first masks the incoming gradient, a' = a where b > 0 else 0 (threshold_backward), uses a' for D and

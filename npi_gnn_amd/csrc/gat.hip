@@ -809,6 +809,41 @@ extern "C" int npi_gat_aggregate_fused(const int32_t* rowptr, const int32_t* col
     return segsum_run(P, W_GAT_DST_FUSED, 0, nnz_max, NPI_F32, stream);
 }
 
+// The same launch for 2 / 4 / 8 heads (W_GAT_DST_FUSED_H2/4/8; the shapes of the fused backward: 32 / 64 / 128 channels per head,
+// H C <= 256): a_dst, m, s are [N, H], att [H, 2C].  One head forwards to the mode above; no other shape has a kernel
+extern "C" int npi_gat_aggregate_fused_heads(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* item_row,
+                                             int64_t item_edges, int64_t N, int64_t nnz_max, const float* x, int64_t ldx,
+                                             const float* x2, int64_t split, float* out, int64_t ldo, int64_t H, int64_t C,
+                                             const float* a_dst, const float* att, float slope, const float* bias, int relu,
+                                             float* m, float* s, float* carry, float* row_scales_out, void* stream_) {
+    if (H == 1)
+        return npi_gat_aggregate_fused(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, x, ldx, x2, split, out, ldo, C, a_dst, att,
+                                       slope, bias, relu, m, s, carry, row_scales_out, stream_);
+    hipStream_t stream = (hipStream_t)stream_;
+    NPI_REQUIRE(H == 2 || H == 4 || H == 8, "npi_gat_aggregate_fused_heads: heads must be 1, 2, 4 or 8");
+    NPI_REQUIRE((C == 32 || C == 64 || C == 128) && H * C <= 256,
+                "npi_gat_aggregate_fused_heads: several heads need 32 / 64 / 128 channels per head and heads * out_channels <= 256");
+    NPI_REQUIRE(row_scales_out == nullptr, "npi_gat_aggregate_fused_heads: row_scales_out serves one head");
+    NPI_REQUIRE(x2 == nullptr || (split >= 0 && split < 0x7fffffff), "npi_gat_aggregate_fused_heads: bad split");
+    NPI_REQUIRE(item_edges_ok(item_edges), "npi_gat_aggregate_fused_heads: item_edges must be 64 or NPI_ITEM_EDGES (the value the CSR was built with)");
+    NPI_REQUIRE(N >= 0 && nnz_max > 0, "npi_gat_aggregate_fused_heads: bad size");
+    NPI_REQUIRE(att == nullptr || (uintptr_t)att % 16 == 0, "npi_gat_aggregate_fused_heads: att must be 16-byte aligned");
+    if (N == 0) return NPI_OK;
+    NPI_REQUIRE(rowptr && col && item_row && x && out && a_dst && att && m && s && carry, "npi_gat_aggregate_fused_heads: null pointer");
+    const int64_t F = H * C;
+    NPI_REQUIRE(ldx >= F && ldo >= F && ldx % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 &&
+                (x2 == nullptr || ((uintptr_t)x2 % 16) == 0) && ((uintptr_t)carry % 16) == 0,
+                "npi_gat_aggregate_fused_heads: leading dimension / 16-byte alignment of the rows");
+    SegParams P{};
+    P.rowptr = rowptr; P.col = col; P.item_row = item_row; P.rowidx = rowidx;
+    P.N = (int)N; P.item = (int)item_edges;
+    P.x = x; P.ldx = ldx; P.out = out; P.ldo = ldo; P.F = (int)F;
+    P.x2 = x2; P.split = (int)split;
+    P.carry = carry; P.bias = bias;
+    P.H = (int)H; P.C = (int)C; P.a_dst = a_dst; P.att = att; P.slope = slope; P.m_out = m; P.s_out = s; P.relu = relu ? 1 : 0;
+    return segsum_run(P, H == 2 ? W_GAT_DST_FUSED_H2 : H == 4 ? W_GAT_DST_FUSED_H4 : W_GAT_DST_FUSED_H8, 0, nnz_max, NPI_F32, stream);
+}
+
 extern "C" int npi_gat_edge_grad_ex(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
                                     int64_t N, int64_t nnz_max, const float* hfeat, int64_t ldh,
                                     const float* hfeat2, int64_t split,

@@ -12,9 +12,16 @@ enum { W_NONE = 0, W_ARRAY = 1, W_GAT_DST = 2, W_GAT_SRC = 3, W_GAT_SRC_PRE = 4,
        // (lane-parallel, parked in LDS); a row that lies inside the item is weighted against its exact maximum, exactly as with the
        // statistics pass in front; the parts of a row that is cut by item / workgroup boundaries carry their own (max, sum exp) and
        // are merged with the usual rescaling exp(m_part - m_row) where the cut rows are resolved (segsum.hip)
-       W_GAT_DST_FUSED = 10 };
+       W_GAT_DST_FUSED = 10,
+       // the same forward for 2 / 4 / 8 heads (H C <= 256, C = 32 / 64 / 128): a head is a group of C / 4 lanes, every lane keeps the
+       // online softmax of ITS head, every partial row carries (max, sum exp) per head
+       W_GAT_DST_FUSED_H2 = 11, W_GAT_DST_FUSED_H4 = 12, W_GAT_DST_FUSED_H8 = 13 };
 constexpr bool is_fused_mode(int m) { return m == W_GAT_SRC_FUSED || (m >= W_GAT_SRC_FUSED_H2 && m <= W_GAT_SRC_FUSED_H8); }
 constexpr int fused_heads(int m) { return m == W_GAT_SRC_FUSED_H2 ? 2 : m == W_GAT_SRC_FUSED_H4 ? 4 : m == W_GAT_SRC_FUSED_H8 ? 8 : 1; }
+// heads of the fused FORWARD (the online softmax): 0 = not that mode
+constexpr int softmax_heads(int m) {
+    return m == W_GAT_DST_FUSED ? 1 : m == W_GAT_DST_FUSED_H2 ? 2 : m == W_GAT_DST_FUSED_H4 ? 4 : m == W_GAT_DST_FUSED_H8 ? 8 : 0;
+}
 
 // What segsum.hip's row epilogue, lane geometry, launch bounds and dispatch ask about a weight mode, each property named once
 struct ModeTraits {
@@ -34,6 +41,7 @@ constexpr ModeTraits mode_traits(int m) {
          : m == W_GAT_DST         ? ModeTraits{false, false, true,  true,  false, 0, false, false}
          : m == W_GAT_DST_PRE     ? ModeTraits{false, true,  true,  true,  false, 0, false, false}
          : m == W_GAT_DST_FUSED   ? ModeTraits{false, false, true,  false, true,  0, false, true}
+         : softmax_heads(m) > 1   ? ModeTraits{false, false, true,  false, true,  0, false, false}
          : m == W_GAT_SRC         ? ModeTraits{false, false, true,  false, false, 0, true,  false}
          : m == W_GAT_SRC_PRE     ? ModeTraits{false, true,  true,  false, false, 0, true,  false}
          : is_fused_mode(m)       ? ModeTraits{false, true,  true,  false, false, fused_heads(m), false, true}
@@ -90,8 +98,8 @@ struct SegParams {
     // (a_dst, m, 1 / (s + 1e-16), D) of every TARGET node AND HEAD as one float4 ([n_cols, H, 4]): one 16-byte gather per entry
     // and head, alpha recomputed by the lane that owns the entry
     const float4* tpack;
-    // W_GAT_DST_FUSED: the statistics it computes, [N] each (one head): row max of the scores, row sum of exp(score - max);
-    // `rowidx` above is then the by-TARGET CSR's row of every entry, a_dst / a_src the per-node scores, slope the leaky_relu's
+    // W_GAT_DST_FUSED*: the statistics it computes, [N, H] each: row max of the scores, row sum of exp(score - max);
+    // `rowidx` above is then the by-TARGET CSR's row of every entry, a_dst [N, H] the targets' scores, slope the leaky_relu's
     float* m_out;
     float* s_out;
 };

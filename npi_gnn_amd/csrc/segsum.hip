@@ -31,6 +31,8 @@
 //              the scores of its own entries, every row part is weighted against the maximum of ITS entries and carries
 //              (max, sum exp) next to its partial row; parts of a cut row are merged with exp(m_part - m_row) where cut rows
 //              are resolved, and the row's (m, s) come out beside the output for the backward
+//   W_GAT_DST_FUSED_H2/4/8  the same for 2 / 4 / 8 heads (H C <= 256): a head is a group of C / 4 lanes, the score's dot is summed
+//              inside the group, every lane keeps (max, sum exp) of its own head and every partial row carries them per head
 #include "segsum.h"
 
 #include <stdlib.h>
@@ -146,6 +148,31 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
     return bcast_f(v, WAVE - 1);
 }
 
+// sum inside every aligned group of lph = 8 / 16 / 32 lanes, the same value in every lane of the group, in one fixed order: an xor
+// butterfly.  Steps 1 and 2 are quad permutes; once the lanes of a quad agree, half_mirror (lane i <- 7 - i) IS the xor-4 step and,
+// once the groups of 8 agree, row_mirror (i <- 15 - i) the xor-8 step; xor 16 crosses DPP rows: ds_swizzle (no address register)
+__device__ __forceinline__ float group_sum(float v, int lph) {
+#define NPI_DPP_XADD(CTRL) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false))
+    NPI_DPP_XADD(0xB1);              // quad_perm [1, 0, 3, 2]
+    NPI_DPP_XADD(0x4E);              // quad_perm [2, 3, 0, 1]
+    NPI_DPP_XADD(0x141);             // row_half_mirror
+    if (lph >= 16) NPI_DPP_XADD(0x140);                                   // row_mirror
+#undef NPI_DPP_XADD
+    if (lph >= 32) v += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x401F));      // bit mode: xor 16
+    return v;
+}
+// the maximum in the same order
+__device__ __forceinline__ float group_max(float v, int lph) {
+#define NPI_DPP_XMAX(CTRL) v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false)))
+    NPI_DPP_XMAX(0xB1);
+    NPI_DPP_XMAX(0x4E);
+    NPI_DPP_XMAX(0x141);
+    if (lph >= 16) NPI_DPP_XMAX(0x140);
+#undef NPI_DPP_XMAX
+    if (lph >= 32) v = fmaxf(v, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x401F)));
+    return v;
+}
+
 // the same reduction for NON-NEGATIVE values, leaving the result in lane 63 only (no broadcast): invalid source lanes read as zero
 // (bound_ctrl), so the DPP needs no identity register -- finish_row runs at the kernel's register cap
 __device__ __forceinline__ float wave_max_nonneg_lane63(float v) {
@@ -162,14 +189,20 @@ __device__ __forceinline__ float wave_max_nonneg_lane63(float v) {
 }
 
 // scale, bias and epilogue of a finished row r, then the store
-// (m_val, s_val: the online softmax only -- the row's softmax statistics, complete; every other mode passes zeros)
+// (m_val, s_val: the online softmax only -- the row's softmax statistics, complete (several heads: of this lane's head); every
+// other mode passes zeros)
 template <typename T, int VEC, int NCH, int WMODE, int EXACT>
 __device__ __forceinline__ void finish_row(const SegParams& P, const Lanes<VEC, NCH, WMODE, EXACT>& L,
                                            const float (&acc)[NCH][VEC], int r, int row_len, float m_val = 0.f, float s_val = 0.f) {
     T* __restrict__ dst = reinterpret_cast<T*>(P.out) + (int64_t)r * P.ldo;
     const T* __restrict__ bias = reinterpret_cast<const T*>(P.bias);
     constexpr ModeTraits MT = mode_traits(WMODE);
-    if constexpr (MT.softmax) {
+    if constexpr (softmax_heads(WMODE) > 1) {
+        if ((lane_id() & ((P.C >> 2) - 1)) == 0 && L.act[0]) {        // the first lane of every head's group
+            P.m_out[(int64_t)r * P.H + L.hd[0]] = row_len > 0 ? m_val : 0.f;
+            P.s_out[(int64_t)r * P.H + L.hd[0]] = row_len > 0 ? s_val : 0.f;
+        }
+    } else if constexpr (MT.softmax) {
         if (lane_id() == 0) {                                // an empty row: m = 0, s = 0, as the statistics pass leaves it
             P.m_out[r] = row_len > 0 ? m_val : 0.f;
             P.s_out[r] = row_len > 0 ? s_val : 0.f;
@@ -262,6 +295,9 @@ struct ItemMeta {                    // what a wavefront leaves behind for the r
     int tail_row, tail_rs, tail_re;                   // tail_row < 0: no tail partial
     float head_m, head_s, tail_m, tail_s;             // W_GAT_DST_FUSED: (max, sum exp(. - max)) of the part's entries
 };
+// W_GAT_DST_FUSED_H2/4/8: the same pair PER HEAD.  In LDS a wave's two parts keep them in an array of their own
+// ([SEG_WAVES][2][SM_HEADS][2], allocated by these kernels only); in `carry` every partial row has SM_HEADS (m, s) slots
+constexpr int SM_HEADS = 8;
 
 struct CarryLayout {                 // global scratch of one launch (f32 words); n_wg = workgroups of the launch
     int64_t n_wg, n_span;
@@ -270,10 +306,11 @@ struct CarryLayout {                 // global scratch of one launch (f32 words)
         n_span = (n_wg + CHAIN_SPAN - 1) / CHAIN_SPAN;
     }
     // [counters: n_wg row counters, 2 n_span span counters][pad to 64 words]
-    // [ms: (max, sum exp) of every partial row below, 2 floats each: W_GAT_DST_FUSED][pad to 64 words]
+    // [ms: (max, sum exp) of every partial row below: W_GAT_DST_FUSED uses 2 floats per row, packed at the front of the region;
+    //      several heads SM_HEADS pairs per row, (m, s) of head h at 2 h][pad to 64 words]
     // [2 n_wg rows of F][2 n_span rows of F]
     __host__ __device__ int64_t counters() const { return ((n_wg + 2 * n_span + 63) / 64) * 64; }
-    __host__ __device__ int64_t ms_words() const { return ((2 * (2 * n_wg + 2 * n_span) + 63) / 64) * 64; }
+    __host__ __device__ int64_t ms_words() const { return ((2 * SM_HEADS * (2 * n_wg + 2 * n_span) + 63) / 64) * 64; }
     __host__ __device__ int64_t rows_off() const { return counters() + ms_words(); }
     __host__ __device__ int64_t elems(int64_t F) const { return rows_off() + (2 * n_wg + 2 * n_span) * F; }
 };
@@ -414,18 +451,57 @@ __device__ __forceinline__ void emit_partial(const SegParams& P, const Geo& L, c
 // merged against ITS maximum: first the (m, s) pairs of the chain (lane-parallel, a wave-wide max), then the rows in chain
 // order, each scaled by exp(m_k - M) -- the same fixed order as the plain sums above, so the result stays bitwise reproducible.
 // max of the m of n (m, s) pairs, `stride` floats apart
-__device__ __forceinline__ float chain_max(const float* ms, int64_t stride, int n) {
+// (HF > 1: `ms` points at this lane's head, the lanes of a head's group share the pairs out and fold inside the group)
+template <int HF>
+__device__ __forceinline__ float chain_max(const float* ms, int64_t stride, int n, int lph) {
     float m = -3.0e38f;
+    if constexpr (HF > 1) {
+        for (int j = lane_id() & (lph - 1); j < n; j += lph) m = fmaxf(m, ms[(int64_t)j * stride]);
+        return group_max(m, lph);
+    }
     for (int j = lane_id(); j < n; j += WAVE) m = fmaxf(m, ms[(int64_t)j * stride]);
     return wave_max(m);
 }
 // acc += sum_j exp(m_j - M) row_j,  s_acc += sum_j exp(m_j - M) s_j  over rows [0, n) of `base` (row stride `stride` floats),
 // their (m, s) pairs `ms_stride` floats apart; in row order, CHAIN_U rows in flight
 constexpr int SM_U = 4;             // partial rows in flight while a chain with statistics is merged
-template <int VEC, int NCH, class Geo>
+template <int VEC, int NCH, int HF, class Geo>
 __device__ __forceinline__ void add_rows_scaled(const Geo& L, float (&acc)[NCH][VEC], float& s_acc, const float* base, int64_t stride,
                                                 const float* ms, int64_t ms_stride, int n, float M) {
     const int lane = lane_id();
+    if constexpr (HF > 1) {
+        // every lane takes the pair of ITS head (`ms` points at it) and scales by its own exp(m_j - M): M, s_acc are per lane
+        for (int j = 0; j < n; j += SM_U) {
+            float v[SM_U][NCH][VEC];
+            float2 t[SM_U];
+#pragma unroll
+            for (int u = 0; u < SM_U; ++u) {
+                const int ju = min(j + u, n - 1);                         // past the end: the last row again, dropped
+                const float* src = base + (int64_t)ju * stride;
+                t[u] = *reinterpret_cast<const float2*>(ms + (int64_t)ju * ms_stride);
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) {
+                    if (L.act[c]) load_row<VEC, float>(src + L.foff[c], v[u][c]);
+                    else {
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k) v[u][c][k] = 0.f;
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < SM_U; ++u) {
+                if (j + u < n) {                                          // wave-uniform
+                    const float fj = expf(t[u].x - M);
+                    s_acc += t[u].y * fj;
+#pragma unroll
+                    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k) acc[c][k] = fmaf(fj, v[u][c][k], acc[c][k]);
+                }
+            }
+        }
+        return;
+    }
     for (int j0 = 0; j0 < n; j0 += WAVE) {
         const int nb = min(WAVE, n - j0);
         float f = 0.f, sv = 0.f;
@@ -463,16 +539,26 @@ __device__ __forceinline__ void add_rows_scaled(const Geo& L, float (&acc)[NCH][
     }
 }
 
-template <int VEC, int NCH, class Geo, class Fin>
+// HF: heads (1: W_GAT_DST_FUSED).  Several heads: pm / ps, the chain maxima and the sums are per-lane values -- those of the lane's
+// own head --, and every (m, s) pointer below is biased to that head's pair, so the same lines serve both forms
+template <int VEC, int NCH, int HF, class Geo, class Fin>
 __device__ __forceinline__ void emit_partial_sm(const SegParams& P, const Geo& L, const Fin& finish, float (&acc)[NCH][VEC],
                                                 int slot, int r, int rs, int re, float pm, float ps) {
     const int F = P.F;
     const int S = P.item * SEG_WAVES;
     const CarryLayout lay(P.n_items);
+    constexpr int MSW = HF > 1 ? 2 * SM_HEADS : 2;                      // floats of statistics per partial row
+    int lph = WAVE;
+    bool lead = lane_id() == 0;                                         // the lane that stores a pair
     int* cnt_row = reinterpret_cast<int*>(P.carry);
     int* cnt_span = cnt_row + lay.n_wg;
-    float* msb = P.carry + lay.counters();                              // [2 n_wg + 2 n_span][2]: (m, s) of every partial row
-    float* span_ms = msb + 2 * (2 * lay.n_wg);
+    float* msb = P.carry + lay.counters();                              // [2 n_wg + 2 n_span][MSW]: (m, s) of every partial row
+    if constexpr (HF > 1) {
+        lph = P.C >> 2;
+        lead = (lane_id() & (lph - 1)) == 0 && L.act[0];
+        msb += 2 * L.hd[0];
+    }
+    float* span_ms = msb + MSW * (2 * lay.n_wg);
     float* rows = P.carry + lay.rows_off();
     float* span_rows = rows + 2 * lay.n_wg * (int64_t)F;
     const int b = blockIdx.x;
@@ -481,16 +567,16 @@ __device__ __forceinline__ void emit_partial_sm(const SegParams& P, const Geo& L
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
         if (L.act[c]) store_row_sc1<VEC>(mine + L.foff[c], acc[c]);
-    if (lane_id() == 0) {
+    if (lead) {
         const float t2[2] = {pm, ps};
-        store_row_sc1<2>(msb + ((int64_t)b * 2 + slot) * 2, t2);
+        store_row_sc1<2>(msb + ((int64_t)b * 2 + slot) * MSW, t2);
     }
     drain_stores();
     float s_tot = 0.f;
     // the row's first partial (the tail of workgroup fi) scaled into acc / s_tot against the chain's maximum M
     auto take_tail = [&](float M) {
         const float* t = rows + ((int64_t)fi * 2 + 1) * F;
-        const float2 tms = *reinterpret_cast<const float2*>(msb + ((int64_t)fi * 2 + 1) * 2);
+        const float2 tms = *reinterpret_cast<const float2*>(msb + ((int64_t)fi * 2 + 1) * MSW);
         const float ft = expf(tms.x - M);
         s_tot = tms.y * ft;
 #pragma unroll
@@ -503,13 +589,13 @@ __device__ __forceinline__ void emit_partial_sm(const SegParams& P, const Geo& L
             for (int k = 0; k < VEC; ++k) acc[c][k] = v[k] * ft;
         }
     };
-    const float* tail_m = msb + ((int64_t)fi * 2 + 1) * 2;
+    const float* tail_m = msb + ((int64_t)fi * 2 + 1) * MSW;
     if (len <= CHAIN_SPAN) {
         if (!arrive_last(cnt_row + fi, len + 1)) return;
-        const float* hms = msb + (int64_t)(fi + 1) * 2 * 2;              // heads of fi + 1 .. li: slot 0 of consecutive workgroups
-        const float M = fmaxf(chain_max(hms, 4, len), *tail_m);
+        const float* hms = msb + (int64_t)(fi + 1) * 2 * MSW;            // heads of fi + 1 .. li: slot 0 of consecutive workgroups
+        const float M = fmaxf(chain_max<HF>(hms, 2 * MSW, len, lph), *tail_m);
         take_tail(M);
-        add_rows_scaled<VEC, NCH>(L, acc, s_tot, rows + (int64_t)(fi + 1) * 2 * F, 2 * (int64_t)F, hms, 4, len, M);
+        add_rows_scaled<VEC, NCH, HF>(L, acc, s_tot, rows + (int64_t)(fi + 1) * 2 * F, 2 * (int64_t)F, hms, 2 * MSW, len, M);
         finish(acc, r, re - rs, M, s_tot);
         return;
     }
@@ -519,42 +605,44 @@ __device__ __forceinline__ void emit_partial_sm(const SegParams& P, const Geo& L
         const int sl = fi >= g * CHAIN_SPAN ? 1 : 0;
         const int lo = max(fi + 1, g * CHAIN_SPAN), hi = min(li, g * CHAIN_SPAN + CHAIN_SPAN - 1);
         if (!arrive_last(cnt_span + 2 * g + sl, hi - lo + 1)) return;
-        const float* hms = msb + (int64_t)lo * 2 * 2;
-        const float Mg = chain_max(hms, 4, hi - lo + 1);
+        const float* hms = msb + (int64_t)lo * 2 * MSW;
+        const float Mg = chain_max<HF>(hms, 2 * MSW, hi - lo + 1, lph);
         float sg = 0.f;
 #pragma unroll
         for (int c = 0; c < NCH; ++c)
 #pragma unroll
             for (int k = 0; k < VEC; ++k) acc[c][k] = 0.f;
-        add_rows_scaled<VEC, NCH>(L, acc, sg, rows + (int64_t)lo * 2 * F, 2 * (int64_t)F, hms, 4, hi - lo + 1, Mg);
+        add_rows_scaled<VEC, NCH, HF>(L, acc, sg, rows + (int64_t)lo * 2 * F, 2 * (int64_t)F, hms, 2 * MSW, hi - lo + 1, Mg);
         float* sp = span_rows + ((int64_t)2 * g + sl) * F;
 #pragma unroll
         for (int c = 0; c < NCH; ++c)
             if (L.act[c]) store_row_sc1<VEC>(sp + L.foff[c], acc[c]);
-        if (lane_id() == 0) {
+        if (lead) {
             const float t2[2] = {Mg, sg};
-            store_row_sc1<2>(span_ms + ((int64_t)2 * g + sl) * 2, t2);
+            store_row_sc1<2>(span_ms + ((int64_t)2 * g + sl) * MSW, t2);
         }
         drain_stores();
     }
     if (!arrive_last(cnt_row + fi, 1 + (g1 - g0 + 1))) return;
     // span g0 holds the row in its slot 1 when the row began inside it, in slot 0 otherwise; every later span in slot 0
     const int64_t first = (int64_t)2 * g0 + (fi >= g0 * CHAIN_SPAN ? 1 : 0);
-    const float* later_ms = span_ms + (int64_t)2 * (g0 + 1) * 2;
-    float M = fmaxf(*tail_m, span_ms[first * 2]);
-    if (g1 > g0) M = fmaxf(M, chain_max(later_ms, 4, g1 - g0));
+    const float* later_ms = span_ms + (int64_t)2 * (g0 + 1) * MSW;
+    float M = fmaxf(*tail_m, span_ms[first * MSW]);
+    if (g1 > g0) M = fmaxf(M, chain_max<HF>(later_ms, 2 * MSW, g1 - g0, lph));
     take_tail(M);
-    add_rows_scaled<VEC, NCH>(L, acc, s_tot, span_rows + first * F, 0, span_ms + first * 2, 0, 1, M);
-    if (g1 > g0) add_rows_scaled<VEC, NCH>(L, acc, s_tot, span_rows + (int64_t)2 * (g0 + 1) * F, 2 * (int64_t)F, later_ms, 4, g1 - g0, M);
+    add_rows_scaled<VEC, NCH, HF>(L, acc, s_tot, span_rows + first * F, 0, span_ms + first * MSW, 0, 1, M);
+    if (g1 > g0) add_rows_scaled<VEC, NCH, HF>(L, acc, s_tot, span_rows + (int64_t)2 * (g0 + 1) * F, 2 * (int64_t)F, later_ms, 2 * MSW, g1 - g0, M);
     finish(acc, r, re - rs, M, s_tot);
 }
 
 // Every wave calls this when its item is done (inactive waves too).  `part`: [SEG_WAVES][2][ROWF] LDS rows, `meta`: [SEG_WAVES],
 // both filled in by the waves themselves (lane 0 writes the meta words at the moment they are known).
-// SM: the partial rows carry softmax statistics (W_GAT_DST_FUSED): merged with rescaling instead of added
-template <int VEC, int NCH, int ROWF, bool SM = false, class Geo, class Fin>
+// SMH > 0: the partial rows carry softmax statistics (W_GAT_DST_FUSED*, SMH heads): merged with rescaling instead of added.
+// Several heads: the parts' (m, s) per head lie in `hstat` ([SEG_WAVES][2][SM_HEADS][2]) and om / os are those of the lane's own head
+template <int VEC, int NCH, int ROWF, int SMH = 0, class Geo, class Fin>
 __device__ __forceinline__ void resolve_block(const SegParams& P, const Geo& L, const Fin& finish, float (*part)[2][ROWF],
-                                              ItemMeta* meta, int* arrived) {
+                                              ItemMeta* meta, int* arrived, const float* hstat = nullptr) {
+    constexpr bool SM = SMH > 0;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");                // the wave's partial rows and meta (LDS) before its arrival
     int old = 0;
     if (lane_id() == 0) old = __hip_atomic_fetch_add(arrived, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -568,7 +656,13 @@ __device__ __forceinline__ void resolve_block(const SegParams& P, const Geo& L, 
     auto load_part = [&](int w, int slot, bool add) {
         float f1 = 1.f, f2 = 1.f;
         if constexpr (SM) {
-            const float pm = slot ? meta[w].tail_m : meta[w].head_m, ps = slot ? meta[w].tail_s : meta[w].head_s;
+            float pm, ps;
+            if constexpr (SMH > 1) {
+                const float* q = hstat + ((w * 2 + slot) * SM_HEADS + L.hd[0]) * 2;
+                pm = q[0]; ps = q[1];
+            } else {
+                pm = slot ? meta[w].tail_m : meta[w].head_m; ps = slot ? meta[w].tail_s : meta[w].head_s;
+            }
             if (add) {
                 const float M = fmaxf(om, pm);
                 f1 = expf(om - M);
@@ -594,7 +688,7 @@ __device__ __forceinline__ void resolve_block(const SegParams& P, const Geo& L, 
         }
     };
     auto emit = [&](int slot) {
-        if constexpr (SM) emit_partial_sm<VEC, NCH>(P, L, finish, acc, slot, orow, ors, ore, om, os);
+        if constexpr (SM) emit_partial_sm<VEC, NCH, SMH>(P, L, finish, acc, slot, orow, ors, ore, om, os);
         else emit_partial<VEC, NCH>(P, L, finish, acc, slot, orow, ors, ore);
     };
     for (int w = 0; w < SEG_WAVES; ++w) {                               // (wave-uniform control flow: meta is read by every lane)
@@ -624,10 +718,38 @@ __device__ __forceinline__ void resolve_block(const SegParams& P, const Geo& L, 
     }
 }
 
-// one item: `part` = this wave's two LDS rows ([2][NCH VEC WAVE]: head partial, tail partial), `M` = what it leaves behind
+// The online softmax's step for one entry of score e, vr = this lane's columns of its gathered row.  One head: every lane holds the
+// same e and m_run, a new maximum is a wave-uniform branch.  Several heads (HF > 1): e, m_run, s_run are those of the lane's own
+// head, and heads reach new maxima at different entries -- which lanes rescale is a select under one wave-uniform "any lane" test
+template <int HF, int VEC>
+__device__ __forceinline__ void softmax_entry(float e, const float (&vr)[VEC], float (&acc)[VEC], float& m_run, float& s_run) {
+    if constexpr (HF > 1) {
+        const bool up = e > m_run;
+        if (__any(up)) {
+            const float rsc = up ? expf(m_run - e) : 1.f;
+            s_run *= rsc;
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) acc[q] *= rsc;
+            m_run = up ? e : m_run;
+        }
+    } else if (e > m_run) {
+        const float rsc = expf(m_run - e);
+        s_run *= rsc;
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) acc[q] *= rsc;
+        m_run = e;
+    }
+    const float we = expf(e - m_run);
+    s_run += we;
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) acc[q] = fmaf(we, vr[q], acc[q]);
+}
+
+// one item: `part` = this wave's two LDS rows ([2][NCH VEC WAVE]: head partial, tail partial), `M` = what it leaves behind;
+// `hstat` (W_GAT_DST_FUSED_H2/4/8 only) = this wave's [2][SM_HEADS][2]: (max, sum exp) per head of the two parts
 template <typename T, int VEC, int NCH, int WMODE, int EXACT>
 __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC, NCH, WMODE, EXACT>& L, const int item,
-                                            float* __restrict__ part, ItemMeta* __restrict__ M) {
+                                            float* __restrict__ part, ItemMeta* __restrict__ M, float* __restrict__ hstat = nullptr) {
     constexpr int U = inflight<VEC, NCH>::value;
     constexpr int ROWF = NCH * VEC * WAVE;
     const int lane = lane_id();
@@ -672,15 +794,23 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
     // gathered and parked in LDS, ran the launch 6-7 % slower and gave back what the statistics pass had cost).  The open row
     // keeps (m_run, s_run) = (max so far, sum of exp(e - m_run)); a new maximum rescales the accumulators (rare after a row's
     // first few entries: a wave-uniform branch).
-    constexpr bool SMX = WMODE == W_GAT_DST_FUSED;
+    // Several heads (HF = 2 / 4 / 8): a head is the group of hlanes = C / 4 lanes that hold its columns, the dot is summed inside the
+    // group (group_sum), and (m_run, s_run) are those of the lane's own head.  Heads reach new maxima at different entries, so the
+    // rescale is a per-lane select under one wave-uniform "any lane" test; lanes past F (H C < 256) gather zeros, form groups of
+    // their own and store nothing.
+    constexpr int HF = softmax_heads(WMODE);
+    constexpr bool SMX = HF > 0;
+    const int hlanes = HF > 1 ? (P.C >> 2) : WAVE;
     float m_run = -3.0e38f, s_run = 0.f;
     float at_src[VEC];
 #pragma unroll
     for (int q = 0; q < VEC; ++q) at_src[q] = 0.f;
-    if constexpr (SMX) {
+    if constexpr (HF > 1) {
+        if (L.act[0]) load_row<VEC, float>(P.att + (int64_t)(L.hd[0] + 1) * P.C + L.foff[0], at_src);     // att[h, C + (column in h)]
+    } else if constexpr (SMX) {
         if (L.act[0]) load_row<VEC, float>(P.att + P.C + L.foff[0], at_src);
     }
-    (void)m_run; (void)s_run; (void)at_src;
+    (void)m_run; (void)s_run; (void)at_src; (void)hlanes;
     float hr[VEC];                       // W_GAT_SRC_FUSED: this lane's columns of the open row's own features (h_j)
 #pragma unroll
     for (int q = 0; q < VEC; ++q) hr[q] = 0.f;
@@ -691,7 +821,10 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
             m_run = -3.0e38f;
             s_run = 0.f;
 #pragma unroll
-            for (int c = 0; c < NCH; ++c) { rs_a[c] = P.a_dst[min(r, N - 1)]; rs_m[c] = 0.f; rs_i[c] = 0.f; }
+            for (int c = 0; c < NCH; ++c) {
+                rs_a[c] = HF > 1 ? P.a_dst[(int64_t)min(r, N - 1) * HF + L.hd[c]] : P.a_dst[min(r, N - 1)];
+                rs_m[c] = 0.f; rs_i[c] = 0.f;
+            }
             return;
         }
         if (WMODE == W_GAT_DST || WMODE == W_GAT_DST_PRE) {
@@ -720,14 +853,24 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
         for (int c = 0; c < NCH; ++c)
             if (L.act[c]) store_row<VEC, float>(dst + L.foff[c], acc[c]);
     };
+    // several heads: the statistics of the part in `slot` go to `hstat`, from the first lane of every head's group
+    auto put_stats = [&](int slot) {
+        if constexpr (HF > 1) {
+            if ((lane & (hlanes - 1)) == 0 && L.act[0]) {
+                float* q = hstat + (slot * SM_HEADS + L.hd[0]) * 2;
+                q[0] = m_run; q[1] = s_run;
+            }
+        }
+    };
     // row r is complete (its last entry has been accumulated, or it is empty)
     auto close_row = [&]() {
         if (head) {
             write_carry(0);
             if (lane == 0) {
                 M->head_row = r; M->head_rs = row_start; M->head_re = row_end; M->head_closed = 1;
-                if constexpr (SMX) { M->head_m = m_run; M->head_s = s_run; }
+                if constexpr (HF == 1) { M->head_m = m_run; M->head_s = s_run; }
             }
+            if constexpr (HF > 1) put_stats(0);
             head = false;
         } else {
             finish_row<T, VEC, NCH, WMODE, EXACT>(P, L, acc, r, row_end - row_start, m_run, s_run);
@@ -841,24 +984,13 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
                     for (int q = 0; q < VEC; ++q) dt[u] = fmaf(v[u][0][q], at_src[q], dt[u]);
                 }
 #pragma unroll
-                for (int u = 0; u < U; ++u) dt[u] = wave_sum_dpp(dt[u]);
+                for (int u = 0; u < U; ++u) dt[u] = HF > 1 ? group_sum(dt[u], hlanes) : wave_sum_dpp(dt[u]);
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const int k = kb + j + u;
                     while (k == row_end) close_row();
                     const float z = rs_a[0] + dt[u];
-                    const float e = z > 0.f ? z : z * P.slope;
-                    if (e > m_run) {                      // wave-uniform: every lane holds the same e and m_run
-                        const float rsc = expf(m_run - e);
-                        s_run *= rsc;
-#pragma unroll
-                        for (int q = 0; q < VEC; ++q) acc[0][q] *= rsc;
-                        m_run = e;
-                    }
-                    const float we = expf(e - m_run);
-                    s_run += we;
-#pragma unroll
-                    for (int q = 0; q < VEC; ++q) acc[0][q] = fmaf(we, v[u][0][q], acc[0][q]);
+                    softmax_entry<HF, VEC>(z > 0.f ? z : z * P.slope, v[u][0], acc[0], m_run, s_run);
                 }
                 continue;
             }
@@ -950,20 +1082,9 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
                 float dt = 0.f;
 #pragma unroll
                 for (int q = 0; q < VEC; ++q) dt = fmaf(v[0][q], at_src[q], dt);
-                dt = wave_sum_dpp(dt);
+                dt = HF > 1 ? group_sum(dt, hlanes) : wave_sum_dpp(dt);
                 const float z = rs_a[0] + dt;
-                const float e = z > 0.f ? z : z * P.slope;
-                if (e > m_run) {
-                    const float rsc = expf(m_run - e);
-                    s_run *= rsc;
-#pragma unroll
-                    for (int q = 0; q < VEC; ++q) acc[0][q] *= rsc;
-                    m_run = e;
-                }
-                const float we = expf(e - m_run);
-                s_run += we;
-#pragma unroll
-                for (int q = 0; q < VEC; ++q) acc[0][q] = fmaf(we, v[0][q], acc[0][q]);
+                softmax_entry<HF, VEC>(z > 0.f ? z : z * P.slope, v[0], acc[0], m_run, s_run);
                 continue;
             }
             float ws = (WMODE == W_ARRAY || WMODE == W_GAT_SRC_PRE || WMODE == W_GAT_SRC_FUSED || WMODE == W_GAT_DST_PRE) ? bcast_f(wv, j) : 1.f;
@@ -1062,23 +1183,28 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
         write_carry(0);                                  // one row spans the whole item
         if (lane == 0) {
             M->head_row = r; M->head_rs = row_start; M->head_re = row_end; M->head_closed = 0;
-            if constexpr (SMX) { M->head_m = m_run; M->head_s = s_run; }
+            if constexpr (HF == 1) { M->head_m = m_run; M->head_s = s_run; }
         }
+        if constexpr (HF > 1) put_stats(0);
     } else {
         write_carry(1);                                  // row continues in the next item
         if (lane == 0) {
             M->tail_row = r; M->tail_rs = row_start; M->tail_re = row_end;
-            if constexpr (SMX) { M->tail_m = m_run; M->tail_s = s_run; }
+            if constexpr (HF == 1) { M->tail_m = m_run; M->tail_s = s_run; }
         }
+        if constexpr (HF > 1) put_stats(1);
     }
 }
 
 // the HBM-bound kernels of the headline (one 16-byte chunk per lane, no GAT weights) must keep 8 waves per SIMD: <= 64 VGPRs
-// (W_GAT_DST_FUSED: 6 waves per SIMD -- 80 VGPRs; left alone the allocator takes 93 for the chain resolution's sake, 5 waves)
+// (W_GAT_DST_FUSED: bounded at 6 waves per SIMD, i.e. at most 80 VGPRs; the compiler reports 69 / 70 / 71 and an occupancy of 7.
+// W_GAT_DST_FUSED_H2/4/8: bounded at 5 waves -- 90 / 91 VGPRs, no scratch.  Their scores, maxima and sums are per-lane values where
+// the one-head mode keeps wave-uniform ones in SGPRs; under the 6-wave bound of 80 registers they spill 48 to 52 bytes per lane)
 template <int VEC, int NCH, int WMODE, int EXACT> struct seg_min_waves {
     // (EXACT == 2: the variant that also writes the finished rows' power-of-two scales -- 70 registers, 7 waves; measured at C4
     // against the 8-wave one: no difference in the launch, EXPERIMENTS A34)
     static constexpr int value = (NCH == 1 && !mode_traits(WMODE).per_head && EXACT) ? (EXACT == 2 ? 7 : 8)
+                               : (NCH == 1 && softmax_heads(WMODE) > 1) ? 5
                                : (NCH == 1 && mode_traits(WMODE).softmax) ? 6 : 1;
 };
 
@@ -1096,11 +1222,17 @@ segsum_kernel(SegParams P) {
     const int item = uniform_i(blockIdx.x * SEG_WAVES + wave);
     Lanes<VEC, NCH, WMODE, EXACT> L;
     L.init(P);
-    if (item < P.n_items) segsum_item<T, VEC, NCH, WMODE, EXACT>(P, L, item, &s_part[wave][0][0], s_meta + wave);
+    float *hstat = nullptr, *hstat_w = nullptr;             // several softmax heads: the parts' (max, sum exp) per head, these kernels' own LDS
+    if constexpr (softmax_heads(WMODE) > 1) {
+        __shared__ float s_hstat[SEG_WAVES][2][SM_HEADS][2];
+        hstat = &s_hstat[0][0][0][0];
+        hstat_w = &s_hstat[wave][0][0][0];
+    }
+    if (item < P.n_items) segsum_item<T, VEC, NCH, WMODE, EXACT>(P, L, item, &s_part[wave][0][0], s_meta + wave, hstat_w);
     auto finish = [&](const float (&acc)[NCH][VEC], int r, int row_len, float m_, float s_) {
         finish_row<T, VEC, NCH, WMODE, EXACT>(P, L, acc, r, row_len, m_, s_);
     };
-    resolve_block<VEC, NCH, ROWF, mode_traits(WMODE).softmax>(P, L, finish, s_part, s_meta, &s_arrived);
+    resolve_block<VEC, NCH, ROWF, softmax_heads(WMODE)>(P, L, finish, s_part, s_meta, &s_arrived, hstat);
 }
 
 // Narrow rows (F <= 32 VEC: hidden = 128 or 64 in f32, the reference's own model width): one row is only
@@ -1275,6 +1407,7 @@ static int launch_one(const SegParams& P, hipStream_t stream) {
         return check_launch("npi_segsum");
     } else {
         if (mode_traits(WMODE).fused_heads > 0) set_error("npi_gat_backward_fused: needs heads * out_channels <= 256");
+        else if (softmax_heads(WMODE) > 1) set_error("npi_gat_aggregate_fused_heads: needs heads * out_channels <= 256");
         else if (mode_traits(WMODE).softmax) set_error("npi_gat_aggregate_fused: needs one head of at most 256 channels");
         else set_error("npi_segsum: no kernel for weight mode %d on these rows", WMODE);
         return NPI_ERR_ARG;
@@ -1305,6 +1438,9 @@ static int launch_segsum(const SegParams& P, int wmode, hipStream_t stream) {
         NPI_SEG_MODE(W_GAT_DST);
         NPI_SEG_MODE(W_GAT_DST_PRE);
         NPI_SEG_MODE(W_GAT_DST_FUSED);
+        NPI_SEG_MODE(W_GAT_DST_FUSED_H2);
+        NPI_SEG_MODE(W_GAT_DST_FUSED_H4);
+        NPI_SEG_MODE(W_GAT_DST_FUSED_H8);
         NPI_SEG_MODE(W_GAT_SRC);
         NPI_SEG_MODE(W_GAT_SRC_PRE);
         NPI_SEG_MODE(W_GAT_SRC_FUSED);

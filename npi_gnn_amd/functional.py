@@ -1420,12 +1420,14 @@ def gat_aggregate_scores(side: CSRSide, table, table2, C, scores, m, s, bias=Non
 
 
 def gat_aggregate_fused(side: CSRSide, table, table2, C, a_dst, att2, slope, bias=None, out=None, relu: bool = False,
-                        scales_out: Optional[torch.Tensor] = None):
-    """One head of at most 256 channels: ``(out, m, s)`` -- the forward aggregation together with the softmax statistics of every
-    row, in ONE launch (``npi_gat_aggregate_fused``): an online softmax whose scores' source half is recomputed from the gathered
-    rows (``att2``: the layer's ``[1, 2C]`` attention vector) -- no statistics pass, no per-entry score array, no gather of
-    ``a_src``.  ``a_dst`` ``[n_rows]``; ``table2``: second part of a two-part table.  ``scales_out`` ``[n_rows]`` (256 channels): also
-    the power-of-two scale of every stored row (bias and ReLU applied) -- the ``x_scales`` of the next layer's projection."""
+                        scales_out: Optional[torch.Tensor] = None, H: int = 1):
+    """One head of at most 256 channels, or ``H`` = 2 / 4 / 8 heads on the shapes of ``gat_fused_shape``: ``(out, m, s)`` -- the
+    forward aggregation together with the softmax statistics ``[n_rows, H]`` of every row, in ONE launch
+    (``npi_gat_aggregate_fused_heads``): an online softmax whose scores' source half is recomputed from the gathered
+    rows (``att2``: the layer's ``[H, 2C]`` attention vectors) -- no statistics pass, no per-entry score array, no gather of
+    ``a_src``.  ``a_dst`` ``[n_rows, H]``; ``table2``: second part of a two-part table.  ``scales_out`` ``[n_rows]`` (one head of 256
+    channels): also the power-of-two scale of every stored row (bias and ReLU applied) -- the ``x_scales`` of the next layer's
+    projection."""
     dev = table.device
     table = _f32c(table, "table")
     if table2 is not None:
@@ -1433,18 +1435,19 @@ def gat_aggregate_fused(side: CSRSide, table, table2, C, a_dst, att2, slope, bia
         if table2.stride(0) != table.stride(0):
             raise ValueError("the two parts of the table must share the row pitch")
     if out is None:
-        out = torch.empty((side.n_rows, C), dtype=torch.float32, device=dev)
+        out = torch.empty((side.n_rows, H * C), dtype=torch.float32, device=dev)
     else:
-        _check_out(out, side.n_rows, C, table, "gat_aggregate_fused")
-    m = torch.empty((side.n_rows, 1), dtype=torch.float32, device=dev)
-    s = torch.empty((side.n_rows, 1), dtype=torch.float32, device=dev)
+        _check_out(out, side.n_rows, H * C, table, "gat_aggregate_fused")
+    m = torch.empty((side.n_rows, H), dtype=torch.float32, device=dev)
+    s = torch.empty((side.n_rows, H), dtype=torch.float32, device=dev)
     with _tag_events("gat_fwd_aggregate", dev):
-        check(load().npi_gat_aggregate_fused(ptr(side.rowptr), ptr(side.col), ptr(side.rowidx), ptr(side.item_row), side.item,
-                                                 side.n_rows, side.nnz_max, ptr(table), table.stride(0), ptr(table2),
-                                                 table.size(0) if table2 is not None else 0, ptr(out), out.stride(0), C,
-                                                 ptr(a_dst.contiguous()), ptr(_f32c(att2.reshape(-1), "att")), float(slope), ptr(bias),
-                                                 1 if relu else 0, ptr(m), ptr(s), ptr(side.carry(C)), ptr(scales_out), stream_ptr(dev)),
-              "npi_gat_aggregate_fused")
+        check(load().npi_gat_aggregate_fused_heads(ptr(side.rowptr), ptr(side.col), ptr(side.rowidx), ptr(side.item_row), side.item,
+                                                   side.n_rows, side.nnz_max, ptr(table), table.stride(0), ptr(table2),
+                                                   table.size(0) if table2 is not None else 0, ptr(out), out.stride(0), H, C,
+                                                   ptr(a_dst.contiguous()), ptr(_f32c(att2.reshape(-1), "att")), float(slope), ptr(bias),
+                                                   1 if relu else 0, ptr(m), ptr(s), ptr(side.carry(H * C)), ptr(scales_out),
+                                                   stream_ptr(dev)),
+              "npi_gat_aggregate_fused_heads")
     return out, m, s
 
 
@@ -1581,6 +1584,9 @@ class _GatConvFn(torch.autograd.Function):
             if want_scales and C == 256:
                 out_scales = torch.empty(d.n_rows, dtype=torch.float32, device=x.device)
             out, m, s = gat_aggregate_fused(d, hfeat, None, C, a_dst, att2, slope, bias=bias, relu=relu, scales_out=out_scales)
+        elif H > 1 and gat_fused_shape(H, C) and d.nnz_max > 0 and sch.gat_fused_stats:
+            # 2 / 4 / 8 heads: the same launch, a head per group of C / 4 lanes (statistics per head, ReLU in its epilogue)
+            out, m, s = gat_aggregate_fused(d, hfeat, None, C, a_dst, att2, slope, bias=bias, relu=relu, H=H)
         elif H == 1 and C % 4 == 0 and d.nnz_max > 0:
             # the statistics pass leaves the score of every entry; the aggregation reads it back (one coalesced load per
             # 64 entries) instead of gathering a_src[j] per entry and redoing the leaky_relu
@@ -2088,6 +2094,8 @@ class _GatBipartiteFn(torch.autograd.Function):
                 out = torch.relu_(out)
         elif H == 1 and C % 4 == 0 and C <= 256 and sch.gat_fused_stats:
             out, m, s = gat_aggregate_fused(d, h_src, None, C, a_dst, att2, slope, bias=bias, relu=relu)
+        elif H > 1 and gat_fused_shape(H, C) and sch.gat_fused_stats:
+            out, m, s = gat_aggregate_fused(d, h_src, None, C, a_dst, att2, slope, bias=bias, relu=relu, H=H)
         else:
             m, s = gat_softmax_stats(d, a_dst, a_src, H, slope)
             out = _gat_aggregate(graph, d, h_src, H, C, a_dst, a_src, m, s, slope, False, bias=bias)

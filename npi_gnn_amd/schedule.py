@@ -40,9 +40,11 @@ class Schedule:
     #: one-head GATConv forward: a_dst / a_src of every node from the accumulators of h = x W in the GEMM's store epilogue
     #: instead of a pass over h (shapes one column tile covers: 128 or 256 output channels)
     gat_scores_epilogue: bool = True
-    #: one-head GATConv forward (<= 256 channels): the softmax statistics INSIDE the aggregation launch (every item computes its
-    #: entries' scores; parts of cut rows are merged with rescaling: ``npi_gat_aggregate_fused``) instead of a statistics pass
-    #: that leaves every entry's score for the aggregation to read back
+    #: GATConv forward, one head (<= 256 channels) or 2 / 4 / 8 heads on the shapes of ``functional.gat_fused_shape``: the softmax
+    #: statistics INSIDE the aggregation launch (every item computes its entries' scores; parts of cut rows are merged with
+    #: rescaling: ``npi_gat_aggregate_fused`` / ``npi_gat_aggregate_fused_heads``) instead of a statistics pass in front of it
+    #: (one head: the pass leaves every entry's score for the aggregation to read back; several heads: ``W_GAT_DST`` gathers
+    #: ``a_src`` per entry and the ReLU is a pass of its own)
     gat_fused_stats: bool = True
     #: one-head GATConv backward (rank-2 path, two streams): the by-source row sum of dz on the side stream, in front of the
     #: by-target one and beside the dW GEMM, instead of on the launch stream in front of dW
