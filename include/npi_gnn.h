@@ -794,6 +794,65 @@ int64_t npi_sample_coalesce_workspace_bytes(int64_t E);
 int npi_sample_coalesce(const int32_t* src_l, const int32_t* dst_l, const int32_t* eid, int64_t E, int64_t U, int64_t* edge_src,
                         int64_t* edge_dst, int64_t* e_id, int32_t* info, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Negative sampling: the pairs a link-prediction loss is taken against.  Replaces the reference's offline loop
+ * `src/generate_edgelist.py:108-139` (draw a uniform ncRNA and a uniform protein; redraw if the pair is a positive or was already
+ * drawn; stop at as many negatives as positives) and PyG 1.4.2 `torch_geometric.utils.negative_sampling` /
+ * `structured_negative_sampling`, which run through Python `random.sample` and `isin` on the CPU.
+ *
+ * Input of both kernels: the by-target CSR WITH SORTED COLUMNS of the edge list as it is (npi_csr_build_ex with key = edge_index[1],
+ * val = edge_index[0], add_self_loops = 0, build_flags = NPI_CSR_SORT_COLUMNS, NPI_CSR_DROP_EQUAL not set): rowptr[n_dst+1],
+ * col[nnz] = source ids, ASCENDING within a row -- the rows MUST be sorted: membership is a binary search of row d for s.  "Edge"
+ * means a column of the edge list as it is: no self loop is added or removed, parallel edges count once.
+ *
+ * THE TWO RULES.  All arithmetic in wrapping uint64; mix64 is the sampler's (above):
+ *     mix64(z)    : z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *     G = 0x9E3779B97F4A7C15,  C = 0xD6E8FEB86659FD93
+ *     mulhi(a, n) = (a * n) >> 64 of the 128-bit product: a 64-bit word to [0, n) with a bias below n / 2^64
+ *     key         : a signed 64-bit integer (the Python side passes sampler.epoch_seed(seed, draw))
+ *
+ * RULE P -- distinct non-edge pairs (the reference's loop driven by a counter-based generator):
+ *     base  = mix64(mix64(key) + G)
+ *     src_i = mulhi(mix64(base + G * (2i + 1)), n_src)        i = 0, 1, 2, ...
+ *     dst_i = mulhi(mix64(base + G * (2i + 2)), n_dst)
+ * Candidate i is VALID if (src_i, dst_i) is not an edge and -- with no_loops -- src_i != dst_i.  The result is the first M valid
+ * candidates that differ from every earlier valid candidate, in order of i: a uniform draw without replacement from the non-edges,
+ * a pure function of (key, graph, M, no_loops) -- independent of launch geometry, of timing and of how many candidates the caller
+ * looks at per round.
+ *
+ * RULE T -- corrupt the target of given sources (PyG's structured_negative_sampling; slots are independent, equal results in
+ * different slots are allowed, as they are there):
+ *     base_k = mix64( mix64(mix64(key) + 2 * G)  ^  (k * C) )            slot k = 0 .. K-1
+ *     d_k,t  = mulhi(mix64(base_k + G * (t + 1)), n_dst)                  t = 0 .. tries-1
+ * out[k] = the first d_k,t for which (src[k], d_k,t) is not an edge; none (the source is joined to every target, or tries ran out):
+ * -1 and NPI_STATUS_NO_NEGATIVE.  A src[k] outside [0, n_src) is never dereferenced: -1 and NPI_STATUS_BAD_SOURCE_ID.
+ *
+ *   npi_negative_candidates : candidates first .. first + W - 1 of Rule P: cand_src[j], cand_dst[j] (int32) = candidate first + j,
+ *                             or (-1, -1) when it is invalid.  flags bit 0: no_loops.
+ *   npi_negative_targets    : Rule T: out_dst[K] (int64).  status (int32 device word, may be NULL) is cleared first, then OR-ed
+ *                             into.  No host read and no allocation: it may run inside a stream capture.
+ *   npi_negative_distinct   : the first M distinct valid pairs of a window of W candidates (npi_negative_candidates' output for
+ *                             first = 0): two stable radix sorts on the bits the id bounds need (target, then source with one more
+ *                             bit that sorts the invalid candidates last, carrying the position), run heads -- the earliest
+ *                             occurrence of each pair -- set keep[position], an exclusive scan of keep in position order, and the
+ *                             compaction: out_src / out_dst[0 .. min(M, info[0])) (int64) in position order.  info[0] = the number
+ *                             of distinct valid pairs in the window; info[1] = the number of candidates consumed up to and including
+ *                             the M-th kept one, 0 if the window holds fewer than M (the caller then runs a window twice as long,
+ *                             from candidate 0).  workspace: npi_negative_distinct_workspace_bytes(W) bytes, 16-byte aligned.
+ * All allocate nothing and keep no state.  Bad arguments -- a null pointer, a negative size, W / K or an id bound >= 2^31 - 1 (or an
+ * id bound below 1), tries < 1, a misaligned or short workspace -- are refused with -1 before anything is launched; W == 0 / K == 0
+ * returns 0 without a launch.
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_STATUS_NO_NEGATIVE 64
+#define NPI_STATUS_BAD_SOURCE_ID 128
+int npi_negative_candidates(const int32_t* rowptr, const int32_t* col, int64_t n_dst, int64_t n_src, int64_t key, int64_t first,
+                            int64_t W, int flags, int32_t* cand_src, int32_t* cand_dst, void* stream);
+int npi_negative_targets(const int32_t* rowptr, const int32_t* col, int64_t n_dst, int64_t n_src, const int64_t* src, int64_t K,
+                         int64_t key, int64_t tries, int64_t* out_dst, int32_t* status, void* stream);
+int64_t npi_negative_distinct_workspace_bytes(int64_t W);
+int npi_negative_distinct(const int32_t* cand_src, const int32_t* cand_dst, int64_t W, int64_t n_src, int64_t n_dst, int64_t M,
+                          int64_t* out_src, int64_t* out_dst, int32_t* info, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Evaluation loop (reference src/methods.py:87-105 compares one element per Python
  * iteration, one device sync each).  counts[4] += [TP, FN, TN, FP] for pred = first arg-max of scores[i, 0..C):
  * pred 1 & y 1 -> TP, pred 1 & y 0 -> FP, pred 0 & y 1 -> FN, anything else -> TN (the reference's else

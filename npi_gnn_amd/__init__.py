@@ -13,6 +13,8 @@ from .nn import GATConv, GCNConv, SAGEConv  # noqa: F401
 from .schedule import Schedule  # noqa: F401
 from .graphed import GraphedStack  # noqa: F401
 from .sampler import Block, DataFlow, NeighborSampler, SubgraphBatch  # noqa: F401
+from .negative import NegativeSampler, negative_sampling, structured_negative_sampling  # noqa: F401
 
 __all__ = ["CSRGraph", "GraphBatch", "as_graph", "set_debug", "GCNNorm", "gat_conv", "gcn_conv", "sage_conv", "segsum",
-           "GATConv", "GCNConv", "SAGEConv", "Schedule", "GraphedStack", "NeighborSampler", "DataFlow", "Block", "SubgraphBatch", "NpiError", "load", "LIB_PATH"]
+           "GATConv", "GCNConv", "SAGEConv", "Schedule", "GraphedStack", "NeighborSampler", "DataFlow", "Block", "SubgraphBatch", "NegativeSampler", "negative_sampling",
+           "structured_negative_sampling", "NpiError", "load", "LIB_PATH"]

@@ -25,6 +25,8 @@ NPI_PREPARE_F16X2 = 4             # npi_linear_prepare(which | this): the fp16 x
 NPI_STATUS_BAD_ROW_ID = 8         # status bit of npi_rows_gather: a row id outside the source table
 NPI_STATUS_BAD_TARGET_ID = 16     # status bit of npi_sample_counts / npi_sample_union: a target (batch) id outside [0, N)
 NPI_STATUS_BAD_SAMPLE_SIZES = 32  # status bit of npi_sample_select / _relabel / _union: offsets / counts / capacity of another call
+NPI_STATUS_NO_NEGATIVE = 64       # status bit of npi_negative_targets: a slot whose tries all hit edges (it holds -1)
+NPI_STATUS_BAD_SOURCE_ID = 128    # status bit of npi_negative_targets: a source id outside [0, n_src) (its slot holds -1)
 NPI_HUB_MAX = 128                # hubs per plan (npi_hub_plan; mask words of NPI_HUB_MAX / 32 per source row)
 
 
@@ -149,6 +151,10 @@ PROTOTYPES = {
     "npi_sample_union": (c_int, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "npi_sample_coalesce_workspace_bytes": (_I, [_I]),
     "npi_sample_coalesce": (c_int, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
+    "npi_negative_candidates": (c_int, [_P, _P, _I, _I, _I, _I, _I, c_int, _P, _P, _P]),
+    "npi_negative_targets": (c_int, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
+    "npi_negative_distinct_workspace_bytes": (_I, [_I]),
+    "npi_negative_distinct": (c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
 }
 
 _lib = None

@@ -403,6 +403,55 @@ __global__ void coalesce_compact_kernel(const uint32_t* __restrict__ src_s, cons
     e_id[q] = m;
 }
 
+// ---- the first M distinct valid pairs of a window of negative candidates (npi_negative_distinct; the candidates: negative.hip) ----------
+// Replaces the `if (a, b) in positives or (a, b) in negatives: continue` of src/generate_edgelist.py:108-139 for the "already drawn"
+// half.  The same LSD scheme as above -- by target, then by source, val = the candidate's position -- with one more key bit in the
+// second sort that puts the invalid candidates ((-1, -1), or an id out of range) behind every valid one.  The sorts are stable over
+// the position, so the head of a run of equal pairs is its EARLIEST occurrence: it alone sets keep[position].
+__global__ void negative_keys_kernel(const int32_t* __restrict__ cand_dst, int64_t W, int64_t n_dst, uint32_t* __restrict__ keys,
+                                     int32_t* __restrict__ vals) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= W) return;
+    const int32_t d = cand_dst[i];
+    keys[i] = (d < 0 || d >= n_dst) ? 0u : (uint32_t)d;
+    vals[i] = (int32_t)i;
+}
+__global__ void negative_rekey_kernel(const int32_t* __restrict__ cand_src, const int32_t* __restrict__ cand_dst,
+                                      const int32_t* __restrict__ vals, int64_t W, int64_t n_src, int64_t n_dst, uint32_t invalid,
+                                      uint32_t* __restrict__ keys) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= W) return;
+    const int32_t i = vals[p], s = cand_src[i], d = cand_dst[i];
+    keys[p] = (s < 0 || s >= n_src || d < 0 || d >= n_dst) ? invalid : (uint32_t)s;
+}
+// keep / kept (both ALL ZERO on entry): 1 at the position of every first occurrence of a valid pair
+__global__ void negative_heads_kernel(const uint32_t* __restrict__ src_s, const int32_t* __restrict__ vals, const int32_t* __restrict__ cand_dst,
+                                      int64_t W, uint32_t invalid, int32_t* __restrict__ keep, int32_t* __restrict__ kept) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= W) return;
+    const uint32_t s = src_s[p];
+    if (s == invalid) return;
+    const int32_t i = vals[p];
+    if (p == 0 || src_s[p - 1] != s || cand_dst[vals[p - 1]] != cand_dst[i]) {
+        keep[i] = 1;
+        kept[i] = 1;
+    }
+}
+// pos = the exclusive scan of keep in position order; info (ALL ZERO on entry) = (distinct valid pairs, candidates consumed by the M-th)
+__global__ void negative_compact_kernel(const int32_t* __restrict__ cand_src, const int32_t* __restrict__ cand_dst,
+                                        const int32_t* __restrict__ pos, const int32_t* __restrict__ kept, int64_t W, int64_t M,
+                                        int64_t* __restrict__ out_src, int64_t* __restrict__ out_dst, int32_t* __restrict__ info) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= W) return;
+    const int64_t q = pos[i];                                    // q <= i
+    const bool on = kept[i] != 0;
+    if (i == W - 1) info[0] = (int32_t)(q + (on ? 1 : 0));
+    if (!on || q >= M) return;
+    out_src[q] = cand_src[i];
+    out_dst[q] = cand_dst[i];
+    if (q == M - 1) info[1] = (int32_t)(i + 1);
+}
+
 // ---- TopKPooling selection for graphs of ANY size (pool.hip sorts a graph's scores in LDS: up to 16,384 nodes) -----------
 // Two stable radix sorts of the whole batch: by score (descending; the sort is stable over the node index, so equal scores
 // keep the lower index first -- torch.sort(descending=True, stable) order, as the LDS kernel), then by graph id: position
@@ -570,6 +619,59 @@ extern "C" int npi_sample_coalesce(const int32_t* src_l, const int32_t* dst_l, c
     scan_add_kernel<<<(unsigned)ntiles, SCAN_THREADS, 0, stream>>>(head, E, counts);
     coalesce_compact_kernel<<<eb, 256, 0, stream>>>(keys_a, dst_s, vals_a, head, eid, E, edge_src, edge_dst, e_id, info);
     return check_launch("npi_sample_coalesce");
+}
+
+extern "C" int64_t npi_negative_distinct_workspace_bytes(int64_t W) {
+    if (W < 0 || W >= (int64_t)0x7fffffff) return -1;
+    return sort_layout(W, 0).total;
+}
+
+extern "C" int npi_negative_distinct(const int32_t* cand_src, const int32_t* cand_dst, int64_t W, int64_t n_src, int64_t n_dst, int64_t M,
+                                     int64_t* out_src, int64_t* out_dst, int32_t* info, void* workspace, int64_t workspace_bytes,
+                                     void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    NPI_REQUIRE(W >= 0 && W < (int64_t)0x7fffffff && M >= 0, "npi_negative_distinct: bad size");
+    NPI_REQUIRE(n_src >= 1 && n_src < (int64_t)0x7fffffff && n_dst >= 1 && n_dst < (int64_t)0x7fffffff,
+                "npi_negative_distinct: bad id bound");
+    NPI_REQUIRE(info, "npi_negative_distinct: null pointer");
+    if (W == 0) return NPI_OK;
+    NPI_REQUIRE(cand_src && cand_dst && workspace && (M == 0 || (out_src && out_dst)), "npi_negative_distinct: null pointer");
+    NPI_REQUIRE(((uintptr_t)workspace & 15) == 0, "npi_negative_distinct: workspace must be 16-byte aligned");
+    SortLayout L = sort_layout(W, 0);
+    if (workspace_bytes < L.total) {
+        set_error("npi_negative_distinct: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)L.total);
+        return NPI_ERR_ARG;
+    }
+    char* ws = (char*)workspace;
+    uint32_t* keys_a = (uint32_t*)(ws + L.off_keys_a);
+    uint32_t* keys_b = (uint32_t*)(ws + L.off_keys_b);
+    int32_t* vals_a = (int32_t*)(ws + L.off_vals_a);
+    int32_t* vals_b = (int32_t*)(ws + L.off_vals_b);
+    int32_t* counts = (int32_t*)(ws + L.off_counts);
+    int32_t* tiles = (int32_t*)(ws + L.off_tiles);
+    int dbits = 1, sbits = 1;
+    while (((int64_t)1 << dbits) < n_dst) ++dbits;         // ids lie in [0, n)
+    while (((int64_t)1 << sbits) < n_src) ++sbits;
+    const uint32_t invalid = (uint32_t)1 << sbits;         // sbits <= 31: one bit above every source id
+    const unsigned wb = (unsigned)ceil_div(W, 256);
+    negative_keys_kernel<<<wb, 256, 0, stream>>>(cand_dst, W, n_dst, keys_a, vals_a);
+    radix_sort_pairs(keys_a, keys_b, vals_a, vals_b, W, dbits, L, counts, tiles, stream);
+    negative_rekey_kernel<<<wb, 256, 0, stream>>>(cand_src, cand_dst, vals_a, W, n_src, n_dst, invalid, keys_a);
+    radix_sort_pairs(keys_a, keys_b, vals_a, vals_b, W, sbits + 1, L, counts, tiles, stream);
+    // the sort's second pair of buffers is free now: keep (scanned in place into the output positions) and a copy of it; the
+    // histogram buffer (W / 16 words) holds the scan's tile sums (W / SCAN_TILE of them)
+    int32_t* keep = (int32_t*)keys_b;
+    int32_t* kept = vals_b;
+    const int64_t ntiles = ceil_div(W, SCAN_TILE);
+    (void)hipMemsetAsync(keep, 0, (size_t)W * sizeof(int32_t), stream);
+    (void)hipMemsetAsync(kept, 0, (size_t)W * sizeof(int32_t), stream);
+    (void)hipMemsetAsync(info, 0, 2 * sizeof(int32_t), stream);
+    negative_heads_kernel<<<wb, 256, 0, stream>>>(keys_a, vals_a, cand_dst, W, invalid, keep, kept);
+    scan_tiles_kernel<<<(unsigned)ntiles, SCAN_THREADS, 0, stream>>>(keep, W, counts);
+    scan_sums_kernel<<<1, SCAN_THREADS, 0, stream>>>(counts, ntiles);
+    scan_add_kernel<<<(unsigned)ntiles, SCAN_THREADS, 0, stream>>>(keep, W, counts);
+    negative_compact_kernel<<<wb, 256, 0, stream>>>(cand_src, cand_dst, keep, kept, W, M, out_src, out_dst, info);
+    return check_launch("npi_negative_distinct");
 }
 
 extern "C" int64_t npi_topk_sorted_workspace_bytes(int64_t N) {

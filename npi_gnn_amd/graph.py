@@ -58,6 +58,11 @@ def raise_on_status(values) -> None:
     if any(int(v) & _lib.NPI_STATUS_BAD_SAMPLE_SIZES for v in values):
         raise ValueError("npi_sample_select / npi_sample_relabel: the offsets or counts they were given belong to another call; "
                          "the entries concerned were not written")
+    if any(int(v) & _lib.NPI_STATUS_BAD_SOURCE_ID for v in values):
+        raise IndexError("NegativeSampler.corrupt: a source id outside [0, n_src): its slot holds -1 (npi_negative_targets)")
+    if any(int(v) & _lib.NPI_STATUS_NO_NEGATIVE for v in values):
+        raise ValueError("NegativeSampler.corrupt: a source found no non-edge target within its tries (it is joined to every "
+                         "target, or tries ran out): its slot holds -1 (npi_negative_targets)")
     if any(int(v) & 4 for v in values):
         raise ValueError("InteractionGraph.batch: the n_nodes / n_pairs it was given do not belong to its keys (the device counted "
                          "other totals); that batch holds placeholders only (node 0 / graph 0 rows, padding edges, zero features).  "
