@@ -853,6 +853,61 @@ int64_t npi_negative_distinct_workspace_bytes(int64_t W);
 int npi_negative_distinct(const int32_t* cand_src, const int32_t* cand_dst, int64_t W, int64_t n_src, int64_t n_dst, int64_t M,
                           int64_t* out_src, int64_t* out_dst, int32_t* info, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Pair scores and the link-prediction loss: the third stage of a link-prediction step, after the samplers (the pairs) and the
+ * layers (the embeddings).  Replaces PyG 1.4.2 `torch_geometric/nn/models/autoencoder.py`:
+ *     InnerProductDecoder.forward : value = (z[edge_index[0]] * z[edge_index[1]]).sum(dim=1); torch.sigmoid(value) if sigmoid
+ *     GAE.recon_loss              : pos_loss = -torch.log(self.decoder(z, pos_edge_index, sigmoid=True) + EPS).mean()
+ *                                   neg_loss = -torch.log(1 - self.decoder(z, neg_edge_index, sigmoid=True) + EPS).mean()
+ *                                   return pos_loss + neg_loss                                    (EPS = 1e-15)
+ * and the composition `F.binary_cross_entropy_with_logits((z[i] * z[j]).sum(1), labels)`: two [M, F] gathers, their product and
+ * its row sum, then sigmoid / log / mean, each a pass over memory -- here ONE launch over the pair list as it is (no CSR, no sort).
+ *
+ *   src, dst  : int64 [M] (PyG's edge_index rows / NegativeSampler.pairs as they are).  The first n_pos pairs are POSITIVES, the
+ *               other M - n_pos negatives: the layout of `torch.cat([pos_edge_index, neg_edge_index], 1)`
+ *   z_src     : f32 [n_src, F], leading dimension ld_src (elements);  z_dst : f32 [n_dst, F], ld_dst.  They may be the same pointer
+ *               (one id space).  16-byte lanes when F % 4 == 0 and both bases and pitches are 16-byte aligned; else one float per lane
+ *   mode      : NPI_PAIR_LOGITS, NPI_PAIR_LOSS_GAE or NPI_PAIR_LOSS_BCE
+ *   logits [M]: <z_src[src_m], z_dst[dst_m]>, f32 accumulation in a fixed order                                     (may be NULL)
+ *   coef [M]  : d loss / d logit_m                                                               (loss modes only; may be NULL)
+ *   loss [1]  : the loss (loss modes only; may be NULL); needs `partials`: npi_pair_score_workspace_bytes(M) bytes, 16-byte aligned,
+ *               caller-owned, fully overwritten (one fp64 partial per workgroup of 256 pairs)
+ *   status    : int32 device word as npi_csr_build_ex's (may be NULL): OR-ed into, never cleared here
+ * At least one of logits / coef / loss must be given.
+ *
+ * Per pair, with x = logit_m and s = sigmoid(x) = 1 / (1 + exp(-x)), all in f32:
+ *   NPI_PAIR_LOSS_GAE : a positive contributes -log(s + EPS) / n_pos, a negative -log(q + EPS) / (M - n_pos) with q = 1 - s computed
+ *                       ONCE; coef is what autograd gives for exactly these expressions: -s q / (s + EPS) / n_pos and
+ *                       s q / (q + EPS) / (M - n_pos).  A part WITHOUT a pair (n_pos == 0 or n_pos == M) contributes 0 -- where
+ *                       PyG's `.mean()` of an empty tensor gives NaN; a deliberate deviation
+ *   NPI_PAIR_LOSS_BCE : binary_cross_entropy_with_logits(logits, y) with y = 1 for a positive, 0 for a negative, mean over all M:
+ *                       (max(x, 0) - x y + log1p(exp(-|x|))) / M;  coef = (s - y) / M with s - 1 evaluated as -sigmoid(-x): finite
+ *                       and accurate at any logit
+ * The loss is a DETERMINISTIC sum: a wavefront adds its 64 terms (fp64) in a fixed tree, a workgroup its four wavefronts in order
+ * into one partial, a second one-workgroup launch the partials in a fixed order.  No float atomics anywhere; bitwise reproducible.
+ *
+ * A pair with src_m outside [0, n_src) or dst_m outside [0, n_dst): logit 0, coef 0, loss term 0 (it still counts in n_pos / M);
+ * no row is dereferenced for it and NPI_STATUS_BAD_PAIR_ID is raised (torch's indexing raises there).
+ *
+ * Nothing is allocated, nothing read back to the host.  Refused with NPI_ERR_ARG before any launch: an unknown mode; M, F, n_src or
+ * n_dst negative or >= 2^31 - 1 (F < 1); n_pos outside [0, M]; a leading dimension below F; no output at all; coef or loss in
+ * NPI_PAIR_LOGITS mode; loss without partials, or partials misaligned or shorter than npi_pair_score_workspace_bytes(M); a null
+ * src / dst / z_src / z_dst when M > 0.  M == 0 returns NPI_OK WITHOUT a kernel launch; loss[0], if given, is then set to 0 by a
+ * hipMemsetAsync on `stream`.  npi_pair_score_workspace_bytes returns -1 for an M outside [0, 2^31 - 1).
+ *
+ * The backward needs no kernel of its own: dZ_dst[j] = sum_{m: dst_m = j} g_m z_src[src_m] and dZ_src[i] = sum_{m: src_m = i} g_m
+ * z_dst[dst_m] (g = coef times the upstream gradient) are npi_segsum_ex over the by-target / by-source CSR of the pair list with g
+ * as per-entry weights (npi_entry_weights) -- one id space: ONE sum over the CSR of keys cat(src, dst), values cat(dst, src).
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_PAIR_LOGITS 0
+#define NPI_PAIR_LOSS_GAE 1
+#define NPI_PAIR_LOSS_BCE 2
+#define NPI_STATUS_BAD_PAIR_ID 256
+int64_t npi_pair_score_workspace_bytes(int64_t M);
+int npi_pair_score(const int64_t* src, const int64_t* dst, int64_t M, int64_t n_pos, const float* z_src, int64_t ld_src,
+                   int64_t n_src, const float* z_dst, int64_t ld_dst, int64_t n_dst, int64_t F, int mode, float* logits, float* coef,
+                   float* loss, void* partials, int64_t partials_bytes, int32_t* status, void* stream);
+
 /* Evaluation loop (reference src/methods.py:87-105 compares one element per Python
  * iteration, one device sync each).  counts[4] += [TP, FN, TN, FP] for pred = first arg-max of scores[i, 0..C):
  * pred 1 & y 1 -> TP, pred 1 & y 0 -> FP, pred 0 & y 1 -> FN, anything else -> TN (the reference's else

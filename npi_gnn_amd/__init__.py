@@ -8,13 +8,15 @@ be imported.
 """
 from ._lib import LIB_PATH, NpiError, load  # noqa: F401
 from .graph import BipartiteGraph, CSRGraph, GraphBatch, as_graph, set_debug  # noqa: F401
-from .functional import GCNNorm, gat_conv, gat_conv_bipartite, gcn_conv, sage_conv, sage_conv_bipartite, segsum  # noqa: F401
+from .functional import (GCNNorm, gat_conv, gat_conv_bipartite, gcn_conv, link_loss, pair_scores, sage_conv,  # noqa: F401
+                         sage_conv_bipartite, segsum)
 from .nn import GATConv, GCNConv, SAGEConv  # noqa: F401
 from .schedule import Schedule  # noqa: F401
 from .graphed import GraphedStack  # noqa: F401
 from .sampler import Block, DataFlow, NeighborSampler, SubgraphBatch  # noqa: F401
 from .negative import NegativeSampler, negative_sampling, structured_negative_sampling  # noqa: F401
+from .autoencoder import GAE, InnerProductDecoder  # noqa: F401
 
 __all__ = ["CSRGraph", "GraphBatch", "as_graph", "set_debug", "GCNNorm", "gat_conv", "gcn_conv", "sage_conv", "segsum",
            "GATConv", "GCNConv", "SAGEConv", "Schedule", "GraphedStack", "NeighborSampler", "DataFlow", "Block", "SubgraphBatch", "NegativeSampler", "negative_sampling",
-           "structured_negative_sampling", "NpiError", "load", "LIB_PATH"]
+           "structured_negative_sampling", "InnerProductDecoder", "GAE", "pair_scores", "link_loss", "NpiError", "load", "LIB_PATH"]

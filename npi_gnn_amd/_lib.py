@@ -27,6 +27,10 @@ NPI_STATUS_BAD_TARGET_ID = 16     # status bit of npi_sample_counts / npi_sample
 NPI_STATUS_BAD_SAMPLE_SIZES = 32  # status bit of npi_sample_select / _relabel / _union: offsets / counts / capacity of another call
 NPI_STATUS_NO_NEGATIVE = 64       # status bit of npi_negative_targets: a slot whose tries all hit edges (it holds -1)
 NPI_STATUS_BAD_SOURCE_ID = 128    # status bit of npi_negative_targets: a source id outside [0, n_src) (its slot holds -1)
+NPI_STATUS_BAD_PAIR_ID = 256      # status bit of npi_pair_score: a pair with an id outside its table (logit, coefficient and loss term 0)
+NPI_PAIR_LOGITS = 0               # modes of npi_pair_score
+NPI_PAIR_LOSS_GAE = 1
+NPI_PAIR_LOSS_BCE = 2
 NPI_HUB_MAX = 128                # hubs per plan (npi_hub_plan; mask words of NPI_HUB_MAX / 32 per source row)
 
 
@@ -155,6 +159,8 @@ PROTOTYPES = {
     "npi_negative_targets": (c_int, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "npi_negative_distinct_workspace_bytes": (_I, [_I]),
     "npi_negative_distinct": (c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "npi_pair_score_workspace_bytes": (_I, [_I]),
+    "npi_pair_score": (c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, c_int, _P, _P, _P, _P, _I, _P, _P]),
 }
 
 _lib = None

@@ -1,0 +1,83 @@
+"""PyG 1.4.2 ``torch_geometric.nn.models.autoencoder`` on the MI355X: the decoder and the loss that close a link-prediction step::
+
+    model = npi.GAE(encoder)                                   # decoder: npi.InnerProductDecoder()
+    z = model.encode(x, edge_index)                            # a tensor [N, F], or a pair (z_src, z_dst) from bipartite layers
+    loss = model.recon_loss(z, pos_edge_index)                 # negatives drawn on the device, as many as positives
+    loss.backward()
+
+``InnerProductDecoder.forward`` is ``functional.pair_scores`` (one launch over the pair list, no sort), ``GAE.recon_loss`` is
+``functional.link_loss`` (one forward launch, no logits written; the backward is the layers' own aggregation: no float atomics,
+bitwise reproducible).  ``InnerProductDecoder.forward_all`` -- the dense ``[N, N]`` product -- and ``GAE.test`` are not provided.
+CPU tensors raise ``NpiError``: there is no CPU path.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+from torch import nn
+
+from . import functional as F_
+from .negative import NegativeSampler
+
+
+def _reset(module) -> None:
+    """PyG ``inits.reset``: ``reset_parameters()`` of the module, or of each of its children"""
+    if module is None:
+        return
+    if hasattr(module, "reset_parameters"):
+        module.reset_parameters()
+    else:
+        for child in (module.children() if hasattr(module, "children") else []):
+            _reset(child)
+
+
+class InnerProductDecoder(nn.Module):
+    """``forward(z, edge_index, sigmoid=True)``: ``sigmoid(<z_src[edge_index[0]], z_dst[edge_index[1]]>)`` per pair, ``[M]``;
+    ``sigmoid=False``: the logits.  ``z``: a tensor (one id space) or a pair ``(z_src, z_dst)``; ``edge_index``: the ``[2, M]``
+    LongTensor or a ``BipartiteGraph`` of it (``functional.pair_scores``)."""
+
+    def forward(self, z, edge_index, sigmoid: bool = True) -> torch.Tensor:
+        value = F_.pair_scores(z, edge_index)
+        return torch.sigmoid(value) if sigmoid else value
+
+
+class GAE(nn.Module):
+    """``GAE(encoder, decoder=None)``: ``encode`` runs the encoder, ``decode`` the decoder (default ``InnerProductDecoder``),
+    ``recon_loss`` the link-prediction loss of embeddings ``z``.  ``draw`` counts the negative draws ``recon_loss`` has made
+    (readable and settable, like ``NegativeSampler.draw``): successive calls see different negatives, and a run that starts from the
+    same ``seed`` and ``draw`` sees the same ones."""
+
+    def __init__(self, encoder, decoder=None):
+        super().__init__()
+        self.encoder = encoder
+        self.decoder = InnerProductDecoder() if decoder is None else decoder
+        self.draw = 0
+        GAE.reset_parameters(self)
+
+    def reset_parameters(self) -> None:
+        _reset(self.encoder)
+        _reset(self.decoder)
+
+    def encode(self, *args, **kwargs):
+        return self.encoder(*args, **kwargs)
+
+    def decode(self, *args, **kwargs):
+        return self.decoder(*args, **kwargs)
+
+    def recon_loss(self, z, pos_edge_index: torch.Tensor, neg_edge_index: Optional[torch.Tensor] = None, loss: str = "gae",
+                   seed: int = 0) -> torch.Tensor:
+        """PyG's ``recon_loss(z, pos_edge_index)`` (``loss="gae"``; ``"bce"``: ``binary_cross_entropy_with_logits`` over all
+        pairs), computed by ``functional.link_loss`` whatever the decoder.  ``neg_edge_index=None`` draws as many negatives as
+        there are positives (``NegativeSampler(pos_edge_index, size, seed).pairs(draw=self.draw)``, then ``draw`` counts up): one
+        id space excludes ``(v, v)`` -- PyG's "do not include self-loops in negative samples" --, a pair ``z`` draws from
+        ``size = (n_src, n_dst)``."""
+        if neg_edge_index is None:
+            z_src, z_dst, n_src, n_dst = F_._pair_tables(z, None, "GAE.recon_loss")
+            if loss not in F_.PAIR_LOSSES:
+                raise ValueError(f"GAE.recon_loss: loss is 'gae' or 'bce', got {loss!r}")
+            one = z_dst is None
+            sampler = NegativeSampler(pos_edge_index, n_src if one else (n_src, n_dst), seed=seed, allow_loops=not one)
+            neg_edge_index = sampler.pairs(draw=self.draw)
+            self.draw += 1
+        return F_.link_loss(z, pos_edge_index, neg_edge_index, loss=loss)

@@ -4,27 +4,9 @@
 // -- and, for GCNConv(normalize=True), the chain through norm = deg^-1/2[j] w deg^-1/2[i] (npi_gcn_norm_bwd).
 // The general form of gat.hip's by-target SDDMM (gat_edge_grad_kernel), without the softmax chain behind it.
 // No float atomics: every entry is summed by one wavefront in a fixed order, every output element has one writer.
-#include "npi_common.h"
+#include "dot_lanes.h"
 
 namespace npi {
-
-template <bool VEC> struct Lanes;
-template <> struct Lanes<true> {
-    using T = float4;
-    static constexpr int W = 4;
-    static __device__ __forceinline__ T zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-    static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const float4*>(p); }
-    static __device__ __forceinline__ float dot(const T& u, const T& v, float acc) {
-        return fmaf(u.w, v.w, fmaf(u.z, v.z, fmaf(u.y, v.y, fmaf(u.x, v.x, acc))));
-    }
-};
-template <> struct Lanes<false> {
-    using T = float;
-    static constexpr int W = 1;
-    static __device__ __forceinline__ T zero() { return 0.f; }
-    static __device__ __forceinline__ T load(const float* p) { return *p; }
-    static __device__ __forceinline__ float dot(const T& u, const T& v, float acc) { return fmaf(u, v, acc); }
-};
 
 // One wavefront per item of `item_edges` entries (64 or 256, picked per call by the rule of npi_item_edges), walked in blocks of
 // 64: columns, rows and edge ids of a block are fetched lane-parallel, the entries go eight at a time -- eight gathered rows of b
@@ -52,8 +34,7 @@ edge_dot_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ 
     const int k1 = (int)min(k0 + item_edges, (int64_t)nnz);
     __shared__ float pbuf[4][WAVE];
     float* __restrict__ pb = pbuf[threadIdx.x >> 6];
-    const bool b5 = (lane & 32) != 0, b4 = (lane & 16) != 0, b3 = (lane & 8) != 0;
-    const int e_of_lane = (b5 ? 4 : 0) + (b4 ? 2 : 0) + (b3 ? 1 : 0);
+    const int e_of_lane = group_of_lane(lane);
     T ar = L::zero();
     int cur = -1;
     for (int kb = (int)k0; kb < k1; kb += WAVE) {
@@ -107,17 +88,7 @@ edge_dot_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ 
                     }
                 }
             }
-            // reduce-scatter: every xor step halves the number of entries a lane still carries; afterwards the eight lanes
-            // of group e_of_lane all hold the sum of entry j + e_of_lane
-            float w4[4], w2[2];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) w4[k] = (b5 ? p[k + 4] : p[k]) + __shfl_xor(b5 ? p[k] : p[k + 4], 32, WAVE);
-#pragma unroll
-            for (int k = 0; k < 2; ++k) w2[k] = (b4 ? w4[k + 2] : w4[k]) + __shfl_xor(b4 ? w4[k] : w4[k + 2], 16, WAVE);
-            float y = (b3 ? w2[1] : w2[0]) + __shfl_xor(b3 ? w2[0] : w2[1], 8, WAVE);
-            y += __shfl_xor(y, 4, WAVE);
-            y += __shfl_xor(y, 2, WAVE);
-            y += __shfl_xor(y, 1, WAVE);
+            const float y = reduce_scatter8(p, lane);          // the eight lanes of group e_of_lane hold entry j + e_of_lane
             if ((lane & 7) == 0 && j + e_of_lane < nb) pb[j + e_of_lane] = y;
         }
         __builtin_amdgcn_wave_barrier();
@@ -167,8 +138,6 @@ __global__ void gcn_norm_bwd_kernel(const int32_t* __restrict__ rowptr, const in
 }  // namespace npi
 
 using namespace npi;
-
-static bool rows16(const void* p, int64_t ld, int64_t F) { return F % 4 == 0 && ld % 4 == 0 && ((uintptr_t)p % 16) == 0; }
 
 extern "C" int npi_edge_dot(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* eid, int64_t N,
                             int64_t n_cols, int64_t nnz_max, int64_t n_edges, const float* a, int64_t lda, const float* b,

@@ -14,8 +14,9 @@ from typing import Optional
 import torch
 
 from ._lib import (NPI_BF16, NPI_F32, NPI_GEMM_A_ZERO_PADDED, NPI_GEMM_EXACT_F32, NPI_GEMM_RESERVE_CUS, NPI_GEMM_SPLIT_F16X2,
-                   NPI_GEMM_WORKSPACE_PREPARED, NPI_PREPARE_F16X2, check, load, ptr, require_gpu, stream_ptr)
-from .graph import BipartiteGraph, CSRGraph, CSRSide, GraphBatch, HubPlan, as_graph, note_status
+                   NPI_GEMM_WORKSPACE_PREPARED, NPI_PAIR_LOGITS, NPI_PAIR_LOSS_BCE, NPI_PAIR_LOSS_GAE, NPI_PREPARE_F16X2, check, load, ptr,
+                   require_gpu, stream_ptr)
+from .graph import BipartiteGraph, CSRGraph, CSRSide, GraphBatch, HubPlan, as_graph, build_side, note_status, pair_list_side
 from .schedule import DEFAULT, Schedule
 
 
@@ -2214,3 +2215,227 @@ def gat_conv_bipartite(x, edge_index, weight: torch.Tensor, att: torch.Tensor, b
     out = out.view(n_dst, int(heads), -1).mean(dim=1)
     out = out + bias if bias is not None else out
     return torch.relu(out) if relu else out
+
+
+# ---------------------------------------------------------------------------------------------
+# Link prediction: pair scores and the loss over them (PyG 1.4.2 ``InnerProductDecoder`` / ``GAE.recon_loss``).  The forward is ONE
+# launch over the pair list as it is (``npi_pair_score``: no CSR, no sort); the backward is the aggregation the layers already
+# use -- ``segsum`` over the sides of the pair list with ``d loss / d logit`` as per-entry weights -- so it has no float atomics
+# and is bitwise reproducible, where autograd's ``index_add_`` of the torch composition is not.
+PAIR_LOSSES = {"gae": NPI_PAIR_LOSS_GAE, "bce": NPI_PAIR_LOSS_BCE}
+_PAIR_LIMIT = 2 ** 31 - 1
+
+
+def _pair_tables(z, size, who: str):
+    """``z``: a tensor ``[N, F]`` (one id space) or a pair ``(z_src, z_dst)``; ``(z_src, z_dst or None, n_src, n_dst)`` with
+    ``z_dst`` None when both ends read ONE table (a pair of the same tensor included)"""
+    if isinstance(z, torch.Tensor):
+        z_src = z_dst = z
+    elif isinstance(z, (tuple, list)) and len(z) == 2 and all(isinstance(t, torch.Tensor) for t in z):
+        z_src, z_dst = z
+    else:
+        raise TypeError(f"{who}: z is a tensor [N, F] (one id space) or a pair (z_src, z_dst) of tensors")
+    for t, name in ((z_src, "z_src"), (z_dst, "z_dst")):
+        if t.dim() != 2 or t.size(1) < 1:
+            raise ValueError(f"{who}: {name} must be a [rows, F] tensor with F >= 1 (got shape {tuple(t.shape)})")
+    if z_src.size(1) != z_dst.size(1):
+        raise ValueError(f"{who}: z_src has {z_src.size(1)} columns, z_dst {z_dst.size(1)}: an inner product needs equal widths")
+    n_src, n_dst = int(z_src.size(0)), int(z_dst.size(0))
+    if size is not None:
+        if not isinstance(size, (tuple, list)) or len(size) != 2:
+            raise ValueError(f"{who}: size must be a pair (n_src, n_dst)")
+        if (int(size[0]), int(size[1])) != (n_src, n_dst):
+            raise ValueError(f"{who}: size is {tuple(size)!r}, the tables have {(n_src, n_dst)} rows")
+    if max(n_src, n_dst, z_src.size(1)) >= _PAIR_LIMIT:
+        raise ValueError(f"{who}: table rows and width stay below 2^31 - 1")
+    for t, name in ((z_src, "z_src"), (z_dst, "z_dst")):
+        if t.dtype == torch.bfloat16:
+            raise NotImplementedError(f"{who}: the pair scores run on float32 tables (bf16 storage is not implemented)")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{who}: {name} must be float32 (got {t.dtype})")
+    return z_src, (None if z_dst is z_src else z_dst), n_src, n_dst
+
+
+class _PairList:
+    """The ``M`` pairs of one call -- ``src``, ``dst`` contiguous LongTensors -- and, built only when a backward asks, the CSR sides
+    its gradients are summed over: the caller's ``BipartiteGraph`` of the pairs when one was passed, else a side per request."""
+
+    def __init__(self, edge_index, n_src: int, n_dst: int, who: str):
+        self.graph = None
+        if isinstance(edge_index, BipartiteGraph):
+            if edge_index.size != (n_src, n_dst):
+                raise ValueError(f"{who}: the BipartiteGraph of the pairs was built for size {edge_index.size}, the tables give "
+                                 f"{(n_src, n_dst)}")
+            self.graph, self.src, self.dst = edge_index, edge_index._src, edge_index._dst
+        elif isinstance(edge_index, torch.Tensor):
+            if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
+                raise ValueError(f"{who}: the pairs are a LongTensor of shape [2, M] (got {edge_index.dtype} {tuple(edge_index.shape)})")
+            self.src, self.dst = edge_index[0].contiguous(), edge_index[1].contiguous()
+        else:
+            raise TypeError(f"{who}: the pairs are the [2, M] LongTensor or a BipartiteGraph of it")
+        self.n_src, self.n_dst, self.M = n_src, n_dst, int(self.src.numel())
+        if self.M >= _PAIR_LIMIT:
+            raise ValueError(f"{who}: more than 2^31 - 2 pairs in one call")
+        self._sides = {}
+
+    def side(self, which: str) -> CSRSide:
+        """``"dst"``: pairs grouped by target over the source table; ``"src"``: by source over the target table; ``"both"``: one id
+        space, both ends as keys (``graph.pair_list_side``)"""
+        if which not in self._sides:
+            g = self.graph
+            if which == "dst":
+                side = g.by_dst if g is not None else build_side(self.dst, self.src, self.n_dst, self.n_src, self_loops=False, drop_equal=False)
+            elif which == "src":
+                side = g.by_src if g is not None else build_side(self.src, self.dst, self.n_src, self.n_dst, self_loops=False, drop_equal=False)
+            else:
+                side = g.pair_side() if g is not None else pair_list_side(self.src, self.dst, self.n_src)
+            self._sides[which] = side
+        return self._sides[which]
+
+
+def _pitched(t: torch.Tensor) -> torch.Tensor:
+    """a table as the kernels take it: unit column stride, any row pitch >= F (a view of a wider buffer stays a view)"""
+    return t if (t.stride(1) == 1 and t.stride(0) >= t.size(1)) else t.contiguous()
+
+
+def _pair_score_launch(z_src, z_dst, pairs: _PairList, n_pos: int, mode: int, want_logits: bool, want_coef: bool, want_loss: bool):
+    """one ``npi_pair_score`` launch (plus the one-workgroup sum of the partials when the loss is asked for): ``(logits, coef, loss)``"""
+    dev = require_gpu(z_src, z_dst, pairs.src, pairs.dst)
+    z_src = _pitched(z_src)
+    z_dst = z_src if z_dst is None else _pitched(z_dst)
+    M, lib = pairs.M, load()
+    f32 = dict(dtype=torch.float32, device=dev)
+    logits = torch.empty(M, **f32) if want_logits else None
+    coef = torch.empty(M, **f32) if want_coef else None
+    loss = torch.empty((), **f32) if want_loss else None
+    ws = torch.empty(int(lib.npi_pair_score_workspace_bytes(M)), dtype=torch.uint8, device=dev) if want_loss else None
+    if M == 0 and not want_loss:
+        return logits, coef, loss                              # empty outputs (null pointers to the library): nothing to launch
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib.npi_pair_score(ptr(pairs.src), ptr(pairs.dst), M, int(n_pos), ptr(z_src), z_src.stride(0), pairs.n_src, ptr(z_dst),
+                             z_dst.stride(0), pairs.n_dst, z_src.size(1), mode, ptr(logits), ptr(coef), ptr(loss), ptr(ws),
+                             0 if ws is None else int(ws.numel()), ptr(status), stream_ptr(dev)), "npi_pair_score")
+    note_status(status)
+    return logits, coef, loss
+
+
+def _side_weights(side: CSRSide, g: torch.Tensor) -> torch.Tensor:
+    """per-pair values ``g`` (indexed by ``eid``) in the entry order of ``side``"""
+    we = torch.empty(max(side.nnz_max, 1), dtype=torch.float32, device=g.device)
+    check(load().npi_entry_weights(ptr(side.eid), ptr(side.rowidx), ptr(side.rowptr), ptr(g), 0, 1.0, side.n_rows, side.nnz_max, ptr(we),
+                                   stream_ptr(g.device)), "npi_entry_weights")
+    return we
+
+
+def _pair_grads(pairs: _PairList, z_src, z_dst, g: torch.Tensor, want_src: bool, want_dst: bool):
+    """``(dZ_src, dZ_dst)`` for ``d loss / d logit = g [M]``: ``dZ_dst[j] = sum_{m: dst_m = j} g_m z_src[src_m]`` over the by-target
+    side, ``dZ_src[i] = sum_{m: src_m = i} g_m z_dst[dst_m]`` over the by-source side -- only the sides asked for are built -- or, with
+    ONE table (``z_dst`` None), both terms in one segmented sum over ``pair_list_side`` (returned as ``dZ_src``)."""
+    if pairs.M == 0:
+        return (torch.zeros_like(z_src) if want_src else None,
+                torch.zeros_like(z_dst) if (want_dst and z_dst is not None) else None)
+    if z_dst is None:
+        side = pairs.side("both")
+        return segsum(None, side, _pitched(z_src), w=_side_weights(side, torch.cat([g, g]))), None
+    d_src = d_dst = None
+    if want_dst:
+        side = pairs.side("dst")
+        d_dst = segsum(None, side, _pitched(z_src), w=_side_weights(side, g))
+    if want_src:
+        side = pairs.side("src")
+        d_src = segsum(None, side, _pitched(z_dst), w=_side_weights(side, g))
+    return d_src, d_dst
+
+
+class _PairScoreFn(torch.autograd.Function):
+    """``logits[m] = <z_src[src_m], z_dst[dst_m]>`` (``z_dst`` None: one table) under an arbitrary upstream ``d logits``"""
+
+    @staticmethod
+    def forward(ctx, z_src, z_dst, pairs: _PairList):
+        logits = _pair_score_launch(z_src, z_dst, pairs, pairs.M, NPI_PAIR_LOGITS, True, False, False)[0]
+        ctx.pairs = pairs
+        ctx.save_for_backward(z_src, z_dst)
+        return logits
+
+    @staticmethod
+    def backward(ctx, grad):
+        z_src, z_dst = ctx.saved_tensors
+        d_src, d_dst = _pair_grads(ctx.pairs, z_src, z_dst, _f32c(grad, "grad"), ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return d_src, d_dst, None
+
+
+class _LinkLossFn(torch.autograd.Function):
+    """the scalar loss of ``npi_pair_score`` over ``cat([pos, neg], 1)``; ``coef = d loss / d logit`` comes out of the same launch and
+    is all the backward keeps of it (no logits are written)"""
+
+    @staticmethod
+    def forward(ctx, z_src, z_dst, pairs: _PairList, n_pos: int, mode: int):
+        want_coef = any(ctx.needs_input_grad[:2])
+        _, coef, loss = _pair_score_launch(z_src, z_dst, pairs, n_pos, mode, False, want_coef, True)
+        ctx.pairs, ctx.coef = pairs, coef
+        ctx.save_for_backward(z_src, z_dst)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        z_src, z_dst = ctx.saved_tensors
+        g = ctx.coef * grad.to(torch.float32)
+        d_src, d_dst = _pair_grads(ctx.pairs, z_src, z_dst, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return d_src, d_dst, None, None, None
+
+
+def pair_scores(z, edge_index, size=None) -> torch.Tensor:
+    """PyG 1.4.2 ``InnerProductDecoder.forward(z, edge_index, sigmoid=False)``: ``logits[m] = <z_src[edge_index[0, m]],
+    z_dst[edge_index[1, m]]>``, ``[M]`` float32.  ``z``: a tensor ``[N, F]`` (one id space) or a pair ``(z_src, z_dst)``
+    (``edge_index[0]`` indexes ``z_src``, as everywhere in the bipartite form; ``size``, if given, must be their row counts).
+    ``edge_index``: the ``[2, M]`` LongTensor, read in list order by ONE launch with no sort -- or a ``BipartiteGraph`` of it, whose
+    sides the backward then uses instead of sorting the list itself.  Under ``torch.no_grad()`` nothing is built at all.
+
+    Gradients: both tables, under any upstream gradient, each a deterministic segmented sum (bitwise reproducible; only the side
+    of a table that requires grad is built).  An id outside its table gives logit 0 and is reported like a dropped edge
+    (``graph.check_pending()`` raises ``IndexError``).  float32 only; CPU tensors raise ``NpiError``."""
+    who = "pair_scores"
+    z_src, z_dst, n_src, n_dst = _pair_tables(z, size, who)
+    pairs = _PairList(edge_index, n_src, n_dst, who)
+    require_gpu(z_src, z_dst, pairs.src)
+    return _PairScoreFn.apply(z_src, z_dst, pairs)
+
+
+def link_loss(z, pos_edge_index, neg_edge_index=None, loss: str = "gae", num_pos: Optional[int] = None) -> torch.Tensor:
+    """The link-prediction loss of the positives ``pos_edge_index [2, P]`` and the negatives ``neg_edge_index [2, Q]`` as a scalar,
+    in ONE forward launch that writes no logits:
+
+    ``loss="gae"``: PyG 1.4.2 ``GAE.recon_loss`` -- ``-log(sigmoid(x) + 1e-15).mean()`` over the positives plus
+    ``-log(1 - sigmoid(x) + 1e-15).mean()`` over the negatives, in float32 as PyG evaluates it.  A part without a pair adds 0
+    (PyG's ``mean()`` of an empty tensor is NaN).
+    ``loss="bce"``: ``binary_cross_entropy_with_logits(x, labels)`` with the mean over all ``P + Q`` pairs, in the stable form --
+    finite and accurate at any logit.
+
+    ``z`` as in ``pair_scores``.  A ``BipartiteGraph`` of ``torch.cat([pos, neg], 1)`` may stand in place of ``pos_edge_index``
+    (then ``neg_edge_index`` is None and ``num_pos`` says how many leading pairs are positives): the backward uses its sides.
+    Gradients: both tables, ``d loss / d logit`` from the forward launch times the upstream gradient as the per-entry weights of
+    the aggregation -- no float atomics, bitwise reproducible."""
+    who = "link_loss"
+    if loss not in PAIR_LOSSES:
+        raise ValueError(f"{who}: loss is 'gae' or 'bce', got {loss!r}")
+    z_src, z_dst, n_src, n_dst = _pair_tables(z, None, who)
+    if isinstance(pos_edge_index, BipartiteGraph):
+        if neg_edge_index is not None or num_pos is None:
+            raise ValueError(f"{who}: a BipartiteGraph holds cat([pos, neg], 1); pass neg_edge_index=None and num_pos")
+        pairs = _PairList(pos_edge_index, n_src, n_dst, who)
+        n_pos = int(num_pos)
+        if n_pos < 0 or n_pos > pairs.M:
+            raise ValueError(f"{who}: num_pos must lie in [0, {pairs.M}], got {num_pos}")
+    else:
+        if num_pos is not None:
+            raise ValueError(f"{who}: num_pos belongs to the BipartiteGraph form; with tensors the positives are pos_edge_index")
+        for t, name in ((pos_edge_index, "pos_edge_index"), (neg_edge_index, "neg_edge_index")):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{who}: {name} must be a LongTensor of shape [2, M]")
+            if t.dtype != torch.int64 or t.dim() != 2 or t.size(0) != 2:
+                raise ValueError(f"{who}: {name} must be a LongTensor of shape [2, M] (got {t.dtype} {tuple(t.shape)})")
+        require_gpu(z_src, z_dst, pos_edge_index, neg_edge_index)
+        n_pos = int(pos_edge_index.size(1))
+        pairs = _PairList(torch.cat([pos_edge_index, neg_edge_index], 1), n_src, n_dst, who)
+    require_gpu(z_src, z_dst, pairs.src)
+    return _LinkLossFn.apply(z_src, z_dst, pairs, n_pos, PAIR_LOSSES[loss])

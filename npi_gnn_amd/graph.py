@@ -63,6 +63,9 @@ def raise_on_status(values) -> None:
     if any(int(v) & _lib.NPI_STATUS_NO_NEGATIVE for v in values):
         raise ValueError("NegativeSampler.corrupt: a source found no non-edge target within its tries (it is joined to every "
                          "target, or tries ran out): its slot holds -1 (npi_negative_targets)")
+    if any(int(v) & _lib.NPI_STATUS_BAD_PAIR_ID for v in values):
+        raise IndexError("pair_scores / link_loss: a pair holds an id outside its embedding table: its logit, coefficient and loss "
+                         "term are 0 (npi_pair_score; torch's indexing raises here)")
     if any(int(v) & 4 for v in values):
         raise ValueError("InteractionGraph.batch: the n_nodes / n_pairs it was given do not belong to its keys (the device counted "
                          "other totals); that batch holds placeholders only (node 0 / graph 0 rows, padding edges, zero features).  "
@@ -415,6 +418,7 @@ class BipartiteGraph:
         self.by_dst.rect_hub = True
         self._by_src: Optional[CSRSide] = None
         self._root = None                       # (res_n_id storage, _version, shape) -> the combined by-source side (root_side)
+        self._pair = None                       # the one-id-space side of the list read as pairs (pair_side)
 
     @property
     def by_src(self) -> CSRSide:
@@ -453,11 +457,28 @@ class BipartiteGraph:
             self._root = (key, side, res_n_id)            # (the tensor is held: its storage cannot be reused under the key)
         return self._root[1]
 
+    def pair_side(self) -> CSRSide:
+        """The list read as PAIRS over ONE id space (``size = (N, N)``): the side of ``pair_list_side`` -- both ends of every pair
+        as keys -- built on first use and kept (the backward of ``functional.pair_scores`` / ``link_loss`` with one table)."""
+        if self._pair is None:
+            if self.num_src != self.num_dst:
+                raise ValueError(f"BipartiteGraph.pair_side: one id space needs size (N, N), this graph has {self.size}")
+            self._pair = pair_list_side(self._src, self._dst, self.num_src, item=self.by_dst.item)
+        return self._pair
+
     def nnz(self) -> int:
         """Entries (device read; synchronises -- and reports dropped out-of-range ids)."""
         n = int(self.by_dst.rowptr[-1].item())
         check_pending()
         return n
+
+
+def pair_list_side(src: torch.Tensor, dst: torch.Tensor, num_nodes: int, item: Optional[int] = None) -> CSRSide:
+    """The side over which ``dZ[v] = sum_{m: src_m = v} g_m z[dst_m] + sum_{m: dst_m = v} g_m z[src_m]`` -- the gradient of pair
+    scores ``<z[src_m], z[dst_m]>`` taken from ONE table -- is a single deterministic segmented sum: keys ``cat(src, dst)``, values
+    ``cat(dst, src)`` (``BipartiteGraph.root_side`` is the precedent for a concatenated side).  ``eid``: ``m`` for the entry that
+    pair m files under its source, ``M + m`` for the one under its target, so the per-entry weights come from ``cat(g, g)``."""
+    return build_side(torch.cat([src, dst]), torch.cat([dst, src]), num_nodes, num_nodes, self_loops=False, drop_equal=False, item=item)
 
 
 @dataclass
