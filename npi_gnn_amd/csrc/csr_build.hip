@@ -6,31 +6,13 @@
 //
 // Stable LSD radix sort on the key node id (8-bit digits, ceil(log2(N+1)/8) passes):
 // entries of a row keep their edge_index order, so the reduction order equals the
-// reference's CPU scatter order and every run is bitwise identical.
-#include "npi_common.h"
-#include <stdarg.h>
+// reference's CPU scatter order and every run is bitwise identical.  The sort itself: sort.h.
+//
+// Here: the key kernels, fill_csr_kernel, item_rows_kernel (write_item_rows for the other files), npi_csr_build_ex, npi_csr_filter
+// (the CSR of a pooled graph from its parent's, no sort) with its kernels, npi_edge_positions and the item-size queries.
+#include "sort.h"
 
 namespace npi {
-
-static thread_local char g_err[512] = "";
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-constexpr int SORT_THREADS = 256;
-constexpr int SORT_WAVES = SORT_THREADS / WAVE;
-constexpr int SORT_ITEMS = 16;                       // keys per lane
-constexpr int SORT_WAVE_TILE = WAVE * SORT_ITEMS;    // 1024 keys per wave, striped: key j*64+lane
-constexpr int SORT_TILE = SORT_THREADS * SORT_ITEMS; // 4096 keys per workgroup
-constexpr int RADIX = 256;
-
-constexpr int SCAN_THREADS = 256;
-constexpr int SCAN_ITEMS = 8;
-constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
-static_assert(SCAN_THREADS == SORT_THREADS && SORT_THREADS == 256, "one thread per radix digit");
 
 // key = key node, or N (sentinel, sorts behind every row) for dropped columns
 __global__ void make_keys_kernel(const int64_t* __restrict__ key_nodes,
@@ -73,163 +55,6 @@ __global__ void rekey_kernel(const int64_t* __restrict__ key_nodes, const int64_
     const bool bad = !pad & ((k < 0) | (k >= N) | (v < 0) | (v >= n_cols));
     if (bad) atomicOr(status, 1);
     keys[i] = (pad || bad || (drop_equal && k == v)) ? (uint32_t)N : (uint32_t)k;
-}
-
-__global__ void __launch_bounds__(SORT_THREADS)
-radix_hist_kernel(const uint32_t* __restrict__ keys, int64_t n, int shift, int nblocks,
-                  int32_t* __restrict__ counts) {
-    __shared__ int hist[RADIX];
-    hist[threadIdx.x] = 0;
-    __syncthreads();
-    int64_t base = (int64_t)blockIdx.x * SORT_TILE;
-#pragma unroll
-    for (int j = 0; j < SORT_ITEMS; ++j) {
-        int64_t i = base + j * SORT_THREADS + threadIdx.x;
-        if (i < n) atomicAdd(&hist[(keys[i] >> shift) & (RADIX - 1)], 1);
-    }
-    __syncthreads();
-    counts[(int64_t)threadIdx.x * nblocks + blockIdx.x] = hist[threadIdx.x];   // digit-major
-}
-
-// ---- exclusive scan of an int32 array (three launches) -------------------------------------
-__device__ __forceinline__ int block_exclusive_scan(int v, int* lds /*[SCAN_THREADS]*/, int* total) {
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 1; off < SCAN_THREADS; off <<= 1) {
-        int t = (threadIdx.x >= off) ? lds[threadIdx.x - off] : 0;
-        __syncthreads();
-        lds[threadIdx.x] += t;
-        __syncthreads();
-    }
-    int incl = lds[threadIdx.x];
-    *total = lds[SCAN_THREADS - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-__global__ void __launch_bounds__(SCAN_THREADS)
-scan_tiles_kernel(int32_t* __restrict__ data, int64_t n, int32_t* __restrict__ tile_sums) {
-    __shared__ int lds[SCAN_THREADS];
-    int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
-    int v[SCAN_ITEMS];
-    int s = 0;
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j) {
-        v[j] = (base + j < n) ? data[base + j] : 0;
-        s += v[j];
-    }
-    int total;
-    int excl = block_exclusive_scan(s, lds, &total);
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j) {
-        if (base + j < n) data[base + j] = excl;
-        excl += v[j];
-    }
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(SCAN_THREADS)
-scan_sums_kernel(int32_t* __restrict__ sums, int64_t n) {   // one workgroup
-    __shared__ int lds[SCAN_THREADS];
-    int carry = 0;
-    for (int64_t base = 0; base < n; base += SCAN_THREADS) {
-        int64_t i = base + threadIdx.x;
-        int v = (i < n) ? sums[i] : 0;
-        int total;
-        int excl = block_exclusive_scan(v, lds, &total);
-        if (i < n) sums[i] = carry + excl;
-        carry += total;
-    }
-}
-
-__global__ void __launch_bounds__(SCAN_THREADS)
-scan_add_kernel(int32_t* __restrict__ data, int64_t n, const int32_t* __restrict__ tile_sums) {
-    int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
-    int add = tile_sums[blockIdx.x];
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j)
-        if (base + j < n) data[base + j] += add;
-}
-
-// ---- stable scatter of one radix pass ----------------------------------------------------------
-// SCANNED: `offsets` is the exclusive scan of the digit-major tile histograms (three scan launches before this one).
-// !SCANNED (at most SMALL_SORT_TILES tiles -- the reference's 200-subgraph batches, launch-bound): `offsets` holds the
-// raw histograms and every workgroup derives its own start offsets from them, two launches per pass instead of five.
-constexpr int SMALL_SORT_TILES = 64;
-template <bool SCANNED>
-__global__ void __launch_bounds__(SORT_THREADS)
-radix_scatter_kernel(const uint32_t* __restrict__ keys_in, const int32_t* __restrict__ vals_in,
-                     uint32_t* __restrict__ keys_out, int32_t* __restrict__ vals_out,
-                     int64_t n, int shift, int nblocks, const int32_t* __restrict__ offsets) {
-    __shared__ int wcnt[SORT_WAVES][RADIX];
-    const int lane = lane_id();
-    const int wave = threadIdx.x >> 6;
-    for (int i = threadIdx.x; i < SORT_WAVES * RADIX; i += SORT_THREADS) (&wcnt[0][0])[i] = 0;
-    __syncthreads();
-
-    const int64_t base = (int64_t)blockIdx.x * SORT_TILE + (int64_t)wave * SORT_WAVE_TILE;
-    uint32_t key[SORT_ITEMS];
-    int32_t val[SORT_ITEMS];
-    int rank[SORT_ITEMS];
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int j = 0; j < SORT_ITEMS; ++j) {
-        int64_t i = base + j * WAVE + lane;
-        bool valid = i < n;
-        key[j] = valid ? keys_in[i] : 0xFFFFFFFFu;
-        val[j] = valid ? vals_in[i] : 0;
-        // tail lanes rank as digit 255 of the last tile: they sort behind everything and are not written
-        int digit = valid ? (int)((key[j] >> shift) & (RADIX - 1)) : (RADIX - 1);
-        uint64_t same = ~0ull;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            bool bit = (digit >> b) & 1;
-            uint64_t m = __ballot(bit);
-            same &= bit ? m : ~m;
-        }
-        int before = __popcll(same & lt_mask);
-        int prev = wcnt[wave][digit];
-        __builtin_amdgcn_wave_barrier();
-        if (before == 0) wcnt[wave][digit] = prev + __popcll(same);
-        __builtin_amdgcn_wave_barrier();
-        rank[j] = prev + before;
-    }
-    __syncthreads();
-    {   // thread d owns digit d: turn per-wave counts into global start offsets
-        int d = threadIdx.x;
-        int off;
-        if (SCANNED) {
-            off = offsets[(int64_t)d * nblocks + blockIdx.x];
-        } else {
-            __shared__ int scan_s[SCAN_THREADS];
-            const int32_t* __restrict__ h = offsets + (int64_t)d * nblocks;
-            int total = 0, before = 0;
-            for (int t = 0; t < nblocks; ++t) {
-                const int c = h[t];
-                before += (t < (int)blockIdx.x) ? c : 0;
-                total += c;
-            }
-            int all;
-            off = block_exclusive_scan(total, scan_s, &all) + before;   // keys with a smaller digit + same digit in earlier tiles
-        }
-#pragma unroll
-        for (int w = 0; w < SORT_WAVES; ++w) {
-            int c = wcnt[w][d];
-            wcnt[w][d] = off;
-            off += c;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < SORT_ITEMS; ++j) {
-        int64_t i = base + j * WAVE + lane;
-        if (i < n) {
-            int digit = (int)((key[j] >> shift) & (RADIX - 1));
-            int pos = wcnt[wave][digit] + rank[j];
-            keys_out[pos] = key[j];
-            vals_out[pos] = val[j];
-        }
-    }
 }
 
 __device__ __forceinline__ int64_t first_key_at_least(const uint32_t* __restrict__ keys, int64_t E, int64_t r) {
@@ -298,6 +123,10 @@ __global__ void item_rows_kernel(const int32_t* __restrict__ rowptr, int64_t N, 
     }
     item_row[i] = (int32_t)(lo - 1);
 }
+void write_item_rows(const int32_t* rowptr, int64_t N, int64_t nnz_max, int64_t item_edges, int32_t* item_row, hipStream_t stream) {
+    const int64_t n_items = num_items_of(nnz_max, item_edges);
+    item_rows_kernel<<<(unsigned)ceil_div(n_items + 1, 256), 256, 0, stream>>>(rowptr, N, n_items, (int)item_edges, item_row);
+}
 
 __global__ void edge_positions_kernel(const int32_t* __restrict__ eid, const int32_t* __restrict__ rowptr,
                                       int64_t N, int64_t nnz_max, int32_t* __restrict__ pos_of) {
@@ -312,207 +141,13 @@ __global__ void fill_i32_kernel(int32_t* __restrict__ p, int64_t n, int32_t v) {
     if (i < n) p[i] = v;
 }
 
-struct SortLayout {
-    int64_t nblocks, counts_len, ntiles;
-    int64_t off_keys_a, off_keys_b, off_vals_a, off_vals_b, off_counts, off_tiles, total;
-};
-
-static SortLayout sort_layout(int64_t E, int64_t N) {
-    SortLayout L;
-    L.nblocks = ceil_div(E > 0 ? E : 1, SORT_TILE);
-    L.counts_len = L.nblocks * RADIX;
-    L.ntiles = ceil_div(L.counts_len, SCAN_TILE);
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) { int64_t r = o; o += align_up(bytes, 256); return r; };
-    int64_t Ee = E > 0 ? E : 1;
-    L.off_keys_a = take(Ee * 4);
-    L.off_keys_b = take(Ee * 4);
-    L.off_vals_a = take(Ee * 4);
-    L.off_vals_b = take(Ee * 4);
-    L.off_counts = take(L.counts_len * 4);
-    L.off_tiles = take(L.ntiles * 4);
-    L.total = o;
-    return L;
-}
-
-// stable LSD radix sort of (key, val) pairs on the low `bits` bits of the key, 8 bits per pass; the sorted pairs end up in
-// (keys_a, vals_a) -- the pointers are swapped pass by pass
-static void radix_sort_pairs(uint32_t*& keys_a, uint32_t*& keys_b, int32_t*& vals_a, int32_t*& vals_b, int64_t n, int bits,
-                             const SortLayout& L, int32_t* counts, int32_t* tiles, hipStream_t stream) {
-    const int passes = (bits + 7) / 8;
-    for (int p = 0; p < passes; ++p) {
-        const int shift = 8 * p;
-        radix_hist_kernel<<<(unsigned)L.nblocks, SORT_THREADS, 0, stream>>>(keys_a, n, shift, (int)L.nblocks, counts);
-        if (L.nblocks <= SMALL_SORT_TILES) {
-            radix_scatter_kernel<false><<<(unsigned)L.nblocks, SORT_THREADS, 0, stream>>>(keys_a, vals_a, keys_b, vals_b, n, shift, (int)L.nblocks, counts);
-        } else {
-            scan_tiles_kernel<<<(unsigned)L.ntiles, SCAN_THREADS, 0, stream>>>(counts, L.counts_len, tiles);
-            scan_sums_kernel<<<1, SCAN_THREADS, 0, stream>>>(tiles, L.ntiles);
-            scan_add_kernel<<<(unsigned)L.ntiles, SCAN_THREADS, 0, stream>>>(counts, L.counts_len, tiles);
-            radix_scatter_kernel<true><<<(unsigned)L.nblocks, SORT_THREADS, 0, stream>>>(keys_a, vals_a, keys_b, vals_b, n, shift, (int)L.nblocks, counts);
-        }
-        uint32_t* tk = keys_a; keys_a = keys_b; keys_b = tk;
-        int32_t* tv = vals_a; vals_a = vals_b; vals_b = tv;
-    }
-}
-
-// ---- merging the equal (source, target) pairs of a sampled subgraph (npi_sample_coalesce; the sampler's other kernels: sample.hip) ------
-// Replaces the `idx = src * num_nodes + dst; idx.unique()` + `scatter_` lines of PyG 1.4.2 NeighborSampler.__produce_subgraph__.  LSD over
-// the pair: the stable sort by target first, then the stable sort by source; val = the entry's index, so equal pairs stay in entry order.
-__global__ void coalesce_keys_kernel(const int32_t* __restrict__ dst_l, int64_t E, uint32_t* __restrict__ keys, int32_t* __restrict__ vals) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= E) return;
-    keys[i] = (uint32_t)dst_l[i];
-    vals[i] = (int32_t)i;
-}
-__global__ void coalesce_rekey_kernel(const int32_t* __restrict__ src_l, const int32_t* __restrict__ vals, int64_t E,
-                                      uint32_t* __restrict__ keys) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < E) keys[p] = (uint32_t)src_l[vals[p]];
-}
-// dst_s[p] = the target of the entry sorted to p (its source: the sort's key); head[p] = 1 where a run of equal pairs starts
-__global__ void coalesce_heads_kernel(const uint32_t* __restrict__ src_s, const int32_t* __restrict__ vals, const int32_t* __restrict__ dst_l,
-                                      int64_t E, int32_t* __restrict__ dst_s, int32_t* __restrict__ head) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= E) return;
-    const int32_t d = dst_l[vals[p]];
-    dst_s[p] = d;
-    head[p] = (p == 0 || src_s[p - 1] != src_s[p] || dst_l[vals[p - 1]] != d) ? 1 : 0;
-}
-// pos = the exclusive scan of head.  The head of a run writes the pair and the smallest eid of its run (runs are short: a pair
-// repeats once per hop it was sampled in and once per parallel edge); info[0] = the number of runs
-__global__ void coalesce_compact_kernel(const uint32_t* __restrict__ src_s, const int32_t* __restrict__ dst_s, const int32_t* __restrict__ vals,
-                                        const int32_t* __restrict__ pos, const int32_t* __restrict__ eid, int64_t E,
-                                        int64_t* __restrict__ edge_src, int64_t* __restrict__ edge_dst, int64_t* __restrict__ e_id,
-                                        int32_t* __restrict__ info) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= E) return;
-    const uint32_t s = src_s[p];
-    const int32_t d = dst_s[p];
-    const bool head = p == 0 || src_s[p - 1] != s || dst_s[p - 1] != d;
-    const int64_t q = pos[p];                                    // q <= p < E: within the caller's bound
-    if (p == E - 1) info[0] = (int32_t)(q + (head ? 1 : 0));
-    if (!head) return;
-    int32_t m = eid[vals[p]];
-    for (int64_t r = p + 1; r < E && src_s[r] == s && dst_s[r] == d; ++r) {
-        const int32_t e = eid[vals[r]];
-        m = e < m ? e : m;
-    }
-    edge_src[q] = (int64_t)(int32_t)s;
-    edge_dst[q] = d;
-    e_id[q] = m;
-}
-
-// ---- the first M distinct valid pairs of a window of negative candidates (npi_negative_distinct; the candidates: negative.hip) ----------
-// Replaces the `if (a, b) in positives or (a, b) in negatives: continue` of src/generate_edgelist.py:108-139 for the "already drawn"
-// half.  The same LSD scheme as above -- by target, then by source, val = the candidate's position -- with one more key bit in the
-// second sort that puts the invalid candidates ((-1, -1), or an id out of range) behind every valid one.  The sorts are stable over
-// the position, so the head of a run of equal pairs is its EARLIEST occurrence: it alone sets keep[position].
-__global__ void negative_keys_kernel(const int32_t* __restrict__ cand_dst, int64_t W, int64_t n_dst, uint32_t* __restrict__ keys,
-                                     int32_t* __restrict__ vals) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= W) return;
-    const int32_t d = cand_dst[i];
-    keys[i] = (d < 0 || d >= n_dst) ? 0u : (uint32_t)d;
-    vals[i] = (int32_t)i;
-}
-__global__ void negative_rekey_kernel(const int32_t* __restrict__ cand_src, const int32_t* __restrict__ cand_dst,
-                                      const int32_t* __restrict__ vals, int64_t W, int64_t n_src, int64_t n_dst, uint32_t invalid,
-                                      uint32_t* __restrict__ keys) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= W) return;
-    const int32_t i = vals[p], s = cand_src[i], d = cand_dst[i];
-    keys[p] = (s < 0 || s >= n_src || d < 0 || d >= n_dst) ? invalid : (uint32_t)s;
-}
-// keep / kept (both ALL ZERO on entry): 1 at the position of every first occurrence of a valid pair
-__global__ void negative_heads_kernel(const uint32_t* __restrict__ src_s, const int32_t* __restrict__ vals, const int32_t* __restrict__ cand_dst,
-                                      int64_t W, uint32_t invalid, int32_t* __restrict__ keep, int32_t* __restrict__ kept) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= W) return;
-    const uint32_t s = src_s[p];
-    if (s == invalid) return;
-    const int32_t i = vals[p];
-    if (p == 0 || src_s[p - 1] != s || cand_dst[vals[p - 1]] != cand_dst[i]) {
-        keep[i] = 1;
-        kept[i] = 1;
-    }
-}
-// pos = the exclusive scan of keep in position order; info (ALL ZERO on entry) = (distinct valid pairs, candidates consumed by the M-th)
-__global__ void negative_compact_kernel(const int32_t* __restrict__ cand_src, const int32_t* __restrict__ cand_dst,
-                                        const int32_t* __restrict__ pos, const int32_t* __restrict__ kept, int64_t W, int64_t M,
-                                        int64_t* __restrict__ out_src, int64_t* __restrict__ out_dst, int32_t* __restrict__ info) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= W) return;
-    const int64_t q = pos[i];                                    // q <= i
-    const bool on = kept[i] != 0;
-    if (i == W - 1) info[0] = (int32_t)(q + (on ? 1 : 0));
-    if (!on || q >= M) return;
-    out_src[q] = cand_src[i];
-    out_dst[q] = cand_dst[i];
-    if (q == M - 1) info[1] = (int32_t)(i + 1);
-}
-
-// ---- TopKPooling selection for graphs of ANY size (pool.hip sorts a graph's scores in LDS: up to 16,384 nodes) -----------
-// Two stable radix sorts of the whole batch: by score (descending; the sort is stable over the node index, so equal scores
-// keep the lower index first -- torch.sort(descending=True, stable) order, as the LDS kernel), then by graph id: position
-// graph_ptr[g] + r of the result is the node of graph g with the r-th highest score.
-__global__ void topk_score_keys_kernel(const float* __restrict__ score, int64_t N, uint32_t* __restrict__ keys,
-                                       int32_t* __restrict__ vals) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const float f = score[i];
-    uint32_t u = __float_as_uint(f);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);     // ascending-orderable
-    keys[i] = (f != f) ? 0u : ~u;                       // descending; NaN first, as torch.sort treats it as the largest
-    vals[i] = (int32_t)i;
-}
-__global__ void topk_graph_keys_kernel(const int64_t* __restrict__ batch, const int32_t* __restrict__ vals, int64_t N,
-                                       uint32_t* __restrict__ keys) {
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < N) keys[q] = (uint32_t)batch[vals[q]];
-}
-// out_ptr[g] = sum_{g' < g} min(ceil(ratio n_g'), n_g') in the f32 arithmetic of pool.hip's topk_counts_kernel; one workgroup
-__global__ void __launch_bounds__(256)
-topk_kept_offsets_kernel(const int32_t* __restrict__ graph_ptr, int B, float ratio, int32_t* __restrict__ out_ptr) {
-    __shared__ int lds[256];
-    int carry = 0;
-    for (int base = 0; base < B; base += 256) {
-        const int g = base + threadIdx.x;
-        int k = 0;
-        if (g < B) {
-            const int n = graph_ptr[g + 1] - graph_ptr[g];
-            k = min((int)ceilf(ratio * (float)n), n);
-        }
-        int total;
-        const int excl = block_exclusive_scan(k, lds, &total);
-        if (g < B) out_ptr[g] = carry + excl;
-        carry += total;
-    }
-    if (threadIdx.x == 0) out_ptr[B] = carry;
-}
-__global__ void topk_take_kernel(const uint32_t* __restrict__ graph_of, const int32_t* __restrict__ node_of, int64_t N,
-                                 const int32_t* __restrict__ graph_ptr, const int32_t* __restrict__ out_ptr,
-                                 int32_t* __restrict__ perm, int32_t* __restrict__ remap) {
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= N) return;
-    const int g = (int)graph_of[q], node = node_of[q];
-    const int rank = (int)(q - graph_ptr[g]);
-    const int k = out_ptr[g + 1] - out_ptr[g];
-    const int at = rank < k ? out_ptr[g] + rank : -1;
-    if (at >= 0) perm[at] = node;
-    remap[node] = at;                                    // every node occurs exactly once: kept -> new id, dropped -> -1
-}
-
 }  // namespace npi
 
 using namespace npi;
 
-extern "C" const char* npi_last_error(void) { return npi::g_err; }
-extern "C" int npi_abi_version(void) { return 4; }
-
 extern "C" int64_t npi_csr_workspace_bytes(int64_t E, int64_t N) {
     if (E < 0 || N < 0) return -1;
-    return sort_layout(E, N).total;
+    return PairSort::bytes(E);
 }
 
 extern "C" int64_t npi_item_edges(int64_t nnz_max) { return npi::item_edges_for(nnz_max); }
@@ -536,178 +171,30 @@ extern "C" int npi_csr_build_ex(const int64_t* key_nodes, const int64_t* val_nod
                 "npi_csr_build: column range does not fit");
     NPI_REQUIRE(rowptr && item_row && status && workspace, "npi_csr_build: null output");
     NPI_REQUIRE(E == 0 || (key_nodes && val_nodes && col), "npi_csr_build: null edge arrays");
-    SortLayout L = sort_layout(E, N);
-    if (workspace_bytes < L.total) {
-        set_error("npi_csr_build: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)L.total);
+    PairSort ps;
+    if (!ps.carve(workspace, workspace_bytes, E)) {
+        set_error("npi_csr_build: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)PairSort::bytes(E));
         return NPI_ERR_WORKSPACE;
     }
-    char* ws = (char*)workspace;
-    uint32_t* keys_a = (uint32_t*)(ws + L.off_keys_a);
-    uint32_t* keys_b = (uint32_t*)(ws + L.off_keys_b);
-    int32_t* vals_a = (int32_t*)(ws + L.off_vals_a);
-    int32_t* vals_b = (int32_t*)(ws + L.off_vals_b);
-    int32_t* counts = (int32_t*)(ws + L.off_counts);
-    int32_t* tiles = (int32_t*)(ws + L.off_tiles);
-
     (void)hipMemsetAsync(status, 0, sizeof(int32_t), stream);
     const int drop_equal = build_flags & NPI_CSR_DROP_EQUAL;
     if (E > 0) {
         const unsigned eb = (unsigned)ceil_div(E, 256);
         if (build_flags & NPI_CSR_SORT_COLUMNS) {
             // LSD over the pair (row, column): the stable sort by column first, then the stable sort by row keeps it inside a row
-            col_keys_kernel<<<eb, 256, 0, stream>>>(val_nodes, E, n_cols, keys_a, vals_a);
-            int cbits = 1;
-            while (((int64_t)1 << cbits) <= n_cols) ++cbits;
-            radix_sort_pairs(keys_a, keys_b, vals_a, vals_b, E, cbits, L, counts, tiles, stream);
-            rekey_kernel<<<eb, 256, 0, stream>>>(key_nodes, val_nodes, vals_a, E, N, n_cols, drop_equal, keys_a, status);
+            col_keys_kernel<<<eb, 256, 0, stream>>>(val_nodes, E, n_cols, ps.keys_a, ps.vals_a);
+            ps.sort(key_bits(n_cols + 1), stream);      // keys lie in [0, n_cols]
+            rekey_kernel<<<eb, 256, 0, stream>>>(key_nodes, val_nodes, ps.vals_a, E, N, n_cols, drop_equal, ps.keys_a, status);
         } else {
-            make_keys_kernel<<<eb, 256, 0, stream>>>(key_nodes, val_nodes, E, N, n_cols, drop_equal, keys_a, vals_a, status);
+            make_keys_kernel<<<eb, 256, 0, stream>>>(key_nodes, val_nodes, E, N, n_cols, drop_equal, ps.keys_a, ps.vals_a, status);
         }
-        int bits = 1;
-        while (((int64_t)1 << bits) <= N) ++bits;       // keys lie in [0, N]
-        radix_sort_pairs(keys_a, keys_b, vals_a, vals_b, E, bits, L, counts, tiles, stream);
+        ps.sort(key_bits(N + 1), stream);               // keys lie in [0, N]
     }
     const unsigned entry_blocks = (unsigned)ceil_div(E, 256);
     fill_csr_kernel<<<entry_blocks + (unsigned)ceil_div(N + 1, 256), 256, 0, stream>>>(
-        keys_a, vals_a, val_nodes, E, N, add_self_loops, (int32_t)loop_col_offset, entry_blocks, rowptr, col, eid, rowidx);
-    const int64_t nnz_max = E + (add_self_loops ? N : 0);
-    int64_t n_items = num_items_of(nnz_max, item_edges);
-    item_rows_kernel<<<(unsigned)ceil_div(n_items + 1, 256), 256, 0, stream>>>(rowptr, N, n_items, (int)item_edges, item_row);
+        ps.keys_a, ps.vals_a, val_nodes, E, N, add_self_loops, (int32_t)loop_col_offset, entry_blocks, rowptr, col, eid, rowidx);
+    write_item_rows(rowptr, N, E + (add_self_loops ? N : 0), item_edges, item_row, stream);
     return check_launch("npi_csr_build");
-}
-
-extern "C" int64_t npi_sample_coalesce_workspace_bytes(int64_t E) {
-    if (E < 0 || E >= (int64_t)0x7fffffff) return -1;
-    return sort_layout(E, 0).total;
-}
-
-extern "C" int npi_sample_coalesce(const int32_t* src_l, const int32_t* dst_l, const int32_t* eid, int64_t E, int64_t U, int64_t* edge_src,
-                                   int64_t* edge_dst, int64_t* e_id, int32_t* info, void* workspace, int64_t workspace_bytes,
-                                   void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(E >= 0 && E < (int64_t)0x7fffffff && U >= 0 && U < (int64_t)0x7fffffff, "npi_sample_coalesce: bad size");
-    if (E == 0) return NPI_OK;
-    NPI_REQUIRE(src_l && dst_l && eid && edge_src && edge_dst && e_id && info && workspace, "npi_sample_coalesce: null pointer");
-    NPI_REQUIRE(((uintptr_t)workspace & 15) == 0, "npi_sample_coalesce: workspace must be 16-byte aligned");
-    SortLayout L = sort_layout(E, 0);
-    if (workspace_bytes < L.total) {
-        set_error("npi_sample_coalesce: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)L.total);
-        return NPI_ERR_WORKSPACE;
-    }
-    char* ws = (char*)workspace;
-    uint32_t* keys_a = (uint32_t*)(ws + L.off_keys_a);
-    uint32_t* keys_b = (uint32_t*)(ws + L.off_keys_b);
-    int32_t* vals_a = (int32_t*)(ws + L.off_vals_a);
-    int32_t* vals_b = (int32_t*)(ws + L.off_vals_b);
-    int32_t* counts = (int32_t*)(ws + L.off_counts);
-    int32_t* tiles = (int32_t*)(ws + L.off_tiles);
-    int bits = 1;
-    while (((int64_t)1 << bits) < U) ++bits;             // local ids lie in [0, U)
-    const unsigned eb = (unsigned)ceil_div(E, 256);
-    coalesce_keys_kernel<<<eb, 256, 0, stream>>>(dst_l, E, keys_a, vals_a);
-    radix_sort_pairs(keys_a, keys_b, vals_a, vals_b, E, bits, L, counts, tiles, stream);
-    coalesce_rekey_kernel<<<eb, 256, 0, stream>>>(src_l, vals_a, E, keys_a);
-    radix_sort_pairs(keys_a, keys_b, vals_a, vals_b, E, bits, L, counts, tiles, stream);
-    // the sort's second pair of buffers is free now: the sorted targets and the run heads; the histogram buffer (E / 16 words) holds
-    // the scan's tile sums (E / SCAN_TILE of them)
-    int32_t* dst_s = vals_b;
-    int32_t* head = (int32_t*)keys_b;
-    const int64_t ntiles = ceil_div(E, SCAN_TILE);
-    coalesce_heads_kernel<<<eb, 256, 0, stream>>>(keys_a, vals_a, dst_l, E, dst_s, head);
-    scan_tiles_kernel<<<(unsigned)ntiles, SCAN_THREADS, 0, stream>>>(head, E, counts);
-    scan_sums_kernel<<<1, SCAN_THREADS, 0, stream>>>(counts, ntiles);
-    scan_add_kernel<<<(unsigned)ntiles, SCAN_THREADS, 0, stream>>>(head, E, counts);
-    coalesce_compact_kernel<<<eb, 256, 0, stream>>>(keys_a, dst_s, vals_a, head, eid, E, edge_src, edge_dst, e_id, info);
-    return check_launch("npi_sample_coalesce");
-}
-
-extern "C" int64_t npi_negative_distinct_workspace_bytes(int64_t W) {
-    if (W < 0 || W >= (int64_t)0x7fffffff) return -1;
-    return sort_layout(W, 0).total;
-}
-
-extern "C" int npi_negative_distinct(const int32_t* cand_src, const int32_t* cand_dst, int64_t W, int64_t n_src, int64_t n_dst, int64_t M,
-                                     int64_t* out_src, int64_t* out_dst, int32_t* info, void* workspace, int64_t workspace_bytes,
-                                     void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(W >= 0 && W < (int64_t)0x7fffffff && M >= 0, "npi_negative_distinct: bad size");
-    NPI_REQUIRE(n_src >= 1 && n_src < (int64_t)0x7fffffff && n_dst >= 1 && n_dst < (int64_t)0x7fffffff,
-                "npi_negative_distinct: bad id bound");
-    NPI_REQUIRE(info, "npi_negative_distinct: null pointer");
-    if (W == 0) return NPI_OK;
-    NPI_REQUIRE(cand_src && cand_dst && workspace && (M == 0 || (out_src && out_dst)), "npi_negative_distinct: null pointer");
-    NPI_REQUIRE(((uintptr_t)workspace & 15) == 0, "npi_negative_distinct: workspace must be 16-byte aligned");
-    SortLayout L = sort_layout(W, 0);
-    if (workspace_bytes < L.total) {
-        set_error("npi_negative_distinct: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)L.total);
-        return NPI_ERR_ARG;
-    }
-    char* ws = (char*)workspace;
-    uint32_t* keys_a = (uint32_t*)(ws + L.off_keys_a);
-    uint32_t* keys_b = (uint32_t*)(ws + L.off_keys_b);
-    int32_t* vals_a = (int32_t*)(ws + L.off_vals_a);
-    int32_t* vals_b = (int32_t*)(ws + L.off_vals_b);
-    int32_t* counts = (int32_t*)(ws + L.off_counts);
-    int32_t* tiles = (int32_t*)(ws + L.off_tiles);
-    int dbits = 1, sbits = 1;
-    while (((int64_t)1 << dbits) < n_dst) ++dbits;         // ids lie in [0, n)
-    while (((int64_t)1 << sbits) < n_src) ++sbits;
-    const uint32_t invalid = (uint32_t)1 << sbits;         // sbits <= 31: one bit above every source id
-    const unsigned wb = (unsigned)ceil_div(W, 256);
-    negative_keys_kernel<<<wb, 256, 0, stream>>>(cand_dst, W, n_dst, keys_a, vals_a);
-    radix_sort_pairs(keys_a, keys_b, vals_a, vals_b, W, dbits, L, counts, tiles, stream);
-    negative_rekey_kernel<<<wb, 256, 0, stream>>>(cand_src, cand_dst, vals_a, W, n_src, n_dst, invalid, keys_a);
-    radix_sort_pairs(keys_a, keys_b, vals_a, vals_b, W, sbits + 1, L, counts, tiles, stream);
-    // the sort's second pair of buffers is free now: keep (scanned in place into the output positions) and a copy of it; the
-    // histogram buffer (W / 16 words) holds the scan's tile sums (W / SCAN_TILE of them)
-    int32_t* keep = (int32_t*)keys_b;
-    int32_t* kept = vals_b;
-    const int64_t ntiles = ceil_div(W, SCAN_TILE);
-    (void)hipMemsetAsync(keep, 0, (size_t)W * sizeof(int32_t), stream);
-    (void)hipMemsetAsync(kept, 0, (size_t)W * sizeof(int32_t), stream);
-    (void)hipMemsetAsync(info, 0, 2 * sizeof(int32_t), stream);
-    negative_heads_kernel<<<wb, 256, 0, stream>>>(keys_a, vals_a, cand_dst, W, invalid, keep, kept);
-    scan_tiles_kernel<<<(unsigned)ntiles, SCAN_THREADS, 0, stream>>>(keep, W, counts);
-    scan_sums_kernel<<<1, SCAN_THREADS, 0, stream>>>(counts, ntiles);
-    scan_add_kernel<<<(unsigned)ntiles, SCAN_THREADS, 0, stream>>>(keep, W, counts);
-    negative_compact_kernel<<<wb, 256, 0, stream>>>(cand_src, cand_dst, keep, kept, W, M, out_src, out_dst, info);
-    return check_launch("npi_negative_distinct");
-}
-
-extern "C" int64_t npi_topk_sorted_workspace_bytes(int64_t N) {
-    if (N < 0) return -1;
-    return sort_layout(N, 0).total;
-}
-
-extern "C" int npi_topk_select_sorted(const float* score, const int64_t* batch, const int32_t* graph_ptr, int64_t N, int64_t B,
-                                      float ratio, int32_t* out_ptr, int32_t* perm, int32_t* remap, void* workspace,
-                                      int64_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(N >= 0 && B >= 0 && N < (int64_t)0x7fffffff && ratio > 0.f && ratio <= 1.f, "npi_topk_select_sorted: bad argument");
-    NPI_REQUIRE(out_ptr && graph_ptr && (N == 0 || (score && batch && perm && remap && workspace)), "npi_topk_select_sorted: null pointer");
-    topk_kept_offsets_kernel<<<1, 256, 0, stream>>>(graph_ptr, (int)B, ratio, out_ptr);
-    if (N == 0 || B == 0) return check_launch("npi_topk_select_sorted");
-    SortLayout L = sort_layout(N, 0);
-    if (workspace_bytes < L.total) {
-        set_error("npi_topk_select_sorted: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)L.total);
-        return NPI_ERR_WORKSPACE;
-    }
-    char* ws = (char*)workspace;
-    uint32_t* keys_a = (uint32_t*)(ws + L.off_keys_a);
-    uint32_t* keys_b = (uint32_t*)(ws + L.off_keys_b);
-    int32_t* vals_a = (int32_t*)(ws + L.off_vals_a);
-    int32_t* vals_b = (int32_t*)(ws + L.off_vals_b);
-    int32_t* counts = (int32_t*)(ws + L.off_counts);
-    int32_t* tiles = (int32_t*)(ws + L.off_tiles);
-    const unsigned nb = (unsigned)ceil_div(N, 256);
-    topk_score_keys_kernel<<<nb, 256, 0, stream>>>(score, N, keys_a, vals_a);
-    radix_sort_pairs(keys_a, keys_b, vals_a, vals_b, N, 32, L, counts, tiles, stream);
-    topk_graph_keys_kernel<<<nb, 256, 0, stream>>>(batch, vals_a, N, keys_a);
-    int bits = 1;
-    while (((int64_t)1 << bits) < B) ++bits;             // graph ids lie in [0, B)
-    radix_sort_pairs(keys_a, keys_b, vals_a, vals_b, N, bits, L, counts, tiles, stream);
-    topk_take_kernel<<<nb, 256, 0, stream>>>(keys_a, vals_a, N, graph_ptr, out_ptr, perm, remap);
-    return check_launch("npi_topk_select_sorted");
 }
 
 // ---- the CSR of a pooled graph from the CSR of its parent: no sort ------------------------------------------------------
@@ -853,187 +340,8 @@ extern "C" int npi_csr_filter(const int32_t* rowptr, const int32_t* col, const i
         csr_filter_fill_kernel<<<tiles, 256, 0, stream>>>(rowptr, col, eid, perm, remap, newpos, (int)n_out, cnt, tile_total,
                                                           rowptr_o, col_o, eid_o, rowidx_o);
     }
-    const int64_t n_items = num_items_of(nnz_max_out, item_edges);
-    item_rows_kernel<<<(unsigned)ceil_div(n_items + 1, 256), 256, 0, stream>>>(rowptr_o, n_out, n_items, (int)item_edges, item_row_o);
+    write_item_rows(rowptr_o, n_out, nnz_max_out, item_edges, item_row_o, stream);
     return check_launch("npi_csr_filter");
-}
-
-// ---- hub plan: the heaviest rows of a side, for the streaming aggregation (segsum_hub.hip) --------------------------------------
-// npi_hub_plan picks the up to h_max rows with the most entries among those with at least min_degree entries (ties: the lower row
-// first), writes bit j of mask[c] for every entry (hub j, c), drops hubs that hold a column twice (a bit cannot count twice) and
-// leaves the plan EMPTY (info[0] = 0) unless the remaining hubs' entries add up to min_entries.  npi_hub_light_side writes the same
-// side without the hub rows' entries.  All of it once per graph and side; integer atomics only.
-namespace npi {
-
-constexpr int HUB_CAND_CAP = 4096;           // rows with >= min_degree entries the selection looks at (more: the plan is empty)
-constexpr int HUB_WS_CNT = 0, HUB_WS_IDENT = 1, HUB_WS_PRELIM = 8, HUB_WS_BAD = HUB_WS_PRELIM + NPI_HUB_MAX,
-              HUB_WS_REMAP = HUB_WS_BAD + NPI_HUB_MAX, HUB_WS_CAND = HUB_WS_REMAP + NPI_HUB_MAX, HUB_WS_ELEMS = HUB_WS_CAND + HUB_CAND_CAP;
-constexpr int HUB_WORDS = NPI_HUB_MAX / 32;
-
-__global__ void hub_candidates_kernel(const int32_t* __restrict__ rowptr, int64_t N, int32_t min_degree, int32_t* __restrict__ ws) {
-    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= N || rowptr[r + 1] - rowptr[r] < min_degree) return;
-    const int i = atomicAdd(&ws[HUB_WS_CNT], 1);
-    if (i < HUB_CAND_CAP) ws[HUB_WS_CAND + i] = (int32_t)r;
-}
-
-// rank of every candidate by (degree descending, row ascending); the first h_max are the preliminary hubs, in that order
-__global__ void __launch_bounds__(1024)
-hub_select_kernel(const int32_t* __restrict__ rowptr, int h_max, int32_t* __restrict__ ws, int32_t* __restrict__ info) {
-    __shared__ int32_t rows[HUB_CAND_CAP], degs[HUB_CAND_CAP];
-    const int seen = ws[HUB_WS_CNT];
-    const int n = seen > HUB_CAND_CAP ? 0 : seen;
-    for (int c = threadIdx.x; c < n; c += blockDim.x) {
-        const int32_t r = ws[HUB_WS_CAND + c];
-        rows[c] = r;
-        degs[c] = rowptr[r + 1] - rowptr[r];
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < n; c += blockDim.x) {
-        const int32_t r = rows[c], d = degs[c];
-        int rank = 0;
-        for (int o = 0; o < n; ++o) rank += (degs[o] > d || (degs[o] == d && rows[o] < r)) ? 1 : 0;
-        if (rank < h_max) ws[HUB_WS_PRELIM + rank] = r;
-    }
-    if (threadIdx.x == 0) {
-        info[2] = seen;
-        info[3] = n < h_max ? n : h_max;
-    }
-    if (threadIdx.x < NPI_HUB_MAX) ws[HUB_WS_BAD + threadIdx.x] = 0;
-}
-
-__global__ void __launch_bounds__(256)
-hub_mask_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t n_cols, int32_t* __restrict__ ws,
-                const int32_t* __restrict__ info, uint32_t* __restrict__ mask) {
-    const int j = blockIdx.y;
-    if (j >= info[3]) return;
-    const int32_t r = ws[HUB_WS_PRELIM + j];
-    const uint32_t bit = 1u << (j & 31);
-    const int64_t p1 = rowptr[r + 1];
-    for (int64_t p = (int64_t)rowptr[r] + blockIdx.x * 256 + threadIdx.x; p < p1; p += (int64_t)gridDim.x * 256) {
-        const int32_t c = col[p];
-        if (c < 0 || c >= n_cols) { ws[HUB_WS_BAD + j] = 1; continue; }
-        const uint32_t old = atomicOr(&mask[(int64_t)c * HUB_WORDS + (j >> 5)], bit);
-        if (old & bit) ws[HUB_WS_BAD + j] = 1;                 // the column a second time: this row cannot be a hub
-    }
-}
-
-__global__ void hub_finalize_kernel(const int32_t* __restrict__ rowptr, int64_t min_entries, int32_t* __restrict__ ws,
-                                    int32_t* __restrict__ info, int32_t* __restrict__ hub_rows) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int h0 = info[3];
-    int h = 0;
-    int64_t total = 0;
-    for (int j = 0; j < NPI_HUB_MAX; ++j) {
-        int m = -1;
-        if (j < h0 && ws[HUB_WS_BAD + j] == 0) {
-            const int32_t r = ws[HUB_WS_PRELIM + j];
-            hub_rows[h] = r;
-            total += rowptr[r + 1] - rowptr[r];
-            m = h++;
-        }
-        ws[HUB_WS_REMAP + j] = m;
-    }
-    if (total < min_entries || total >= ((int64_t)1 << 31)) h = 0;
-    for (int j = h; j < NPI_HUB_MAX; ++j) hub_rows[j] = -1;
-    ws[HUB_WS_IDENT] = (h == h0) ? 1 : 0;
-    info[0] = h;
-    info[1] = h > 0 ? (int32_t)total : 0;
-}
-
-// the bits of the dropped hubs leave the masks, the others move down (only when a hub was dropped)
-__global__ void hub_mask_remap_kernel(int64_t n_cols, const int32_t* __restrict__ ws, const int32_t* __restrict__ info,
-                                      uint32_t* __restrict__ mask) {
-    if (ws[HUB_WS_IDENT] != 0 || info[0] == 0) return;
-    int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_cols) return;
-    uint32_t out[HUB_WORDS] = {};
-    bool any = false;
-    for (int q = 0; q < HUB_WORDS; ++q) {
-        uint32_t m = mask[c * HUB_WORDS + q];
-        any |= m != 0u;
-        while (m != 0u) {
-            const int b = __builtin_ctz(m);
-            m &= m - 1u;
-            const int nj = ws[HUB_WS_REMAP + q * 32 + b];
-            if (nj >= 0) out[nj >> 5] |= 1u << (nj & 31);
-        }
-    }
-    if (!any) return;
-    for (int q = 0; q < HUB_WORDS; ++q) mask[c * HUB_WORDS + q] = out[q];
-}
-
-__global__ void __launch_bounds__(256)
-hub_light_rowptr_kernel(const int32_t* __restrict__ rowptr, int64_t N, const int32_t* __restrict__ hub_rows, int H,
-                        int32_t* __restrict__ rowptr_l) {
-    __shared__ int32_t hr[NPI_HUB_MAX], hd[NPI_HUB_MAX];
-    if (threadIdx.x < H) {
-        const int32_t r = hub_rows[threadIdx.x];
-        hr[threadIdx.x] = r;
-        hd[threadIdx.x] = rowptr[r + 1] - rowptr[r];
-    }
-    __syncthreads();
-    int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r > N) return;
-    int32_t removed = 0;
-    for (int j = 0; j < H; ++j) removed += (hr[j] < r) ? hd[j] : 0;
-    rowptr_l[r] = rowptr[r] - removed;
-}
-
-__global__ void hub_light_entries_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                         const int32_t* __restrict__ eid, const int32_t* __restrict__ rowidx, int64_t N, int64_t nnz_max,
-                                         const int32_t* __restrict__ rowptr_l, int64_t nnz_max_l, int32_t* __restrict__ col_l,
-                                         int32_t* __restrict__ eid_l, int32_t* __restrict__ rowidx_l) {
-    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= nnz_max || p >= rowptr[N]) return;
-    const int32_t r = rowidx[p];
-    if (r < 0 || r >= N || rowptr_l[r + 1] == rowptr_l[r]) return;      // an entry of a hub row
-    const int64_t q = p - (rowptr[r] - rowptr_l[r]);
-    if (q < 0 || q >= nnz_max_l) return;
-    col_l[q] = col[p];
-    eid_l[q] = eid[p];
-    rowidx_l[q] = r;
-}
-
-}  // namespace npi
-
-extern "C" int64_t npi_hub_plan_workspace_elems(void) { return HUB_WS_ELEMS; }
-
-extern "C" int npi_hub_plan(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t n_cols, int64_t nnz_max, int64_t h_max,
-                            int64_t min_degree, int64_t min_entries, int32_t* hub_rows, uint32_t* mask, int32_t* info,
-                            int32_t* workspace, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(N > 0 && n_cols > 0 && nnz_max > 0 && N < ((int64_t)1 << 31) && n_cols < ((int64_t)1 << 31), "npi_hub_plan: bad size");
-    NPI_REQUIRE(h_max >= 1 && h_max <= NPI_HUB_MAX, "npi_hub_plan: h_max must be in [1, NPI_HUB_MAX]");
-    NPI_REQUIRE(min_degree >= 1 && min_degree < ((int64_t)1 << 31) && min_entries >= 0, "npi_hub_plan: bad threshold");
-    NPI_REQUIRE(rowptr && col && hub_rows && mask && info && workspace, "npi_hub_plan: null pointer");
-    (void)hipMemsetAsync(workspace, 0, HUB_WS_CAND * sizeof(int32_t), stream);
-    (void)hipMemsetAsync(info, 0, 4 * sizeof(int32_t), stream);
-    (void)hipMemsetAsync(mask, 0, (size_t)n_cols * HUB_WORDS * sizeof(uint32_t), stream);
-    hub_candidates_kernel<<<(unsigned)ceil_div(N, 256), 256, 0, stream>>>(rowptr, N, (int32_t)min_degree, workspace);
-    hub_select_kernel<<<1, 1024, 0, stream>>>(rowptr, (int)h_max, workspace, info);
-    hub_mask_kernel<<<dim3(64, NPI_HUB_MAX), 256, 0, stream>>>(rowptr, col, n_cols, workspace, info, mask);
-    hub_finalize_kernel<<<1, 64, 0, stream>>>(rowptr, min_entries, workspace, info, hub_rows);
-    hub_mask_remap_kernel<<<(unsigned)ceil_div(n_cols, 256), 256, 0, stream>>>(n_cols, workspace, info, mask);
-    return check_launch("npi_hub_plan");
-}
-
-extern "C" int npi_hub_light_side(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const int32_t* rowidx, int64_t N,
-                                  int64_t nnz_max, const int32_t* hub_rows, int64_t H, int64_t nnz_max_light, int64_t item_edges,
-                                  int32_t* rowptr_l, int32_t* col_l, int32_t* eid_l, int32_t* rowidx_l, int32_t* item_row_l,
-                                  void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(N > 0 && nnz_max > 0 && nnz_max_light >= 0 && nnz_max_light <= nnz_max, "npi_hub_light_side: bad size");
-    NPI_REQUIRE(H >= 1 && H <= NPI_HUB_MAX, "npi_hub_light_side: H must be in [1, NPI_HUB_MAX]");
-    NPI_REQUIRE(item_edges_ok(item_edges), "npi_hub_light_side: item_edges must be 64 or NPI_ITEM_EDGES");
-    NPI_REQUIRE(rowptr && col && eid && rowidx && hub_rows && rowptr_l && col_l && eid_l && rowidx_l && item_row_l,
-                "npi_hub_light_side: null pointer");
-    hub_light_rowptr_kernel<<<(unsigned)ceil_div(N + 1, 256), 256, 0, stream>>>(rowptr, N, hub_rows, (int)H, rowptr_l);
-    hub_light_entries_kernel<<<(unsigned)ceil_div(nnz_max, 256), 256, 0, stream>>>(rowptr, col, eid, rowidx, N, nnz_max, rowptr_l,
-                                                                                 nnz_max_light, col_l, eid_l, rowidx_l);
-    const int64_t n_items = num_items_of(nnz_max_light, item_edges);
-    item_rows_kernel<<<(unsigned)ceil_div(n_items + 1, 256), 256, 0, stream>>>(rowptr_l, N, n_items, (int)item_edges, item_row_l);
-    return check_launch("npi_hub_light_side");
 }
 
 extern "C" int npi_edge_positions(const int32_t* eid, const int32_t* rowptr, int64_t N, int64_t nnz_max,

@@ -1,6 +1,6 @@
 // Per-entry weight plumbing for the weighted convs: GCNConv.norm (PyG 1.4.2, a7 in SURVEY.md 8(a))
 // and edge_weight handling of add_remaining_self_loops.  Integer/index work plus one rsqrt per
-// entry; all arrays are in CSR entry order (see csr_build.hip).
+// entry; all arrays are in CSR entry order (see csr_build.hip; the sort behind it: sort.hip).
 #include "npi_common.h"
 
 namespace npi {

@@ -78,6 +78,8 @@ constexpr int64_t NPI_SMALL_GRAPH_ENTRIES = (int64_t)1 << 22;
 inline int item_edges_for(int64_t nnz_max) { return nnz_max < NPI_SMALL_GRAPH_ENTRIES ? 64 : NPI_ITEM_EDGES; }
 inline bool item_edges_ok(int64_t item) { return item == 64 || item == NPI_ITEM_EDGES; }
 inline int64_t num_items_of(int64_t nnz_max, int64_t item) { return nnz_max <= 0 ? 0 : ceil_div(nnz_max, item); }
+// item_row[0 .. num_items_of(nnz_max, item_edges)] of a finished rowptr[N + 1] (the kernel: csr_build.hip)
+void write_item_rows(const int32_t* rowptr, int64_t N, int64_t nnz_max, int64_t item_edges, int32_t* item_row, hipStream_t stream);
 
 }  // namespace npi
 

@@ -13,7 +13,7 @@
 // Integer / index work is bit-exact; sums are in a fixed order (reproducible).
 #include <algorithm>
 #include <initializer_list>
-#include "npi_common.h"
+#include "sort.h"
 
 namespace npi {
 
@@ -59,8 +59,29 @@ __global__ void graph_bounds_kernel(const int64_t* __restrict__ batch, int64_t N
     graph_ptr[g] = (int32_t)lo;
 }
 
-// out_ptr[g] = sum_{g' < g} ceil(ratio * n_g'); one workgroup, B is small (graphs per batch).  The same launch clears the
-// status word and presets remap to -1 (blocks 1 ..: one element per thread) -- three launches in one.
+// out_ptr[g] = sum_{g' < g} min(ceil(ratio n_g'), n_g') in f32 arithmetic, out_ptr[B] = the sum over all graphs; one workgroup of 256
+// threads, B is small (graphs per batch)
+__device__ __forceinline__ void topk_kept_offsets(const int32_t* __restrict__ graph_ptr, int B, float ratio,
+                                                  int32_t* __restrict__ out_ptr) {
+    __shared__ int lds[256];
+    int carry = 0;
+    for (int base = 0; base < B; base += 256) {
+        const int g = base + threadIdx.x;
+        int k = 0;
+        if (g < B) {
+            const int n = graph_ptr[g + 1] - graph_ptr[g];
+            k = min((int)ceilf(ratio * (float)n), n);
+        }
+        int total;
+        const int excl = block_exclusive_scan<256>(k, lds, &total);
+        if (g < B) out_ptr[g] = carry + excl;
+        carry += total;
+    }
+    if (threadIdx.x == 0) out_ptr[B] = carry;
+}
+
+// The kept-row offsets (block 0); the same launch clears the status word and presets remap to -1 (blocks 1 ..: one element per
+// thread) -- three launches in one.
 __global__ void __launch_bounds__(256)
 topk_counts_kernel(const int32_t* __restrict__ graph_ptr, int B, float ratio, int32_t* __restrict__ out_ptr,
                    int32_t* __restrict__ status, int32_t* __restrict__ remap, int64_t N) {
@@ -70,29 +91,7 @@ topk_counts_kernel(const int32_t* __restrict__ graph_ptr, int B, float ratio, in
         return;
     }
     if (threadIdx.x == 0) *status = 0;
-    __shared__ int lds[256];
-    int carry = 0;
-    for (int base = 0; base < B; base += 256) {
-        const int g = base + threadIdx.x;
-        int k = 0;
-        if (g < B) {
-            const int n = graph_ptr[g + 1] - graph_ptr[g];
-            k = (int)ceilf(ratio * (float)n);
-            k = min(k, n);
-        }
-        lds[threadIdx.x] = k;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            int t = (threadIdx.x >= off) ? lds[threadIdx.x - off] : 0;
-            __syncthreads();
-            lds[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (g < B) out_ptr[g] = carry + lds[threadIdx.x] - k;
-        carry += lds[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out_ptr[B] = carry;
+    topk_kept_offsets(graph_ptr, B, ratio, out_ptr);
 }
 
 // sortable key: ascending key order == (score descending, node index ascending)
@@ -140,6 +139,42 @@ topk_select_kernel(const float* __restrict__ score, const int32_t* __restrict__ 
         perm[ob + i] = node;
         remap[node] = ob + i;
     }
+}
+
+// ---- TopKPooling selection for graphs of ANY size (topk_select_kernel sorts a graph's scores in LDS: up to 16,384 nodes) -----------
+// Two stable radix sorts of the whole batch: by score (descending; the sort is stable over the node index, so equal scores
+// keep the lower index first -- torch.sort(descending=True, stable) order, as the LDS kernel), then by graph id: position
+// graph_ptr[g] + r of the result is the node of graph g with the r-th highest score.
+__global__ void topk_score_keys_kernel(const float* __restrict__ score, int64_t N, uint32_t* __restrict__ keys,
+                                       int32_t* __restrict__ vals) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const float f = score[i];
+    uint32_t u = __float_as_uint(f);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);     // ascending-orderable
+    keys[i] = (f != f) ? 0u : ~u;                       // descending; NaN first, as torch.sort treats it as the largest
+    vals[i] = (int32_t)i;
+}
+__global__ void topk_graph_keys_kernel(const int64_t* __restrict__ batch, const int32_t* __restrict__ vals, int64_t N,
+                                       uint32_t* __restrict__ keys) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < N) keys[q] = (uint32_t)batch[vals[q]];
+}
+__global__ void __launch_bounds__(256)
+topk_kept_offsets_kernel(const int32_t* __restrict__ graph_ptr, int B, float ratio, int32_t* __restrict__ out_ptr) {
+    topk_kept_offsets(graph_ptr, B, ratio, out_ptr);
+}
+__global__ void topk_take_kernel(const uint32_t* __restrict__ graph_of, const int32_t* __restrict__ node_of, int64_t N,
+                                 const int32_t* __restrict__ graph_ptr, const int32_t* __restrict__ out_ptr,
+                                 int32_t* __restrict__ perm, int32_t* __restrict__ remap) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= N) return;
+    const int g = (int)graph_of[q], node = node_of[q];
+    const int rank = (int)(q - graph_ptr[g]);
+    const int k = out_ptr[g + 1] - out_ptr[g];
+    const int at = rank < k ? out_ptr[g] + rank : -1;
+    if (at >= 0) perm[at] = node;
+    remap[node] = at;                                    // every node occurs exactly once: kept -> new id, dropped -> -1
 }
 
 // x'[q] = x[perm[q]] * score[perm[q]], batch'[q] = batch[perm[q]]; one wave per output row
@@ -192,17 +227,10 @@ scan_small_kernel(int32_t* __restrict__ v, int n, int32_t* __restrict__ total) {
     for (int base = 0; base < n; base += 256) {
         const int i = base + threadIdx.x;
         const int val = i < n ? v[i] : 0;
-        lds[threadIdx.x] = val;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            int t = (threadIdx.x >= off) ? lds[threadIdx.x - off] : 0;
-            __syncthreads();
-            lds[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < n) v[i] = carry + lds[threadIdx.x] - val;
-        carry += lds[255];
-        __syncthreads();
+        int sum;
+        const int excl = block_exclusive_scan<256>(val, lds, &sum);
+        if (i < n) v[i] = carry + excl;
+        carry += sum;
     }
     if (threadIdx.x == 0) *total = carry;
 }
@@ -631,6 +659,33 @@ extern "C" int npi_topk_select(const float* score, const int32_t* graph_ptr, int
             topk_select_kernel<16384, 1024><<<(unsigned)B, 1024, 0, stream>>>(score, graph_ptr, out_ptr, (int)B, perm, remap, status);
     }
     return check_launch("npi_topk_select");
+}
+
+extern "C" int64_t npi_topk_sorted_workspace_bytes(int64_t N) {
+    if (N < 0) return -1;
+    return PairSort::bytes(N);
+}
+
+extern "C" int npi_topk_select_sorted(const float* score, const int64_t* batch, const int32_t* graph_ptr, int64_t N, int64_t B,
+                                      float ratio, int32_t* out_ptr, int32_t* perm, int32_t* remap, void* workspace,
+                                      int64_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    NPI_REQUIRE(N >= 0 && B >= 0 && N < (int64_t)0x7fffffff && ratio > 0.f && ratio <= 1.f, "npi_topk_select_sorted: bad argument");
+    NPI_REQUIRE(out_ptr && graph_ptr && (N == 0 || (score && batch && perm && remap && workspace)), "npi_topk_select_sorted: null pointer");
+    topk_kept_offsets_kernel<<<1, 256, 0, stream>>>(graph_ptr, (int)B, ratio, out_ptr);
+    if (N == 0 || B == 0) return check_launch("npi_topk_select_sorted");
+    PairSort ps;
+    if (!ps.carve(workspace, workspace_bytes, N)) {
+        set_error("npi_topk_select_sorted: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)PairSort::bytes(N));
+        return NPI_ERR_WORKSPACE;
+    }
+    const unsigned nb = (unsigned)ceil_div(N, 256);
+    topk_score_keys_kernel<<<nb, 256, 0, stream>>>(score, N, ps.keys_a, ps.vals_a);
+    ps.sort(32, stream);
+    topk_graph_keys_kernel<<<nb, 256, 0, stream>>>(batch, ps.vals_a, N, ps.keys_a);
+    ps.sort(key_bits(B), stream);                        // graph ids lie in [0, B)
+    topk_take_kernel<<<nb, 256, 0, stream>>>(ps.keys_a, ps.vals_a, N, graph_ptr, out_ptr, perm, remap);
+    return check_launch("npi_topk_select_sorted");
 }
 
 extern "C" int npi_topk_gather(const float* x, int64_t ldx, const float* score, const int64_t* batch,

@@ -19,7 +19,7 @@
 // select over the 64-bit keys, 8 bits a pass, stopping at the first pass after which every remaining key is taken.  A budget too
 // large for LDS (a fraction of a hub) runs the same select straight over the positions, hashing once per pass.  Entries (col, eid)
 // are read for the winners only.  Integer LDS counters, no float anywhere except the fraction's ceil (in double, as the host's).
-#include "npi_common.h"
+#include "sort.h"
 
 namespace npi {
 
@@ -305,23 +305,16 @@ relabel_scan_kernel(int32_t* __restrict__ chunk_cnt, int64_t nb, const int64_t* 
     const int64_t b = min(nb, t * per), e = min(nb, b + per);
     long long s = 0;
     for (int64_t g = b; g < e; ++g) s += chunk_cnt[g];
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {                   // Hillis-Steele inclusive scan of the thread sums
-        const long long v = (t >= d) ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    long long run = (t > 0) ? part[t - 1] : 0;
+    long long all;
+    long long run = block_exclusive_scan<1024>(s, part, &all);
     for (int64_t g = b; g < e; ++g) {
         const int c = chunk_cnt[g];
         chunk_cnt[g] = (int)run;
         run += c;
     }
     if (t == 1023) {
-        chunk_cnt[nb] = (int)part[1023];                   // at most N < 2^31 marks
-        info[0] = (int)part[1023];
+        chunk_cnt[nb] = (int)all;                          // at most N < 2^31 marks
+        info[0] = (int)all;
         int64_t E = offsets != nullptr ? offsets[n] : n_out;       // (the union of the hops has no offsets: its entry count is n_out)
         E = E < n_out ? E : n_out;
         info[1] = (int)(E < 0 ? 0 : E);
@@ -415,6 +408,53 @@ union_local_kernel(const int32_t* __restrict__ scratch, int64_t N, const int32_t
         const int64_t v = b_id[i];
         sub_b_id[i] = (v >= 0 && v < N) ? (int64_t)scratch[v] - 1 : -1;
     }
+}
+
+// ---- merging the equal (source, target) pairs of a sampled subgraph (npi_sample_coalesce; the sort and the scan: sort.h) -------------------
+// Replaces the `idx = src * num_nodes + dst; idx.unique()` + `scatter_` lines of PyG 1.4.2 NeighborSampler.__produce_subgraph__.  LSD over
+// the pair: the stable sort by target first, then the stable sort by source; val = the entry's index, so equal pairs stay in entry order.
+__global__ void coalesce_keys_kernel(const int32_t* __restrict__ dst_l, int64_t E, uint32_t* __restrict__ keys, int32_t* __restrict__ vals) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= E) return;
+    keys[i] = (uint32_t)dst_l[i];
+    vals[i] = (int32_t)i;
+}
+__global__ void coalesce_rekey_kernel(const int32_t* __restrict__ src_l, const int32_t* __restrict__ vals, int64_t E,
+                                      uint32_t* __restrict__ keys) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < E) keys[p] = (uint32_t)src_l[vals[p]];
+}
+// dst_s[p] = the target of the entry sorted to p (its source: the sort's key); head[p] = 1 where a run of equal pairs starts
+__global__ void coalesce_heads_kernel(const uint32_t* __restrict__ src_s, const int32_t* __restrict__ vals, const int32_t* __restrict__ dst_l,
+                                      int64_t E, int32_t* __restrict__ dst_s, int32_t* __restrict__ head) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= E) return;
+    const int32_t d = dst_l[vals[p]];
+    dst_s[p] = d;
+    head[p] = (p == 0 || src_s[p - 1] != src_s[p] || dst_l[vals[p - 1]] != d) ? 1 : 0;
+}
+// pos = the exclusive scan of head.  The head of a run writes the pair and the smallest eid of its run (runs are short: a pair
+// repeats once per hop it was sampled in and once per parallel edge); info[0] = the number of runs
+__global__ void coalesce_compact_kernel(const uint32_t* __restrict__ src_s, const int32_t* __restrict__ dst_s, const int32_t* __restrict__ vals,
+                                        const int32_t* __restrict__ pos, const int32_t* __restrict__ eid, int64_t E,
+                                        int64_t* __restrict__ edge_src, int64_t* __restrict__ edge_dst, int64_t* __restrict__ e_id,
+                                        int32_t* __restrict__ info) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= E) return;
+    const uint32_t s = src_s[p];
+    const int32_t d = dst_s[p];
+    const bool head = p == 0 || src_s[p - 1] != s || dst_s[p - 1] != d;
+    const int64_t q = pos[p];                                    // q <= p < E: within the caller's bound
+    if (p == E - 1) info[0] = (int32_t)(q + (head ? 1 : 0));
+    if (!head) return;
+    int32_t m = eid[vals[p]];
+    for (int64_t r = p + 1; r < E && src_s[r] == s && dst_s[r] == d; ++r) {
+        const int32_t e = eid[vals[r]];
+        m = e < m ? e : m;
+    }
+    edge_src[q] = (int64_t)(int32_t)s;
+    edge_dst[q] = d;
+    e_id[q] = m;
 }
 
 }  // namespace npi
@@ -520,4 +560,37 @@ extern "C" int npi_sample_union(const int32_t* src_g, const int32_t* dst_g, int6
                                                  status);
     if (N > 0) (void)hipMemsetAsync(scratch, 0, (size_t)N * sizeof(int32_t), stream);   // the scratch is left as it was found
     return check_launch("npi_sample_union");
+}
+
+extern "C" int64_t npi_sample_coalesce_workspace_bytes(int64_t E) {
+    if (E < 0 || E >= (int64_t)0x7fffffff) return -1;
+    return PairSort::bytes(E);
+}
+
+extern "C" int npi_sample_coalesce(const int32_t* src_l, const int32_t* dst_l, const int32_t* eid, int64_t E, int64_t U, int64_t* edge_src,
+                                   int64_t* edge_dst, int64_t* e_id, int32_t* info, void* workspace, int64_t workspace_bytes,
+                                   void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    NPI_REQUIRE(E >= 0 && E < (int64_t)0x7fffffff && U >= 0 && U < (int64_t)0x7fffffff, "npi_sample_coalesce: bad size");
+    if (E == 0) return NPI_OK;
+    NPI_REQUIRE(src_l && dst_l && eid && edge_src && edge_dst && e_id && info && workspace, "npi_sample_coalesce: null pointer");
+    NPI_REQUIRE(((uintptr_t)workspace & 15) == 0, "npi_sample_coalesce: workspace must be 16-byte aligned");
+    PairSort ps;
+    if (!ps.carve(workspace, workspace_bytes, E)) {
+        set_error("npi_sample_coalesce: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)PairSort::bytes(E));
+        return NPI_ERR_WORKSPACE;
+    }
+    const int bits = key_bits(U);                        // local ids lie in [0, U)
+    const unsigned eb = (unsigned)ceil_div(E, 256);
+    coalesce_keys_kernel<<<eb, 256, 0, stream>>>(dst_l, E, ps.keys_a, ps.vals_a);
+    ps.sort(bits, stream);
+    coalesce_rekey_kernel<<<eb, 256, 0, stream>>>(src_l, ps.vals_a, E, ps.keys_a);
+    ps.sort(bits, stream);
+    // the sort's free buffers (PairSort): the sorted targets, the run heads and the scan's tile sums
+    int32_t* dst_s = ps.vals_b;
+    int32_t* head = (int32_t*)ps.keys_b;
+    coalesce_heads_kernel<<<eb, 256, 0, stream>>>(ps.keys_a, ps.vals_a, dst_l, E, dst_s, head);
+    exclusive_scan_i32(head, E, ps.counts, stream);
+    coalesce_compact_kernel<<<eb, 256, 0, stream>>>(ps.keys_a, dst_s, ps.vals_a, head, eid, E, edge_src, edge_dst, e_id, info);
+    return check_launch("npi_sample_coalesce");
 }

@@ -1,4 +1,4 @@
-// The heaviest rows of a CSR side ("hubs", csr_build.hip: npi_hub_plan) aggregated by STREAMING the source table once instead of
+// The heaviest rows of a CSR side ("hubs", picked by npi_hub_plan at the end of this file) aggregated by STREAMING the source table once instead of
 // gathering it: a hub whose row touches a sizeable fraction of all source rows re-reads the table row by row, and no cache holds a
 // table of a million 1 KiB rows.  Here every source row is fetched once per launch and added into the accumulators of the hubs its
 // mask word names (bit j of mask[r]: the side has an entry (hub j, r)).  f32, 256 columns, one table; deterministic: no float
@@ -187,4 +187,181 @@ extern "C" int npi_segsum_hub(const int32_t* hub_rows, int64_t H, const uint32_t
     hipLaunchKernelGGL(hub_finish_kernel, dim3((unsigned)H), dim3(FIN_WAVES * WAVE), 0, stream, partial, (int)n_slabs, hub_rows, rowptr,
                        mean, out, ldo, row_scales_out);
     return check_launch("npi_segsum_hub(finish)");
+}
+
+// ---- hub plan: the heaviest rows of a side, for the streaming aggregation above ---------------------------------------------------
+// npi_hub_plan picks the up to h_max rows with the most entries among those with at least min_degree entries (ties: the lower row
+// first), writes bit j of mask[c] for every entry (hub j, c), drops hubs that hold a column twice (a bit cannot count twice) and
+// leaves the plan EMPTY (info[0] = 0) unless the remaining hubs' entries add up to min_entries.  npi_hub_light_side writes the same
+// side without the hub rows' entries.  All of it once per graph and side; integer atomics only.
+namespace npi {
+
+constexpr int HUB_CAND_CAP = 4096;           // rows with >= min_degree entries the selection looks at (more: the plan is empty)
+constexpr int HUB_WS_CNT = 0, HUB_WS_IDENT = 1, HUB_WS_PRELIM = 8, HUB_WS_BAD = HUB_WS_PRELIM + NPI_HUB_MAX,
+              HUB_WS_REMAP = HUB_WS_BAD + NPI_HUB_MAX, HUB_WS_CAND = HUB_WS_REMAP + NPI_HUB_MAX, HUB_WS_ELEMS = HUB_WS_CAND + HUB_CAND_CAP;
+constexpr int HUB_WORDS = HUB_MASK_WORDS;
+
+__global__ void hub_candidates_kernel(const int32_t* __restrict__ rowptr, int64_t N, int32_t min_degree, int32_t* __restrict__ ws) {
+    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N || rowptr[r + 1] - rowptr[r] < min_degree) return;
+    const int i = atomicAdd(&ws[HUB_WS_CNT], 1);
+    if (i < HUB_CAND_CAP) ws[HUB_WS_CAND + i] = (int32_t)r;
+}
+
+// rank of every candidate by (degree descending, row ascending); the first h_max are the preliminary hubs, in that order
+__global__ void __launch_bounds__(1024)
+hub_select_kernel(const int32_t* __restrict__ rowptr, int h_max, int32_t* __restrict__ ws, int32_t* __restrict__ info) {
+    __shared__ int32_t rows[HUB_CAND_CAP], degs[HUB_CAND_CAP];
+    const int seen = ws[HUB_WS_CNT];
+    const int n = seen > HUB_CAND_CAP ? 0 : seen;
+    for (int c = threadIdx.x; c < n; c += blockDim.x) {
+        const int32_t r = ws[HUB_WS_CAND + c];
+        rows[c] = r;
+        degs[c] = rowptr[r + 1] - rowptr[r];
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < n; c += blockDim.x) {
+        const int32_t r = rows[c], d = degs[c];
+        int rank = 0;
+        for (int o = 0; o < n; ++o) rank += (degs[o] > d || (degs[o] == d && rows[o] < r)) ? 1 : 0;
+        if (rank < h_max) ws[HUB_WS_PRELIM + rank] = r;
+    }
+    if (threadIdx.x == 0) {
+        info[2] = seen;
+        info[3] = n < h_max ? n : h_max;
+    }
+    if (threadIdx.x < NPI_HUB_MAX) ws[HUB_WS_BAD + threadIdx.x] = 0;
+}
+
+__global__ void __launch_bounds__(256)
+hub_mask_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t n_cols, int32_t* __restrict__ ws,
+                const int32_t* __restrict__ info, uint32_t* __restrict__ mask) {
+    const int j = blockIdx.y;
+    if (j >= info[3]) return;
+    const int32_t r = ws[HUB_WS_PRELIM + j];
+    const uint32_t bit = 1u << (j & 31);
+    const int64_t p1 = rowptr[r + 1];
+    for (int64_t p = (int64_t)rowptr[r] + blockIdx.x * 256 + threadIdx.x; p < p1; p += (int64_t)gridDim.x * 256) {
+        const int32_t c = col[p];
+        if (c < 0 || c >= n_cols) { ws[HUB_WS_BAD + j] = 1; continue; }
+        const uint32_t old = atomicOr(&mask[(int64_t)c * HUB_WORDS + (j >> 5)], bit);
+        if (old & bit) ws[HUB_WS_BAD + j] = 1;                 // the column a second time: this row cannot be a hub
+    }
+}
+
+__global__ void hub_finalize_kernel(const int32_t* __restrict__ rowptr, int64_t min_entries, int32_t* __restrict__ ws,
+                                    int32_t* __restrict__ info, int32_t* __restrict__ hub_rows) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int h0 = info[3];
+    int h = 0;
+    int64_t total = 0;
+    for (int j = 0; j < NPI_HUB_MAX; ++j) {
+        int m = -1;
+        if (j < h0 && ws[HUB_WS_BAD + j] == 0) {
+            const int32_t r = ws[HUB_WS_PRELIM + j];
+            hub_rows[h] = r;
+            total += rowptr[r + 1] - rowptr[r];
+            m = h++;
+        }
+        ws[HUB_WS_REMAP + j] = m;
+    }
+    if (total < min_entries || total >= ((int64_t)1 << 31)) h = 0;
+    for (int j = h; j < NPI_HUB_MAX; ++j) hub_rows[j] = -1;
+    ws[HUB_WS_IDENT] = (h == h0) ? 1 : 0;
+    info[0] = h;
+    info[1] = h > 0 ? (int32_t)total : 0;
+}
+
+// the bits of the dropped hubs leave the masks, the others move down (only when a hub was dropped)
+__global__ void hub_mask_remap_kernel(int64_t n_cols, const int32_t* __restrict__ ws, const int32_t* __restrict__ info,
+                                      uint32_t* __restrict__ mask) {
+    if (ws[HUB_WS_IDENT] != 0 || info[0] == 0) return;
+    int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_cols) return;
+    uint32_t out[HUB_WORDS] = {};
+    bool any = false;
+    for (int q = 0; q < HUB_WORDS; ++q) {
+        uint32_t m = mask[c * HUB_WORDS + q];
+        any |= m != 0u;
+        while (m != 0u) {
+            const int b = __builtin_ctz(m);
+            m &= m - 1u;
+            const int nj = ws[HUB_WS_REMAP + q * 32 + b];
+            if (nj >= 0) out[nj >> 5] |= 1u << (nj & 31);
+        }
+    }
+    if (!any) return;
+    for (int q = 0; q < HUB_WORDS; ++q) mask[c * HUB_WORDS + q] = out[q];
+}
+
+__global__ void __launch_bounds__(256)
+hub_light_rowptr_kernel(const int32_t* __restrict__ rowptr, int64_t N, const int32_t* __restrict__ hub_rows, int H,
+                        int32_t* __restrict__ rowptr_l) {
+    __shared__ int32_t hr[NPI_HUB_MAX], hd[NPI_HUB_MAX];
+    if (threadIdx.x < H) {
+        const int32_t r = hub_rows[threadIdx.x];
+        hr[threadIdx.x] = r;
+        hd[threadIdx.x] = rowptr[r + 1] - rowptr[r];
+    }
+    __syncthreads();
+    int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r > N) return;
+    int32_t removed = 0;
+    for (int j = 0; j < H; ++j) removed += (hr[j] < r) ? hd[j] : 0;
+    rowptr_l[r] = rowptr[r] - removed;
+}
+
+__global__ void hub_light_entries_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                         const int32_t* __restrict__ eid, const int32_t* __restrict__ rowidx, int64_t N, int64_t nnz_max,
+                                         const int32_t* __restrict__ rowptr_l, int64_t nnz_max_l, int32_t* __restrict__ col_l,
+                                         int32_t* __restrict__ eid_l, int32_t* __restrict__ rowidx_l) {
+    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nnz_max || p >= rowptr[N]) return;
+    const int32_t r = rowidx[p];
+    if (r < 0 || r >= N || rowptr_l[r + 1] == rowptr_l[r]) return;      // an entry of a hub row
+    const int64_t q = p - (rowptr[r] - rowptr_l[r]);
+    if (q < 0 || q >= nnz_max_l) return;
+    col_l[q] = col[p];
+    eid_l[q] = eid[p];
+    rowidx_l[q] = r;
+}
+
+}  // namespace npi
+
+extern "C" int64_t npi_hub_plan_workspace_elems(void) { return HUB_WS_ELEMS; }
+
+extern "C" int npi_hub_plan(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t n_cols, int64_t nnz_max, int64_t h_max,
+                            int64_t min_degree, int64_t min_entries, int32_t* hub_rows, uint32_t* mask, int32_t* info,
+                            int32_t* workspace, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    NPI_REQUIRE(N > 0 && n_cols > 0 && nnz_max > 0 && N < ((int64_t)1 << 31) && n_cols < ((int64_t)1 << 31), "npi_hub_plan: bad size");
+    NPI_REQUIRE(h_max >= 1 && h_max <= NPI_HUB_MAX, "npi_hub_plan: h_max must be in [1, NPI_HUB_MAX]");
+    NPI_REQUIRE(min_degree >= 1 && min_degree < ((int64_t)1 << 31) && min_entries >= 0, "npi_hub_plan: bad threshold");
+    NPI_REQUIRE(rowptr && col && hub_rows && mask && info && workspace, "npi_hub_plan: null pointer");
+    (void)hipMemsetAsync(workspace, 0, HUB_WS_CAND * sizeof(int32_t), stream);
+    (void)hipMemsetAsync(info, 0, 4 * sizeof(int32_t), stream);
+    (void)hipMemsetAsync(mask, 0, (size_t)n_cols * HUB_WORDS * sizeof(uint32_t), stream);
+    hub_candidates_kernel<<<(unsigned)ceil_div(N, 256), 256, 0, stream>>>(rowptr, N, (int32_t)min_degree, workspace);
+    hub_select_kernel<<<1, 1024, 0, stream>>>(rowptr, (int)h_max, workspace, info);
+    hub_mask_kernel<<<dim3(64, NPI_HUB_MAX), 256, 0, stream>>>(rowptr, col, n_cols, workspace, info, mask);
+    hub_finalize_kernel<<<1, 64, 0, stream>>>(rowptr, min_entries, workspace, info, hub_rows);
+    hub_mask_remap_kernel<<<(unsigned)ceil_div(n_cols, 256), 256, 0, stream>>>(n_cols, workspace, info, mask);
+    return check_launch("npi_hub_plan");
+}
+
+extern "C" int npi_hub_light_side(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const int32_t* rowidx, int64_t N,
+                                  int64_t nnz_max, const int32_t* hub_rows, int64_t H, int64_t nnz_max_light, int64_t item_edges,
+                                  int32_t* rowptr_l, int32_t* col_l, int32_t* eid_l, int32_t* rowidx_l, int32_t* item_row_l,
+                                  void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    NPI_REQUIRE(N > 0 && nnz_max > 0 && nnz_max_light >= 0 && nnz_max_light <= nnz_max, "npi_hub_light_side: bad size");
+    NPI_REQUIRE(H >= 1 && H <= NPI_HUB_MAX, "npi_hub_light_side: H must be in [1, NPI_HUB_MAX]");
+    NPI_REQUIRE(item_edges_ok(item_edges), "npi_hub_light_side: item_edges must be 64 or NPI_ITEM_EDGES");
+    NPI_REQUIRE(rowptr && col && eid && rowidx && hub_rows && rowptr_l && col_l && eid_l && rowidx_l && item_row_l,
+                "npi_hub_light_side: null pointer");
+    hub_light_rowptr_kernel<<<(unsigned)ceil_div(N + 1, 256), 256, 0, stream>>>(rowptr, N, hub_rows, (int)H, rowptr_l);
+    hub_light_entries_kernel<<<(unsigned)ceil_div(nnz_max, 256), 256, 0, stream>>>(rowptr, col, eid, rowidx, N, nnz_max, rowptr_l,
+                                                                                 nnz_max_light, col_l, eid_l, rowidx_l);
+    write_item_rows(rowptr_l, N, nnz_max_light, item_edges, item_row_l, stream);
+    return check_launch("npi_hub_light_side");
 }

@@ -11,7 +11,7 @@
 // (rna, protein) first, like the reference.  Pairs must be unique and the graph bipartite (checked by the
 // host wrapper): then no partner can have been numbered before and one ballot-ranked pass suffices.
 // All work is integer / byte movement, one wavefront per sample (hub proteins have 10^3..10^5 partners).
-#include "npi_common.h"
+#include "sort.h"
 
 namespace npi {
 
@@ -55,24 +55,17 @@ subgraph_scan_kernel(const int32_t* __restrict__ cnt, int B, int32_t* __restrict
     const int b = min(B, t * per), e = min(B, b + per);
     long long s = 0;
     for (int g = b; g < e; ++g) s += (long long)cnt[g] + cnt[B + g];
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {                   // Hillis-Steele inclusive scan of the thread sums
-        const long long v = (t >= d) ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    long long run = (t > 0) ? part[t - 1] : 0;
+    long long all;
+    long long run = block_exclusive_scan<1024>(s, part, &all);
     for (int g = b; g < e; ++g) {
         node_off[g] = (int)(run + 2 * g);
         pair_off[g] = (int)(run + g);
         run += (long long)cnt[g] + cnt[B + g];
     }
     if (t == 1023) {
-        const long long tot = part[1023] + 2ll * B;        // nodes >= pairs: one check covers both
+        const long long tot = all + 2ll * B;               // nodes >= pairs: one check covers both
         node_off[B] = tot > 0x7fffffffll ? -1 : (int)tot;  // -1: the batch does not fit 32-bit row ids
-        pair_off[B] = tot > 0x7fffffffll ? -1 : (int)(part[1023] + B);
+        pair_off[B] = tot > 0x7fffffffll ? -1 : (int)(all + B);
     }
 }
 
