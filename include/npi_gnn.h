@@ -854,6 +854,58 @@ int npi_negative_distinct(const int32_t* cand_src, const int32_t* cand_dst, int6
                           int64_t* out_src, int64_t* out_dst, int32_t* info, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Random walks and the skip-gram pair list: the node2vec columns of the feature vector, made where the graph already is.  Replaces
+ * the reference's offline step `node2vec-master/src/main.py` (alias-sampled walks, 10 x 80 per node, then gensim) and PyG 1.4.2
+ * `torch_geometric.nn.models.Node2Vec` over `torch_cluster.random_walk`.
+ *
+ * Input of npi_random_walk: the BY-SOURCE CSR WITH SORTED COLUMNS of the edge list as it is (npi_csr_build_ex with key =
+ * edge_index[0], val = edge_index[1], add_self_loops = 0, build_flags = NPI_CSR_SORT_COLUMNS, NPI_CSR_DROP_EQUAL not set):
+ * rowptr[N+1], col[nnz] = target ids, ASCENDING within a row -- the rows MUST be sorted: "is (u, x) an edge" is a binary search of
+ * row u for x.  Parallel edges stay: they weigh in the uniform pick as in torch_cluster, and count once for membership.
+ *
+ * RULE W -- second-order walks by rejection.  mix64, G, C, mulhi and key as in the two rules above; all arithmetic wrapping uint64:
+ *     root    = mix64(mix64(key) + 3 * G)
+ *     base_w  = mix64(root ^ (w * C))                     walk (slot) w = 0 .. W-1: one stream per SLOT, so repeated starts differ
+ *     word(i) = mix64(base_w + G * i)                     i = 1, 2, ...
+ * Walk w starts at v_0 = start[w].  Step t = 1 .. L, from v = v_{t-1} with d = rowptr[v+1] - rowptr[v]:
+ *   d == 0 : v_t = v (torch_cluster's rule: a walk stays at a dead end); no word is consumed.
+ *   else   : attempts, numbered n = 0, 1, 2, ... over the WHOLE walk; attempt n draws pick = word(2n + 1), accept = word(2n + 2).
+ *            The candidate x = col[rowptr[v] + mulhi(pick, d)] is accepted iff (accept >> 32) < thr, where
+ *                thr = 2^32     when there is no previous node (t == 1),
+ *                      thr_ret  when x == v_{t-2},
+ *                      thr_nbr  when (v_{t-2}, x) is an edge (binary search of row v_{t-2}),
+ *                      thr_far  otherwise.
+ *            v_t = the first accepted candidate of at most `tries` attempts; none accepted: the LAST candidate is taken and
+ *            NPI_STATUS_WALK_TRIES is raised.
+ * The three thresholds are integers in [0, 2^32] (int64_t arguments, like every scalar of this header); there is no float in the kernel, so the rule is bitwise restatable.  (The Python
+ * side computes them in double as min(2^32, floor(2^32 * a / mx)) for a in (1/p, 1, 1/q), mx = the largest of the three.)  With all
+ * three 2^32 (p == q == 1) every first attempt is accepted and step t uses word(2t - 1); the kernel then skips the accept word and
+ * the search, with the identical result.  A start[w] outside [0, N) is never dereferenced: the whole row is -1 and
+ * NPI_STATUS_BAD_SOURCE_ID is raised.  Output: walks[W, L+1] int64, row-major (torch_cluster's layout).  A pure function of (key,
+ * graph, start, L, thresholds, tries) -- independent of launch geometry and timing.
+ *
+ * npi_walk_pairs writes the pair list of PyG's `Node2Vec.loss` in the cat([pos, neg], 1) layout npi_pair_score takes.  With
+ * J = L + 2 - c windows per walk and R = J * W window rows, row r = j * W + w (PyG's torch.cat(walks, dim=0) order) starts at
+ * walks[w, j]:
+ *     positives : m = r * (c-1) + (k-1),        k = 1 .. c-1 :  (walks[w, j], walks[w, j+k])
+ *     negatives : m = R * (c-1) + r * S + s,    s = 0 .. S-1 :  (walks[w, j], mulhi(mix64(nbase + G * (r * S + s + 1)), N))
+ *     nbase = mix64(mix64(key) + 4 * G)
+ * A negative is a uniform node, as PyG's torch.randint: it may be the start or a true neighbour, as there.  -1 entries of a bad walk
+ * are copied as they are (npi_pair_score scores such a pair 0 and reports it).  n_pos of npi_pair_score is R * (c-1);
+ * M = R * (c - 1 + S) must stay below 2^31 - 1.
+ *
+ * Neither allocates or reads anything back: both may run inside a stream capture.  Refused with NPI_ERR_ARG before any launch: a
+ * null pointer, a negative size, W, N or M >= 2^31 - 1, N < 1, tries < 1, a threshold outside [0, 2^32], c < 2 or c > L + 1.  W == 0
+ * returns 0 without a launch.  status (int32 device word, may be NULL) is OR-ed into, never cleared here.
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_STATUS_WALK_TRIES 512
+int npi_random_walk(const int32_t* rowptr, const int32_t* col, int64_t N, const int64_t* start, int64_t W, int64_t L, int64_t key,
+                    int64_t thr_ret, int64_t thr_nbr, int64_t thr_far, int64_t tries, int64_t* walks, int32_t* status,
+                    void* stream);
+int npi_walk_pairs(const int64_t* walks, int64_t W, int64_t L, int64_t c, int64_t S, int64_t N, int64_t key, int64_t* src,
+                   int64_t* dst, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Pair scores and the link-prediction loss: the third stage of a link-prediction step, after the samplers (the pairs) and the
  * layers (the embeddings).  Replaces PyG 1.4.2 `torch_geometric/nn/models/autoencoder.py`:
  *     InnerProductDecoder.forward : value = (z[edge_index[0]] * z[edge_index[1]]).sum(dim=1); torch.sigmoid(value) if sigmoid

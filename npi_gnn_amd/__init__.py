@@ -16,7 +16,8 @@ from .graphed import GraphedStack  # noqa: F401
 from .sampler import Block, DataFlow, NeighborSampler, SubgraphBatch  # noqa: F401
 from .negative import NegativeSampler, negative_sampling, structured_negative_sampling  # noqa: F401
 from .autoencoder import GAE, InnerProductDecoder  # noqa: F401
+from .walk import Node2Vec, RandomWalker, random_walk  # noqa: F401
 
 __all__ = ["CSRGraph", "GraphBatch", "as_graph", "set_debug", "GCNNorm", "gat_conv", "gcn_conv", "sage_conv", "segsum",
            "GATConv", "GCNConv", "SAGEConv", "Schedule", "GraphedStack", "NeighborSampler", "DataFlow", "Block", "SubgraphBatch", "NegativeSampler", "negative_sampling",
-           "structured_negative_sampling", "InnerProductDecoder", "GAE", "pair_scores", "link_loss", "NpiError", "load", "LIB_PATH"]
+           "structured_negative_sampling", "InnerProductDecoder", "GAE", "RandomWalker", "random_walk", "Node2Vec", "pair_scores", "link_loss", "NpiError", "load", "LIB_PATH"]

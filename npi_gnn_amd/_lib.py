@@ -1,7 +1,9 @@
 """ctypes binding of ``libnpi_gnn.so`` (the C ABI of ``include/npi_gnn.h``).
 
 There is NO CPU fallback: every wrapper raises if the library is missing or if a tensor is not
-on an AMD GPU.  PyTorch only lends device memory and the current HIP stream.
+on an AMD GPU.  PyTorch only lends device memory and the current HIP stream.  The link-prediction entry points in the
+order of a step: ``npi_sample_*`` (batches), ``npi_negative_*`` (negatives), ``npi_random_walk`` / ``npi_walk_pairs`` (node2vec
+walks and their skip-gram pair list), ``npi_pair_score`` (scores and loss).
 """
 from __future__ import annotations
 
@@ -28,6 +30,7 @@ NPI_STATUS_BAD_SAMPLE_SIZES = 32  # status bit of npi_sample_select / _relabel /
 NPI_STATUS_NO_NEGATIVE = 64       # status bit of npi_negative_targets: a slot whose tries all hit edges (it holds -1)
 NPI_STATUS_BAD_SOURCE_ID = 128    # status bit of npi_negative_targets: a source id outside [0, n_src) (its slot holds -1)
 NPI_STATUS_BAD_PAIR_ID = 256      # status bit of npi_pair_score: a pair with an id outside its table (logit, coefficient and loss term 0)
+NPI_STATUS_WALK_TRIES = 512       # status bit of npi_random_walk: a step whose tries were all rejected (it took the last candidate)
 NPI_PAIR_LOGITS = 0               # modes of npi_pair_score
 NPI_PAIR_LOSS_GAE = 1
 NPI_PAIR_LOSS_BCE = 2
@@ -159,6 +162,8 @@ PROTOTYPES = {
     "npi_negative_targets": (c_int, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "npi_negative_distinct_workspace_bytes": (_I, [_I]),
     "npi_negative_distinct": (c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "npi_random_walk": (c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "npi_walk_pairs": (c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "npi_pair_score_workspace_bytes": (_I, [_I]),
     "npi_pair_score": (c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, c_int, _P, _P, _P, _P, _I, _P, _P]),
 }

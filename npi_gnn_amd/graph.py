@@ -59,10 +59,14 @@ def raise_on_status(values) -> None:
         raise ValueError("npi_sample_select / npi_sample_relabel: the offsets or counts they were given belong to another call; "
                          "the entries concerned were not written")
     if any(int(v) & _lib.NPI_STATUS_BAD_SOURCE_ID for v in values):
-        raise IndexError("NegativeSampler.corrupt: a source id outside [0, n_src): its slot holds -1 (npi_negative_targets)")
+        raise IndexError("NegativeSampler.corrupt / RandomWalker.walks: a source id outside [0, n_src): its slot (its whole walk) "
+                         "holds -1 (npi_negative_targets / npi_random_walk)")
     if any(int(v) & _lib.NPI_STATUS_NO_NEGATIVE for v in values):
         raise ValueError("NegativeSampler.corrupt: a source found no non-edge target within its tries (it is joined to every "
                          "target, or tries ran out): its slot holds -1 (npi_negative_targets)")
+    if any(int(v) & _lib.NPI_STATUS_WALK_TRIES for v in values):
+        raise ValueError("RandomWalker.walks: a step had every one of its tries rejected and took the last candidate "
+                         "(npi_random_walk): raise tries, or choose p and q less far apart")
     if any(int(v) & _lib.NPI_STATUS_BAD_PAIR_ID for v in values):
         raise IndexError("pair_scores / link_loss: a pair holds an id outside its embedding table: its logit, coefficient and loss "
                          "term are 0 (npi_pair_score; torch's indexing raises here)")
