@@ -960,6 +960,58 @@ int npi_pair_score(const int64_t* src, const int64_t* dst, int64_t M, int64_t n_
                    int64_t n_src, const float* z_dst, int64_t ld_dst, int64_t n_dst, int64_t F, int mode, float* logits, float* coef,
                    float* loss, void* partials, int64_t partials_bytes, int32_t* status, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Ranking metrics: the evaluation half of link prediction.  Replaces what PyG 1.4.2 `GAE.test` and the reference's ROC / PR
+ * figures (src/compare_withKmer_noKmer.py:20-54) do on the host through sklearn: `roc_auc_score`, `average_precision_score`,
+ * `roc_curve` and `precision_recall_curve` of M scores -- all four are functions of `_binary_clf_curve`, which this entry point
+ * computes: one sort (the shared sorter, all 32 key bits), two passes over the sorted stream, one over the curve.
+ *
+ * RULE R -- the curve and the two areas of M float32 scores with binary labels.
+ *   Input.  scores[M] f32 and a label per score, in one of two forms: y[M] int64 with values 0 / 1; or y = NULL and a count n_pos:
+ *           score m is a positive exactly when m < n_pos -- the `cat([pos, neg])` layout npi_pair_score takes.
+ *   1. Key.   s = score + 0.0f (so -0.0 ranks and reports as +0.0, as in sklearn's numeric comparison); with b = the bits of s,
+ *             u = (b & 0x80000000) ? ~b : (b | 0x80000000) is ascending-orderable (npi_topk_select_sorted's transform) and the key
+ *             is ~u: an ASCENDING key is a DESCENDING score.  The payload is the label.  +-inf are ordinary scores.  A NaN score
+ *             raises NPI_STATUS_BAD_SCORE; a label other than 0 / 1 raises NPI_STATUS_BAD_LABEL and counts as 0.  Neither reads or
+ *             writes out of bounds; what the metrics are worth then is undefined.
+ *   2. Sort.  The pairs by all 32 key bits.
+ *   3. Curve. Position i of the sorted stream ends a tie group iff i == M-1 or key[i] != key[i+1].  TP_i = the positives among
+ *             positions 0..i, FP_i = i + 1 - TP_i.  The curve is the G triples (thr_g, TP_g, FP_g) at the group ends, in stream
+ *             order, thr_g the score rebuilt from the key: sklearn's `_binary_clf_curve` (thresholds, tps, fps) -- all integers,
+ *             thresholds bitwise.
+ *   4. Metrics.  With TP_-1 = FP_-1 = 0, P = TP_{G-1}, N = FP_{G-1}:
+ *             U2  = sum_g (FP_g - FP_{g-1}) * (TP_g + TP_{g-1})          int64, exact: U2 <= 2 P N < 2^62 for M < 2^31 - 1; it
+ *                   equals 2 #{(p, n): s_p > s_n} + #{(p, n): s_p = s_n} over positives p and negatives n
+ *             auc = U2 / (2.0 * P * N)                                    double;  P * N == 0: NaN
+ *             ap  = sum_g ((TP_g - TP_{g-1}) / P) * (TP_g / (TP_g + FP_g))  every term in double;  P == 0: NaN
+ *             The ap sum has a fixed order: a lane adds its (at most four) terms in order, a wavefront its lanes in a fixed tree,
+ *             a workgroup of 1,024 curve entries its four wavefronts in order, one final workgroup the partials in a fixed order
+ *             (npi_pair_score's scheme).  No float atomics anywhere.
+ * The result is a pure function of the MULTISET of (score, label) pairs: the curve exists at group ends only, so the order of
+ * labels inside a tie group cannot matter, and a permuted input gives bitwise the same auc, ap and curve.  It does not depend on
+ * launch geometry either.
+ *
+ *   result [2]  : auc, ap (fp64)                         counts [4] : P, N, G, U2 (int64)                    -- both required
+ *   thr / tps / fps : the curve, each of capacity M (G entries are written, G <= M; the rest is not touched) -- or all three NULL:
+ *                 no curve is written
+ *   status      : int32 device word as npi_csr_build_ex's (may be NULL): OR-ed into, never cleared here
+ *   workspace   : npi_rank_workspace_bytes(M) bytes, 16-byte aligned, caller-owned (the sorter's buffers, then one int64 and two
+ *                 8-byte partials per 1,024 scores)
+ * Nothing is allocated, nothing read back: the call may run inside a stream capture.  Refused with NPI_ERR_ARG before any launch:
+ * M outside [0, 2^31 - 1); n_pos outside [0, M] when y is NULL (it is ignored otherwise); a null result or counts; a curve given
+ * in part; with M > 0 a null scores or workspace, or a workspace misaligned or shorter than npi_rank_workspace_bytes(M).  M == 0
+ * launches no kernel: two hipMemsetAsync on `stream` write NaN, NaN (every bit set) and four zero counts.
+ * npi_rank_workspace_bytes returns -1 for an M outside [0, 2^31 - 1).
+ *
+ * Out of scope: sample weights, multiclass / `average=`, `drop_intermediate=True`, `max_fpr`, bf16 / fp64 scores.
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_STATUS_BAD_SCORE 1024
+#define NPI_STATUS_BAD_LABEL 2048
+int64_t npi_rank_workspace_bytes(int64_t M);
+int npi_rank_metrics(const float* scores, const int64_t* y_or_null, int64_t M, int64_t n_pos, double* result /*[2]: auc, ap*/,
+                     int64_t* counts /*[4]: P, N, G, U2*/, float* thr, int32_t* tps, int32_t* fps /*each capacity M, or all three NULL*/,
+                     int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Evaluation loop (reference src/methods.py:87-105 compares one element per Python
  * iteration, one device sync each).  counts[4] += [TP, FN, TN, FP] for pred = first arg-max of scores[i, 0..C):
  * pred 1 & y 1 -> TP, pred 1 & y 0 -> FP, pred 0 & y 1 -> FN, anything else -> TN (the reference's else

@@ -17,7 +17,9 @@ from .sampler import Block, DataFlow, NeighborSampler, SubgraphBatch  # noqa: F4
 from .negative import NegativeSampler, negative_sampling, structured_negative_sampling  # noqa: F401
 from .autoencoder import GAE, InnerProductDecoder  # noqa: F401
 from .walk import Node2Vec, RandomWalker, random_walk  # noqa: F401
+from .rank import average_precision_score, precision_recall_curve, rank_metrics, roc_auc_score, roc_curve  # noqa: F401
 
 __all__ = ["CSRGraph", "GraphBatch", "as_graph", "set_debug", "GCNNorm", "gat_conv", "gcn_conv", "sage_conv", "segsum",
            "GATConv", "GCNConv", "SAGEConv", "Schedule", "GraphedStack", "NeighborSampler", "DataFlow", "Block", "SubgraphBatch", "NegativeSampler", "negative_sampling",
-           "structured_negative_sampling", "InnerProductDecoder", "GAE", "RandomWalker", "random_walk", "Node2Vec", "pair_scores", "link_loss", "NpiError", "load", "LIB_PATH"]
+           "structured_negative_sampling", "InnerProductDecoder", "GAE", "RandomWalker", "random_walk", "Node2Vec", "pair_scores", "link_loss", "rank_metrics",
+           "roc_auc_score", "average_precision_score", "roc_curve", "precision_recall_curve", "NpiError", "load", "LIB_PATH"]

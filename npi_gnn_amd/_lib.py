@@ -3,7 +3,8 @@
 There is NO CPU fallback: every wrapper raises if the library is missing or if a tensor is not
 on an AMD GPU.  PyTorch only lends device memory and the current HIP stream.  The link-prediction entry points in the
 order of a step: ``npi_sample_*`` (batches), ``npi_negative_*`` (negatives), ``npi_random_walk`` / ``npi_walk_pairs`` (node2vec
-walks and their skip-gram pair list), ``npi_pair_score`` (scores and loss).
+walks and their skip-gram pair list), ``npi_pair_score`` (scores and loss), ``npi_rank_metrics`` (ROC-AUC, average precision and
+the score curve of an evaluation).
 """
 from __future__ import annotations
 
@@ -31,6 +32,8 @@ NPI_STATUS_NO_NEGATIVE = 64       # status bit of npi_negative_targets: a slot w
 NPI_STATUS_BAD_SOURCE_ID = 128    # status bit of npi_negative_targets: a source id outside [0, n_src) (its slot holds -1)
 NPI_STATUS_BAD_PAIR_ID = 256      # status bit of npi_pair_score: a pair with an id outside its table (logit, coefficient and loss term 0)
 NPI_STATUS_WALK_TRIES = 512       # status bit of npi_random_walk: a step whose tries were all rejected (it took the last candidate)
+NPI_STATUS_BAD_SCORE = 1024      # status bit of npi_rank_metrics: a NaN score (the metrics are undefined)
+NPI_STATUS_BAD_LABEL = 2048      # status bit of npi_rank_metrics: a label other than 0 / 1 (it counted as 0)
 NPI_PAIR_LOGITS = 0               # modes of npi_pair_score
 NPI_PAIR_LOSS_GAE = 1
 NPI_PAIR_LOSS_BCE = 2
@@ -166,6 +169,8 @@ PROTOTYPES = {
     "npi_walk_pairs": (c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "npi_pair_score_workspace_bytes": (_I, [_I]),
     "npi_pair_score": (c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, c_int, _P, _P, _P, _P, _I, _P, _P]),
+    "npi_rank_workspace_bytes": (_I, [_I]),
+    "npi_rank_metrics": (c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
 }
 
 _lib = None

@@ -4,10 +4,12 @@
     z = model.encode(x, edge_index)                            # a tensor [N, F], or a pair (z_src, z_dst) from bipartite layers
     loss = model.recon_loss(z, pos_edge_index)                 # negatives drawn on the device, as many as positives
     loss.backward()
+    auc, ap = model.test(z, pos_edge_index, neg_edge_index)    # 0-d float64 device tensors: float(auc) is PyG's number
 
 ``InnerProductDecoder.forward`` is ``functional.pair_scores`` (one launch over the pair list, no sort), ``GAE.recon_loss`` is
 ``functional.link_loss`` (one forward launch, no logits written; the backward is the layers' own aggregation: no float atomics,
-bitwise reproducible).  ``InnerProductDecoder.forward_all`` -- the dense ``[N, N]`` product -- and ``GAE.test`` are not provided.
+bitwise reproducible), ``GAE.test`` is ``rank.rank_metrics`` (ROC-AUC and average precision of the decoder's outputs: one device
+sort, no copy to the host).  ``InnerProductDecoder.forward_all`` -- the dense ``[N, N]`` product -- is not provided.
 CPU tensors raise ``NpiError``: there is no CPU path.
 """
 from __future__ import annotations
@@ -19,6 +21,7 @@ from torch import nn
 
 from . import functional as F_
 from .negative import NegativeSampler
+from .rank import rank_metrics
 
 
 def _reset(module) -> None:
@@ -81,3 +84,13 @@ class GAE(nn.Module):
             neg_edge_index = sampler.pairs(draw=self.draw)
             self.draw += 1
         return F_.link_loss(z, pos_edge_index, neg_edge_index, loss=loss)
+
+    def test(self, z, pos_edge_index: torch.Tensor, neg_edge_index: torch.Tensor):
+        """PyG's ``test(z, pos_edge_index, neg_edge_index)``: ``(auc, ap)`` = ``roc_auc_score`` and ``average_precision_score`` of
+        ``decode(z, ., sigmoid=True)`` over ``cat([pos, neg])`` with the positives labelled 1 -- ``rank.rank_metrics`` in its
+        ``n_pos`` form, so both are 0-d float64 DEVICE tensors and nothing is read back (``float(auc)`` is the number PyG returns).
+        The float32 sigmoid outputs are what is ranked, as in PyG: where the sigmoid saturates, its ties are PyG's ties."""
+        with torch.no_grad():
+            pos_pred = self.decode(z, pos_edge_index, sigmoid=True)
+            neg_pred = self.decode(z, neg_edge_index, sigmoid=True)
+            return rank_metrics(torch.cat([pos_pred, neg_pred]), n_pos=int(pos_pred.numel()))

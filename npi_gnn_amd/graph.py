@@ -70,6 +70,12 @@ def raise_on_status(values) -> None:
     if any(int(v) & _lib.NPI_STATUS_BAD_PAIR_ID for v in values):
         raise IndexError("pair_scores / link_loss: a pair holds an id outside its embedding table: its logit, coefficient and loss "
                          "term are 0 (npi_pair_score; torch's indexing raises here)")
+    if any(int(v) & _lib.NPI_STATUS_BAD_SCORE for v in values):
+        raise ValueError("Input contains NaN: rank_metrics / roc_auc_score and their kin were given a NaN score; the metrics and "
+                         "the curve of that call are undefined (npi_rank_metrics; sklearn raises here)")
+    if any(int(v) & _lib.NPI_STATUS_BAD_LABEL for v in values):
+        raise ValueError("rank_metrics / roc_auc_score and their kin: a label other than 0 / 1; it counted as 0 "
+                         "(npi_rank_metrics; sklearn's binary metrics raise here)")
     if any(int(v) & 4 for v in values):
         raise ValueError("InteractionGraph.batch: the n_nodes / n_pairs it was given do not belong to its keys (the device counted "
                          "other totals); that batch holds placeholders only (node 0 / graph 0 rows, padding edges, zero features).  "
