@@ -1012,7 +1012,67 @@ int npi_rank_metrics(const float* scores, const int64_t* y_or_null, int64_t M, i
                      int64_t* counts /*[4]: P, N, G, U2*/, float* thr, int32_t* tps, int32_t* fps /*each capacity M, or all three NULL*/,
                      int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
-/* Evaluation loop (reference src/methods.py:87-105 compares one element per Python
+/* ---------------------------------------------------------------------------------------------
+ * Edge splits: one edge list -> a training graph plus held-out positive and negative edges, the first step of a link-prediction
+ * run.  Replaces PyG 1.4.2 `torch_geometric.utils.train_test_split_edges` (`row < col`, a host `torch.randperm`, a dense [N, N]
+ * mask for the held-out negatives, `to_undirected` through `torch_sparse.coalesce`) and the reference's 5-fold key split
+ * (`src/generate_edgelist.py:460-494`; the in-script k-fold of `src/train.py:108-184`).
+ *
+ * RULE S -- a random order of the kept columns; its contiguous ranges are the parts.  All arithmetic in wrapping uint64; mix64, G,
+ * mulhi and key as in Rules P / T / W above.
+ *   1. Keep.   Column e of the [2, E] list (src[e], dst[e]; int64) is KEPT when src[e] lies in [0, n_src) and dst[e] in [0, n_dst)
+ *              and -- with NPI_SPLIT_UPPER (flag bit 0; one id space) -- src[e] < dst[e] (PyG's `row < col`).  An id out of range is
+ *              never dereferenced: the column is dropped and NPI_STATUS_BAD_PAIR_ID is OR-ed into the status word.  K = the number
+ *              of kept columns.  Parallel columns are kept as they are (as PyG keeps them).
+ *   2. Order.  base = mix64(mix64(mix64(key) + 5 * G))           (5 G: the next free stream after the walks' 3 G / 4 G)
+ *              r_e  = mix64(base + G * (e + 1))                  e = the column's index in the INPUT, not after the compaction
+ *              The kept columns come out in ascending (r_e, e): out_src[K], out_dst[K], e_id[K] (int64; e_id = the input column,
+ *              as the sampler's e_id), info[0] = K.  mix64 is a bijection, so for E < 2^31 no two r_e are equal; for a random key
+ *              the order is a uniform random permutation.  A pure function of (key, edge list, flags), independent of launch
+ *              geometry, of timing and of how the compaction is done.
+ *   3. Parts.  Contiguous ranges of that order: slices, no kernel.  For train / val / test with n_v = floor(val_ratio * K) and
+ *              n_t = floor(test_ratio * K): val = [0, n_v), test = [n_v, n_v + n_t), train = the rest (PyG's order).  For k folds,
+ *              fold f tests on [floor(f K / k), floor((f + 1) K / k)) and trains on the complement.
+ *   4. Held-out negatives, one id space.  Let U be the undirected form (5.) of the WHOLE edge list.  Take Rule P's candidates over U
+ *              with no_loops, rewrite every valid candidate (s, d) as (min(s, d), max(s, d)) -- an invalid (-1, -1) stays -- and
+ *              keep the first M distinct ones in candidate order (npi_negative_distinct).  U is symmetric, so (s, d) is valid exactly
+ *              when (d, s) is, and every unordered non-edge {a, b} has the same probability: a uniform draw without replacement from
+ *              the upper-triangle non-edges (PyG's `neg_adj_mask.triu(1)`), which are never materialised.  M is clamped to
+ *              N (N - 1) / 2 - #{distinct (a, b) in U with a < b}.  As in Rule P the result does not depend on the window.
+ *              Two id spaces: Rule P as it is, over the whole list.
+ *   5. Undirected form.  Both orientations of the given columns, coalesced: sorted by (row, col), equal pairs once (PyG's
+ *              `to_undirected`).  (v, v) columns stay, once.
+ *
+ *   npi_split_permute    : Rule S 1-2.  Keep flags, their exclusive scan, a stable partition that puts (low 32 bits of r_e, e) for
+ *                          the kept columns in front of one padding pair per dropped column, two stable radix sorts of 32 bits (the
+ *                          high half of r_e is recomputed from the carried e between them), one gather.  out_src / out_dst / e_id:
+ *                          the caller sizes them with the bound E; K entries are written.  status (int32 device word, may be NULL)
+ *                          is OR-ed into, never cleared here.  workspace: npi_split_workspace_bytes(E) bytes, 16-byte aligned.
+ *   npi_split_canonical  : Rule S 4, in place over W candidates (npi_negative_candidates' output).
+ *   npi_split_undirected : Rule S 5 over one id space [0, N).  out_src / out_dst / e_id: capacity 2 E (int64); info[0] = the number
+ *                          of pairs written; e_id = the smallest input column that gives the pair in either orientation.  A column
+ *                          with an id out of range is dropped and raises NPI_STATUS_BAD_PAIR_ID.  Both orientations are written as
+ *                          int32 pairs and merged by npi_sample_coalesce.  workspace: npi_split_undirected_workspace_bytes(E) bytes,
+ *                          16-byte aligned.
+ * Nothing is allocated, nothing read back, no state is kept; there is no float anywhere.  Refused with -1 before any launch: a null
+ * pointer, a negative size, E (2 E for the undirected form), W or an id bound >= 2^31 - 1 (or an id bound below 1; N >= 2^31 - 2 for
+ * the undirected form), an unknown flag, a misaligned or short workspace.  E == 0 returns 0 without a launch and writes
+ * info[0] = 0 (a hipMemsetAsync on `stream`); W == 0 returns 0.  The two workspace queries return -1 for a size out of range.
+ *
+ * Out of scope: stratified or grouped splits, weighted edges carried through the split, splits inside a stream capture (the caller
+ * reads K), PyG's or the reference's random bits, `negative_sampling`'s `force_undirected`.
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_SPLIT_UPPER 1
+int64_t npi_split_workspace_bytes(int64_t E);
+int npi_split_permute(const int64_t* src, const int64_t* dst, int64_t E, int64_t n_src, int64_t n_dst, int64_t key, int flags,
+                      int64_t* out_src, int64_t* out_dst, int64_t* e_id, int32_t* info, int32_t* status, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+int npi_split_canonical(int32_t* cand_src, int32_t* cand_dst, int64_t W, void* stream);
+int64_t npi_split_undirected_workspace_bytes(int64_t E);
+int npi_split_undirected(const int64_t* src, const int64_t* dst, int64_t E, int64_t N, int64_t* out_src, int64_t* out_dst,
+                         int64_t* e_id, int32_t* info, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Evaluation loop(reference src/methods.py:87-105 compares one element per Python
  * iteration, one device sync each).  counts[4] += [TP, FN, TN, FP] for pred = first arg-max of scores[i, 0..C):
  * pred 1 & y 1 -> TP, pred 1 & y 0 -> FP, pred 0 & y 1 -> FN, anything else -> TN (the reference's else
  * branch).  counts is device memory, accumulated across calls; no synchronisation. */

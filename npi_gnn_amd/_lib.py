@@ -2,7 +2,7 @@
 
 There is NO CPU fallback: every wrapper raises if the library is missing or if a tensor is not
 on an AMD GPU.  PyTorch only lends device memory and the current HIP stream.  The link-prediction entry points in the
-order of a step: ``npi_sample_*`` (batches), ``npi_negative_*`` (negatives), ``npi_random_walk`` / ``npi_walk_pairs`` (node2vec
+order of a run: ``npi_split_*`` (train / val / test parts and folds of the edge list), ``npi_sample_*`` (batches), ``npi_negative_*`` (negatives), ``npi_random_walk`` / ``npi_walk_pairs`` (node2vec
 walks and their skip-gram pair list), ``npi_pair_score`` (scores and loss), ``npi_rank_metrics`` (ROC-AUC, average precision and
 the score curve of an evaluation).
 """
@@ -30,7 +30,9 @@ NPI_STATUS_BAD_TARGET_ID = 16     # status bit of npi_sample_counts / npi_sample
 NPI_STATUS_BAD_SAMPLE_SIZES = 32  # status bit of npi_sample_select / _relabel / _union: offsets / counts / capacity of another call
 NPI_STATUS_NO_NEGATIVE = 64       # status bit of npi_negative_targets: a slot whose tries all hit edges (it holds -1)
 NPI_STATUS_BAD_SOURCE_ID = 128    # status bit of npi_negative_targets: a source id outside [0, n_src) (its slot holds -1)
-NPI_STATUS_BAD_PAIR_ID = 256      # status bit of npi_pair_score: a pair with an id outside its table (logit, coefficient and loss term 0)
+NPI_STATUS_BAD_PAIR_ID = 256      # status bit of npi_pair_score: a pair with an id outside its table (logit, coefficient and loss term 0);
+                                  # of npi_split_permute / npi_split_undirected: a column with an id out of range (it was dropped)
+NPI_SPLIT_UPPER = 1               # flag of npi_split_permute: keep src < dst only (one id space; PyG's row < col)
 NPI_STATUS_WALK_TRIES = 512       # status bit of npi_random_walk: a step whose tries were all rejected (it took the last candidate)
 NPI_STATUS_BAD_SCORE = 1024      # status bit of npi_rank_metrics: a NaN score (the metrics are undefined)
 NPI_STATUS_BAD_LABEL = 2048      # status bit of npi_rank_metrics: a label other than 0 / 1 (it counted as 0)
@@ -171,6 +173,11 @@ PROTOTYPES = {
     "npi_pair_score": (c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, c_int, _P, _P, _P, _P, _I, _P, _P]),
     "npi_rank_workspace_bytes": (_I, [_I]),
     "npi_rank_metrics": (c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "npi_split_workspace_bytes": (_I, [_I]),
+    "npi_split_permute": (c_int, [_P, _P, _I, _I, _I, _I, c_int, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "npi_split_canonical": (c_int, [_P, _P, _I, _P]),
+    "npi_split_undirected_workspace_bytes": (_I, [_I]),
+    "npi_split_undirected": (c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
 }
 
 _lib = None

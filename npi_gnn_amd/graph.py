@@ -69,7 +69,8 @@ def raise_on_status(values) -> None:
                          "(npi_random_walk): raise tries, or choose p and q less far apart")
     if any(int(v) & _lib.NPI_STATUS_BAD_PAIR_ID for v in values):
         raise IndexError("pair_scores / link_loss: a pair holds an id outside its embedding table: its logit, coefficient and loss "
-                         "term are 0 (npi_pair_score; torch's indexing raises here)")
+                         "term are 0 (npi_pair_score; torch's indexing raises here) -- or EdgeSplitter / to_undirected: a column "
+                         "holds an id outside its range: it was dropped (npi_split_permute / npi_split_undirected)")
     if any(int(v) & _lib.NPI_STATUS_BAD_SCORE for v in values):
         raise ValueError("Input contains NaN: rank_metrics / roc_auc_score and their kin were given a NaN score; the metrics and "
                          "the curve of that call are undefined (npi_rank_metrics; sklearn raises here)")

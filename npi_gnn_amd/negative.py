@@ -83,21 +83,29 @@ class NegativeSampler:
         self.last_window = self.last_consumed = 0              # of the latest pairs(): the window that sufficed, info[1]
 
     # ---- Rule P ---------------------------------------------------------------------------------------------------------------------
-    def default_window(self, M: int) -> int:
+    def default_window(self, M: int, canonical: bool = False) -> int:
         """How many candidates the first round of ``pairs`` looks at for ``M`` pairs (a policy, not part of the rule): the expected
         number of valid draws until ``M`` distinct ones have been seen -- ``Z ln(Z / (Z - M))`` of ``Z`` non-edges, the coupon
-        collector's count -- over the non-edge density, plus 1 % and six standard deviations."""
-        Z = self.num_non_edges
-        density = Z / (self.n_src * self.n_dst)
+        collector's count -- over the non-edge density, plus 1 % and six standard deviations.  ``canonical``: the distinct ones are
+        the ``Z / 2`` unordered non-edges; a candidate is valid as often as before."""
+        density = self.num_non_edges / (self.n_src * self.n_dst)
+        Z = self.num_non_edges // 2 if canonical else self.num_non_edges
         valid = Z * math.log(Z / (Z - M + 0.5)) if M < Z else Z * (math.log(Z) + 1.0)
         need = max(valid, float(M)) / density
         return int(1.01 * need + 6.0 * math.sqrt(need)) + 64
 
-    def pairs(self, num_neg_samples: Optional[int] = None, draw: Optional[int] = None, window: Optional[int] = None) -> torch.Tensor:
+    def pairs(self, num_neg_samples: Optional[int] = None, draw: Optional[int] = None, window: Optional[int] = None,
+              canonical: bool = False) -> torch.Tensor:
         """Rule P: ``[2, M]`` distinct non-edge pairs, ``M = min(num_neg_samples, num_non_edges)`` (``None``: the number of columns
         of ``edge_index``).  ``window``: the candidates of the first round (default: ``default_window(M)``); the result does not
-        depend on it.  A round that holds fewer than ``M`` distinct non-edges is run again, from candidate 0, twice as long."""
+        depend on it.  A round that holds fewer than ``M`` distinct non-edges is run again, from candidate 0, twice as long.
+
+        ``canonical=True`` (Rule S 4; what ``EdgeSplitter`` asks of its sampler over the undirected form of a graph): every
+        candidate ``(s, d)`` counts as ``(min, max)``, so the result holds ``a < b`` pairs, each unordered non-edge at most once, and
+        ``M`` is clamped to ``num_non_edges // 2``.  It needs a SYMMETRIC edge list in one id space and ``allow_loops=False``."""
         M = self.num_edges if num_neg_samples is None else int(num_neg_samples)
+        if canonical and (self.allow_loops or self.n_src != self.n_dst):
+            raise ValueError("NegativeSampler.pairs: canonical=True needs one id space and allow_loops=False")
         if M < 0:
             raise ValueError(f"NegativeSampler.pairs: num_neg_samples must not be negative, got {num_neg_samples}")
         if window is not None and int(window) < 1:
@@ -107,12 +115,12 @@ class NegativeSampler:
         if torch.cuda.is_current_stream_capturing():
             raise NpiError("NegativeSampler.pairs reads a size back from the device and cannot run inside a stream capture")
         key = self._key(draw)
-        M = min(M, self.num_non_edges)
+        M = min(M, self.num_non_edges // 2 if canonical else self.num_non_edges)
         dev, lib, side = self.device, load(), self.side
         out = torch.empty((2, M), dtype=torch.int64, device=dev)
         if M == 0:
             return out
-        W = max(self.default_window(M) if window is None else int(window), 1)
+        W = max(self.default_window(M, canonical) if window is None else int(window), 1)
         info = torch.zeros(2, dtype=torch.int32, device=dev)
         st = stream_ptr(dev)
         flags = 0 if self.allow_loops else 1
@@ -121,6 +129,8 @@ class NegativeSampler:
             cand, ws = self._buffers(W)
             check(lib.npi_negative_candidates(ptr(side.rowptr), ptr(side.col), self.n_dst, self.n_src, key, 0, W, flags, ptr(cand[0]),
                                               ptr(cand[1]), st), "npi_negative_candidates")
+            if canonical:
+                check(lib.npi_split_canonical(ptr(cand[0]), ptr(cand[1]), W, st), "npi_split_canonical")
             check(lib.npi_negative_distinct(ptr(cand[0]), ptr(cand[1]), W, self.n_src, self.n_dst, M, ptr(out[0]), ptr(out[1]),
                                             ptr(info), ptr(ws), int(ws.numel()), st), "npi_negative_distinct")
             found, consumed = info.tolist()                    # the ONE host read of a draw in the usual case
