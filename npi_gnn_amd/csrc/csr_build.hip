@@ -166,16 +166,14 @@ extern "C" int npi_csr_build_ex(const int64_t* key_nodes, const int64_t* val_nod
     NPI_REQUIRE(E >= 0 && N >= 0 && n_cols >= 0, "npi_csr_build: negative size");
     NPI_REQUIRE((build_flags & ~(NPI_CSR_DROP_EQUAL | NPI_CSR_SORT_COLUMNS)) == 0, "npi_csr_build: unknown build flag");
     NPI_REQUIRE(item_edges_ok(item_edges), "npi_csr_build: item_edges must be 64 or NPI_ITEM_EDGES (npi_item_edges gives the hint)");
-    NPI_REQUIRE(E + N + 1 < (int64_t)0x7fffffff, "npi_csr_build: E + N does not fit int32");
-    NPI_REQUIRE(n_cols < (int64_t)0x7fffffff && loop_col_offset >= 0 && loop_col_offset + N <= (n_cols > N ? n_cols : N),
+    NPI_REQUIRE(E + N + 1 < NPI_INDEX_LIMIT, "npi_csr_build: E + N does not fit int32");
+    NPI_REQUIRE(n_cols < NPI_INDEX_LIMIT && loop_col_offset >= 0 && loop_col_offset + N <= (n_cols > N ? n_cols : N),
                 "npi_csr_build: column range does not fit");
     NPI_REQUIRE(rowptr && item_row && status && workspace, "npi_csr_build: null output");
     NPI_REQUIRE(E == 0 || (key_nodes && val_nodes && col), "npi_csr_build: null edge arrays");
+    if (workspace_short("npi_csr_build", workspace_bytes, PairSort::bytes(E))) return NPI_ERR_WORKSPACE;
     PairSort ps;
-    if (!ps.carve(workspace, workspace_bytes, E)) {
-        set_error("npi_csr_build: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)PairSort::bytes(E));
-        return NPI_ERR_WORKSPACE;
-    }
+    (void)ps.carve(workspace, workspace_bytes, E);         // (the length was checked above)
     (void)hipMemsetAsync(status, 0, sizeof(int32_t), stream);
     const int drop_equal = build_flags & NPI_CSR_DROP_EQUAL;
     if (E > 0) {
@@ -208,11 +206,6 @@ namespace npi {
 // the whole wave, one after the other.  count: per-row counts and the tile's total.  fill: the tile's base is the sum of the
 // totals in front of it (a few hundred integers), the rows' offsets an exclusive scan inside the tile -- no scan launch.
 constexpr int CF_SHORT = 8;
-__device__ __forceinline__ int cf_wave_sum(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-    return v;
-}
 __global__ void __launch_bounds__(256)
 csr_filter_count_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const int32_t* __restrict__ perm,
                         const int32_t* __restrict__ remap, int n_out, int32_t* __restrict__ cnt, int32_t* __restrict__ tile_total) {
@@ -232,11 +225,11 @@ csr_filter_count_kernel(const int32_t* __restrict__ rowptr, const int32_t* __res
         const int bb = __shfl(b, l, WAVE), ee = __shfl(e, l, WAVE);
         int cc = 0;
         for (int p = bb + lane; p < ee; p += WAVE) cc += remap[col[p]] >= 0 ? 1 : 0;
-        cc = cf_wave_sum(cc);
+        cc = wave_sum(cc);
         if (lane == l) c = cc;
     }
     if (valid) cnt[r2] = c;
-    const int ws_ = cf_wave_sum(c);
+    const int ws_ = wave_sum(c);
     if (lane == 0) wtot[wave] = ws_;
     __syncthreads();
     if (t == 0) tile_total[blockIdx.x] = wtot[0] + wtot[1] + wtot[2] + wtot[3];
@@ -252,7 +245,7 @@ csr_filter_fill_kernel(const int32_t* __restrict__ rowptr, const int32_t* __rest
     // entries in front of this tile
     int s = 0;
     for (int i = t; i < (int)blockIdx.x; i += 256) s += tile_total[i];
-    s = cf_wave_sum(s);
+    s = wave_sum(s);
     if (lane == 0) wtot[wave] = s;
     __syncthreads();
     if (t == 0) base_s = wtot[0] + wtot[1] + wtot[2] + wtot[3];

@@ -13,13 +13,6 @@
 
 namespace npi {
 
-// wave-wide sum by xor shuffles (butterfly order; segsum.hip's wave_sum_dpp adds in another order: not interchangeable bit for bit)
-__device__ __forceinline__ float wave_sum_xor(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-    return v;
-}
-
 // a_dst[i,h] = <h[i,h,:], att[h,:C]>, a_src[i,h] = <h[i,h,:], att[h,C:]>; one wave per node
 __global__ void __launch_bounds__(256)
 gat_scores_kernel(const float* __restrict__ h, int64_t ldh, const float* __restrict__ att, int N, int H, int C,
@@ -36,8 +29,8 @@ gat_scores_kernel(const float* __restrict__ h, int64_t ldh, const float* __restr
             pd = fmaf(v, at[c], pd);
             ps = fmaf(v, at[C + c], ps);
         }
-        pd = wave_sum_xor(pd);
-        ps = wave_sum_xor(ps);
+        pd = wave_sum(pd);
+        ps = wave_sum(ps);
         if (lane == 0) {
             a_dst[(int64_t)i * H + hd] = pd;
             a_src[(int64_t)i * H + hd] = ps;
@@ -57,7 +50,7 @@ gat_rowdot_kernel(const float* __restrict__ a, int64_t lda, const float* __restr
         const float* __restrict__ rb = b + (int64_t)i * ldb + (int64_t)hd * C;
         float p = 0.f;
         for (int c = lane; c < C; c += WAVE) p = fmaf(ra[c], rb[c] - (bias ? bias[hd * C + c] : 0.f), p);
-        p = wave_sum_xor(p);
+        p = wave_sum(p);
         if (lane == 0) D[(int64_t)i * H + hd] = p;
     }
 }
@@ -90,7 +83,7 @@ gat_scores_vec_kernel(const float* __restrict__ h, int64_t ldh, const float* __r
         }
 #pragma unroll
         for (int r = 0; r < ROWS_PER_WAVE; ++r) {
-            const float d = wave_sum_xor(pd[r]), sc = wave_sum_xor(ps[r]);
+            const float d = wave_sum(pd[r]), sc = wave_sum(ps[r]);
             if (lane == 0 && i0 + r < N) {
                 a_dst[(int64_t)(i0 + r) * H + hd] = d;
                 a_src[(int64_t)(i0 + r) * H + hd] = sc;
@@ -161,7 +154,7 @@ gat_rowdot_vec_kernel(const float* __restrict__ a, int64_t lda, const float* __r
         }
 #pragma unroll
         for (int r = 0; r < ROWS_PER_WAVE; ++r) {
-            const float d = wave_sum_xor(p[r]);
+            const float d = wave_sum(p[r]);
             if (lane == 0 && i0 + r < N) D[(int64_t)(i0 + r) * H + hd] = d;
         }
     }
@@ -229,7 +222,7 @@ gat_rowdot_colsum_kernel(const float* __restrict__ a, int64_t lda, const float* 
                 float p = 0.f;
 #pragma unroll
                 for (int k = 0; k < NCHK; ++k) p += (hd[k] == h) ? pk[k] : 0.f;
-                p = wave_sum_xor(p);
+                p = wave_sum(p);
                 if (lane == 0 && live) D[(int64_t)(r0 + r) * H + h] = p;
             }
         }
@@ -401,7 +394,7 @@ gat_edge_grad_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restri
                     for (int c = 0; c < NCH; ++c)
                         if (hd[c] == h)
                             p += dr[c].x * hv[u][c].x + dr[c].y * hv[u][c].y + dr[c].z * hv[u][c].z + dr[c].w * hv[u][c].w;
-                    p = wave_sum_xor(p);
+                    p = wave_sum(p);
                     if (staged) {
                         if (lane == 0) pb[(j + u) * H + h] = p;
                     } else if (lane == 0) {

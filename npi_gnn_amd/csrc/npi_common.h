@@ -24,7 +24,28 @@ inline int check_launch(const char* what) {
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t align_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
 
+// Counts and ids travel as int32 on the device: a count lies in [0, 2^31 - 1), an id bound (ids in [0, n)) in [1, 2^31 - 1)
+constexpr int64_t NPI_INDEX_LIMIT = (int64_t)0x7fffffff;
+inline bool count_ok(int64_t n) { return n >= 0 && n < NPI_INDEX_LIMIT; }
+inline bool id_bound_ok(int64_t n) { return n >= 1 && n < NPI_INDEX_LIMIT; }
+
+// true, with the error text set, when the caller's workspace is too short; the caller picks the status it returns
+inline bool workspace_short(const char* what, int64_t have, int64_t need) {
+    if (have >= need) return false;
+    set_error("%s: workspace %lld < %lld bytes", what, (long long)have, (long long)need);
+    return true;
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+
+// sum over the 64 lanes by xor shuffles, a fixed butterfly; every lane ends with the sum (segsum.hip's wave_sum_dpp adds in another
+// order: not interchangeable bit for bit)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
+    return v;
+}
 
 // value of `v` in lane `l` (l wave-uniform) as a scalar
 __device__ __forceinline__ int bcast_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }

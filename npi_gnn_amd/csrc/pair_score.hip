@@ -15,13 +15,6 @@ namespace npi {
 constexpr int PS_WAVES = 4;                    // wavefronts (blocks of 64 pairs) per workgroup: one partial per 256 pairs
 constexpr int PS_SUM_THREADS = 256;            // the workgroup that adds the partials
 
-// fixed xor tree over the wave; every lane ends with the sum
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, WAVE);
-    return v;
-}
-
 // Loss term and d term / d logit of one pair, before the 1 / count of its part.  s = sigmoid(x) in f32 throughout.
 //   GAE: PyG's expressions literally, EPS = 1e-15: a positive -log(s + EPS), a negative -log(1 - s + EPS), and what autograd
 //        gives for exactly those: -s q / (s + EPS) and s q / (q + EPS) with ONE q = 1 - s in numerator and denominator.
@@ -110,7 +103,7 @@ pair_score_kernel(const int64_t* __restrict__ src, const int64_t* __restrict__ d
     }
     if (MODE != NPI_PAIR_LOGITS) {
         if (partials == nullptr) return;                                                     // (uniform over the workgroup)
-        t = wave_sum_f64(t);
+        t = wave_sum(t);
         if (lane == 0) wsum[wv] = t;
         __syncthreads();
         if (threadIdx.x == 0) partials[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];

@@ -17,17 +17,6 @@
 
 namespace npi {
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-    return v;
-}
-__device__ __forceinline__ int wsum_i(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-    return v;
-}
-
 // score[i] = tanh(<x_i, w> / ||w||_2); one wave per node
 __global__ void __launch_bounds__(256)
 topk_score_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w, int N, int F,
@@ -41,8 +30,8 @@ topk_score_kernel(const float* __restrict__ x, int64_t ldx, const float* __restr
         dot = fmaf(x[(int64_t)i * ldx + c], wc, dot);
         nn = fmaf(wc, wc, nn);
     }
-    dot = wsum(dot);
-    nn = wsum(nn);
+    dot = wave_sum(dot);
+    nn = wave_sum(nn);
     if (lane == 0) score[i] = tanhf(dot / sqrtf(nn));
 }
 
@@ -215,7 +204,7 @@ filter_flag_kernel(const int64_t* __restrict__ src, const int64_t* __restrict__ 
             if (pad_src != nullptr) { pad_src[e] = -1; pad_dst[e] = -1; }   // filter_write overwrites the first `count`
         }
     }
-    c = (int)wsum((float)c);          // <= 512 per wave: exact in f32
+    c = (int)wave_sum((float)c);          // <= 512 per wave: exact in f32
     if (lane_id() == 0) atomicAdd(&cnt, c);
     __syncthreads();
     if (threadIdx.x == 0) tile_counts[blockIdx.x] = cnt;
@@ -271,11 +260,11 @@ filter_write_kernel(const int64_t* __restrict__ src, const int64_t* __restrict__
         all += v;
         if (i < (int)blockIdx.x) pre += v;
     }
-    pre = wsum_i(pre);
+    pre = wave_sum(pre);
     if (lane == 0) { wcnt[wave] = c; psum[wave] = pre; }
     if (blockIdx.x == 0 && total != nullptr && !scanned) {
         __shared__ int asum[4];
-        all = wsum_i(all);
+        all = wave_sum(all);
         if (lane == 0) asum[wave] = all;
         __syncthreads();
         if (threadIdx.x == 0) *total = asum[0] + asum[1] + asum[2] + asum[3];
@@ -401,9 +390,9 @@ __device__ __forceinline__ void topk_bwd_row(const float* __restrict__ x, int64_
         dot = fmaf(xv, wc, dot);
         nn = fmaf(wc, wc, nn);
     }
-    ds = wsum(ds);
-    dot = wsum(dot);
-    nn = wsum(nn);
+    ds = wave_sum(ds);
+    dot = wave_sum(dot);
+    nn = wave_sum(nn);
     const float inv_norm = 1.f / sqrtf(nn);
     const float sc = score[i];
     if (dscore_o) ds += dscore_o[p];
@@ -510,8 +499,8 @@ topk_weight_grad_reduce_kernel(const float* __restrict__ part, int nchunks, cons
     }
     for (int q = ql * 64 + col; q < nchunks; q += 256) z += part[(int64_t)q * (F + 1) + F];
     for (int k = ql * 64 + col; k < F; k += 256) nn = fmaf(w[k], w[k], nn);
-    z = wsum(z);
-    nn = wsum(nn);
+    z = wave_sum(z);
+    nn = wave_sum(nn);
     s_s[ql][col] = s;
     if (col == 0) { z_s[ql] = z; n_s[ql] = nn; }
     __syncthreads();
@@ -636,7 +625,7 @@ extern "C" int npi_topk_score(const float* x, int64_t ldx, const float* w, int64
 
 extern "C" int npi_graph_bounds(const int64_t* batch, int64_t N, int64_t B, int32_t* graph_ptr, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(N >= 0 && B >= 0 && N < 0x7fffffff, "npi_graph_bounds: bad size");
+    NPI_REQUIRE(count_ok(N) && B >= 0, "npi_graph_bounds: bad size");
     NPI_REQUIRE(graph_ptr && (N == 0 || batch), "npi_graph_bounds: null pointer");
     graph_bounds_kernel<<<(unsigned)ceil_div(B + 1, 256), 256, 0, stream>>>(batch, N, B, graph_ptr);
     return check_launch("npi_graph_bounds");
@@ -670,15 +659,13 @@ extern "C" int npi_topk_select_sorted(const float* score, const int64_t* batch, 
                                       float ratio, int32_t* out_ptr, int32_t* perm, int32_t* remap, void* workspace,
                                       int64_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(N >= 0 && B >= 0 && N < (int64_t)0x7fffffff && ratio > 0.f && ratio <= 1.f, "npi_topk_select_sorted: bad argument");
+    NPI_REQUIRE(count_ok(N) && B >= 0 && ratio > 0.f && ratio <= 1.f, "npi_topk_select_sorted: bad argument");
     NPI_REQUIRE(out_ptr && graph_ptr && (N == 0 || (score && batch && perm && remap && workspace)), "npi_topk_select_sorted: null pointer");
     topk_kept_offsets_kernel<<<1, 256, 0, stream>>>(graph_ptr, (int)B, ratio, out_ptr);
     if (N == 0 || B == 0) return check_launch("npi_topk_select_sorted");
+    if (workspace_short("npi_topk_select_sorted", workspace_bytes, PairSort::bytes(N))) return NPI_ERR_WORKSPACE;
     PairSort ps;
-    if (!ps.carve(workspace, workspace_bytes, N)) {
-        set_error("npi_topk_select_sorted: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)PairSort::bytes(N));
-        return NPI_ERR_WORKSPACE;
-    }
+    (void)ps.carve(workspace, workspace_bytes, N);         // (the length was checked above)
     const unsigned nb = (unsigned)ceil_div(N, 256);
     topk_score_keys_kernel<<<nb, 256, 0, stream>>>(score, N, ps.keys_a, ps.vals_a);
     ps.sort(32, stream);
@@ -709,7 +696,7 @@ extern "C" int npi_filter_adj(const int64_t* src, const int64_t* dst, int64_t E,
                                  int64_t* out_src, int64_t* out_dst, int32_t* count, int32_t* workspace,
                                  int pad_tail, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(E >= 0 && E < 0x7fffffff, "npi_filter_adj: bad size");
+    NPI_REQUIRE(count_ok(E), "npi_filter_adj: bad size");
     NPI_REQUIRE(count && workspace, "npi_filter_adj: null pointer");
     if (E == 0) { (void)hipMemsetAsync(count, 0, sizeof(int32_t), stream); return check_launch("npi_filter_adj"); }
     NPI_REQUIRE(src && dst && remap && out_src && out_dst, "npi_filter_adj: null pointer");
@@ -744,7 +731,7 @@ extern "C" int npi_topk_gather_bwd(const float* x, int64_t ldx, const float* sco
                                    int64_t n_out, int64_t F, const float* dxo, int64_t lddxo, const float* dscore_o,
                                    float* dx, int64_t lddx, float* dzv, float* dzz, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(n_out >= 0 && F > 0 && n_out < 0x7fffffff, "npi_topk_gather_bwd: bad size");
+    NPI_REQUIRE(count_ok(n_out) && F > 0, "npi_topk_gather_bwd: bad size");
     if (n_out == 0) return NPI_OK;
     NPI_REQUIRE(x && score && w && perm && dxo && dx && dzv && dzz, "npi_topk_gather_bwd: null pointer");
     topk_gather_bwd_kernel<<<(unsigned)ceil_div(n_out, 4), 256, 0, stream>>>(x, ldx, score, w, perm, (int)n_out, (int)F, dxo,
@@ -756,7 +743,7 @@ extern "C" int npi_topk_gather_bwd_ex(const float* x, int64_t ldx, const float* 
                                       int64_t N, int64_t F, const float* dxo, int64_t lddxo, const float* dscore_o,
                                       float* dx, int64_t lddx, float* dzv, float* dzz, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(N >= 0 && F > 0 && N < 0x7fffffff, "npi_topk_gather_bwd_ex: bad size");
+    NPI_REQUIRE(count_ok(N) && F > 0, "npi_topk_gather_bwd_ex: bad size");
     if (N == 0) return NPI_OK;
     NPI_REQUIRE(x && score && w && remap && dxo && dx && dzv && dzz, "npi_topk_gather_bwd_ex: null pointer");
     topk_gather_bwd_all_kernel<<<(unsigned)ceil_div(N, 4), 256, 0, stream>>>(x, ldx, score, w, remap, (int)N, (int)F, dxo, lddxo,
@@ -772,7 +759,7 @@ extern "C" int npi_topk_weight_grad(const float* x, int64_t ldx, const int32_t* 
                                     int64_t n_out, int64_t F, const float* w, float* dw, float* workspace,
                                     int64_t workspace_elems, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(n_out >= 0 && F > 0 && n_out < 0x7fffffff, "npi_topk_weight_grad: bad size");
+    NPI_REQUIRE(count_ok(n_out) && F > 0, "npi_topk_weight_grad: bad size");
     NPI_REQUIRE(x && perm && dzv && dzz && w && dw && workspace, "npi_topk_weight_grad: null pointer");
     if (workspace_elems < npi_topk_weight_grad_workspace_elems(n_out, F)) {
         set_error("npi_topk_weight_grad: workspace too small");
@@ -800,7 +787,7 @@ extern "C" int npi_readout_max_mean_bwd_ex(const float* x, int64_t ldx, const in
                                            const float* out, const float* dout, float* dx, int64_t lddx, int64_t N,
                                            void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(B >= 0 && F > 0 && N < 0x7fffffff, "npi_readout_max_mean_bwd: bad size");
+    NPI_REQUIRE(B >= 0 && F > 0 && N < NPI_INDEX_LIMIT, "npi_readout_max_mean_bwd: bad size");
     if (B == 0) {
         NPI_REQUIRE(N <= 0, "npi_readout_max_mean_bwd_ex: rows without a graph need B >= 1 (or zero dx yourself)");
         return NPI_OK;
@@ -821,7 +808,7 @@ extern "C" int npi_readout_max_mean_bwd_ex(const float* x, int64_t ldx, const in
 extern "C" int npi_confusion_update(const float* scores, int64_t lds, int64_t C, const int64_t* y, int64_t B,
                                     int64_t* counts, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(B >= 0 && C >= 1 && C < 0x7fffffff && lds >= C, "npi_confusion_update: bad size");
+    NPI_REQUIRE(B >= 0 && id_bound_ok(C) && lds >= C, "npi_confusion_update: bad size");
     if (B == 0) return NPI_OK;
     NPI_REQUIRE(scores && y && counts, "npi_confusion_update: null pointer");
     const int64_t blocks = ceil_div(B, 256);

@@ -100,19 +100,11 @@ __device__ __forceinline__ long long rank_pack(const RankLane& r) {
     return ((long long)p << 32) | (long long)e;
 }
 
-// fixed xor tree over the wave (long long or double); every lane ends with the sum
-template <typename T>
-__device__ __forceinline__ T rank_wave_sum(T v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, WAVE);
-    return v;
-}
-
 __global__ void __launch_bounds__(RANK_THREADS)
 rank_totals_kernel(const uint32_t* __restrict__ keys, const int32_t* __restrict__ labels, int M, long long* __restrict__ tile_tot) {
     __shared__ long long wsum[RANK_WAVES];
     const int64_t base = (int64_t)blockIdx.x * RANK_TILE + (int64_t)threadIdx.x * RANK_ITEMS;
-    const long long v = rank_wave_sum(rank_pack(rank_load(keys, labels, M, base)));
+    const long long v = wave_sum(rank_pack(rank_load(keys, labels, M, base)));
     if (lane_id() == 0) wsum[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) tile_tot[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
@@ -181,8 +173,8 @@ rank_terms_kernel(const int32_t* __restrict__ tps, const int32_t* __restrict__ f
             ap += ((double)(tp - tp0) / P) * ((double)tp / ((double)tp + (double)fp));
         }
     }
-    ap = rank_wave_sum(ap);
-    u2 = rank_wave_sum(u2);
+    ap = wave_sum(ap);
+    u2 = wave_sum(u2);
     if (lane_id() == 0) { wap[threadIdx.x >> 6] = ap; wu2[threadIdx.x >> 6] = u2; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -217,7 +209,6 @@ rank_finish_kernel(const double* __restrict__ ap_part, const long long* __restri
     }
 }
 
-static bool rank_size_ok(int64_t M) { return M >= 0 && M < 0x7fffffff; }
 static int64_t rank_tiles(int64_t M) { return ceil_div(M > 0 ? M : 1, RANK_TILE); }
 // behind the sorter's part: tile totals [tiles + 1] int64, AP partials [tiles] fp64, U2 partials [tiles] int64
 static int64_t rank_tail_bytes(int64_t M) { return align_up((rank_tiles(M) + 1) * 8, 256) + 2 * align_up(rank_tiles(M) * 8, 256); }
@@ -227,7 +218,7 @@ static int64_t rank_tail_bytes(int64_t M) { return align_up((rank_tiles(M) + 1) 
 using namespace npi;
 
 extern "C" int64_t npi_rank_workspace_bytes(int64_t M) {
-    if (!rank_size_ok(M)) return -1;
+    if (!count_ok(M)) return -1;
     return align_up(PairSort::bytes(M), 256) + rank_tail_bytes(M);
 }
 
@@ -235,7 +226,7 @@ extern "C" int npi_rank_metrics(const float* scores, const int64_t* y, int64_t M
                                 float* thr, int32_t* tps, int32_t* fps, int32_t* status, void* workspace, int64_t workspace_bytes,
                                 void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(rank_size_ok(M), "npi_rank_metrics: bad size (M must lie in [0, 2^31 - 1))");
+    NPI_REQUIRE(count_ok(M), "npi_rank_metrics: bad size (M must lie in [0, 2^31 - 1))");
     NPI_REQUIRE(y != nullptr || (n_pos >= 0 && n_pos <= M), "npi_rank_metrics: n_pos outside [0, M] (it names the positives when y is NULL)");
     NPI_REQUIRE(result && counts, "npi_rank_metrics: null pointer (result and counts are required)");
     NPI_REQUIRE((thr && tps && fps) || (!thr && !tps && !fps), "npi_rank_metrics: the curve is thr, tps and fps together, or all three NULL");

@@ -4,9 +4,8 @@
 //
 // THE RULE (include/npi_gnn.h restates it; DESIGN.md "Neighbour sampling").  Over the by-target CSR of the edge list as it is, target
 // v has the row [rowptr[v], rowptr[v + 1]) of d entries; position p in [0, d) gets the 64-bit key (h32(seed, hop, v, p) << 32) | p,
-//     mix64(z)  : z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31     (uint64, wrapping)
-//     base      = mix64(mix64(seed + 0x9E3779B97F4A7C15 * (hop + 1)) ^ (v * 0xD6E8FEB86659FD93))
-//     h32       = mix64(base + 0x9E3779B97F4A7C15 * (p + 1)) >> 32
+//     base      = draw_stream(mix64(seed + G (hop + 1)), v)        (mix64, G, draw_stream, draw_word: draw.h; uint64, wrapping)
+//     h32       = draw_word(base, p + 1) >> 32
 // (splitmix64: a stream per (seed, hop, v), its p-th output, upper half) and the sample is the k entries with the smallest keys,
 // emitted in ascending p.  Keys are distinct (p is part of the key), so the sample is a pure function of (seed, hop, v, d, k): no
 // launch geometry, batch composition or timing enters.  Everything below only finds T = the k-th smallest key of a row and then
@@ -19,6 +18,7 @@
 // select over the 64-bit keys, 8 bits a pass, stopping at the first pass after which every remaining key is taken.  A budget too
 // large for LDS (a fraction of a hub) runs the same select straight over the positions, hashing once per pass.  Entries (col, eid)
 // are read for the winners only.  Integer LDS counters, no float anywhere except the fraction's ceil (in double, as the host's).
+#include "draw.h"
 #include "sort.h"
 
 namespace npi {
@@ -32,16 +32,12 @@ constexpr int RELABEL_CHUNK = 4 * RELABEL_BLOCK;  // scratch entries per workgro
 constexpr int STATUS_BAD_TARGET = NPI_STATUS_BAD_TARGET_ID;
 constexpr int STATUS_BAD_OFFSETS = NPI_STATUS_BAD_SAMPLE_SIZES;
 
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// the hop enters the UNMIXED seed (the rule is older than draw_root and part of the ABI as it is)
 __host__ __device__ __forceinline__ uint64_t row_base(int64_t seed, int64_t hop, int64_t v) {
-    return mix64(mix64((uint64_t)seed + 0x9E3779B97F4A7C15ull * (uint64_t)(hop + 1)) ^ ((uint64_t)v * 0xD6E8FEB86659FD93ull));
+    return draw_stream(mix64((uint64_t)seed + DRAW_G * (uint64_t)(hop + 1)), (uint64_t)v);
 }
 __host__ __device__ __forceinline__ uint64_t key_of(uint64_t base, uint32_t p) {
-    const uint64_t h = mix64(base + 0x9E3779B97F4A7C15ull * ((uint64_t)p + 1)) >> 32;
+    const uint64_t h = draw_word(base, (uint64_t)p + 1) >> 32;
     return (h << 32) | p;
 }
 
@@ -287,9 +283,7 @@ __global__ void __launch_bounds__(RELABEL_BLOCK)
 relabel_count_kernel(const int32_t* __restrict__ scratch, int64_t N, int32_t* __restrict__ chunk_cnt) {
     __shared__ int wsum[RELABEL_BLOCK / WAVE];
     const int64_t i = (int64_t)blockIdx.x * RELABEL_CHUNK + 4 * (int64_t)threadIdx.x;
-    int c = __popc(marks_of(scratch, i, N));
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    const int c = wave_sum(__popc(marks_of(scratch, i, N)));
     if (lane_id() == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) chunk_cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -461,15 +455,10 @@ __global__ void coalesce_compact_kernel(const uint32_t* __restrict__ src_s, cons
 
 using namespace npi;
 
-static unsigned grid_for(int64_t work, int block) {
-    const int64_t g = ceil_div(work > 0 ? work : 1, block);
-    return (unsigned)(g < 4096 ? g : 4096);
-}
-
 extern "C" int npi_sample_counts(const int32_t* rowptr, int64_t N, const int64_t* targets, int64_t n, int64_t budget, float frac,
                                  int32_t* cnt, int32_t* status, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(N >= 0 && N < 0x7fffffff && n >= 0 && n < 0x7fffffff, "npi_sample_counts: bad size");
+    NPI_REQUIRE(count_ok(N) && count_ok(n), "npi_sample_counts: bad size");
     NPI_REQUIRE(budget >= 0, "npi_sample_counts: a budget below 1");
     if (budget > 0) NPI_REQUIRE(frac == 0.f, "npi_sample_counts: a budget and a fraction together");
     else NPI_REQUIRE(frac > 0.f && frac <= 1.f, "npi_sample_counts: a budget below 1, or a fraction outside (0, 1]");
@@ -484,8 +473,8 @@ extern "C" int npi_sample_select(const int32_t* rowptr, const int32_t* col, cons
                                  int64_t n, const int64_t* offsets, int64_t seed, int64_t hop, int32_t* out_src, int32_t* out_eid,
                                  int32_t* out_tgt, int64_t n_out, int32_t* status, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(N >= 0 && N < 0x7fffffff && n >= 0 && n < 0x7fffffff && n_out >= 0 && n_out <= 0x7fffffff, "npi_sample_select: bad size");
-    NPI_REQUIRE(hop >= 0 && hop < 0x7fffffff, "npi_sample_select: bad hop");
+    NPI_REQUIRE(count_ok(N) && count_ok(n) && n_out >= 0 && n_out <= NPI_INDEX_LIMIT, "npi_sample_select: bad size");
+    NPI_REQUIRE(count_ok(hop), "npi_sample_select: bad hop");
     if (n == 0) return NPI_OK;
     NPI_REQUIRE(rowptr && targets && offsets, "npi_sample_select: null pointer");
     if (n_out > 0) NPI_REQUIRE(col && eid && out_src && out_eid && out_tgt, "npi_sample_select: null pointer");
@@ -495,7 +484,7 @@ extern "C" int npi_sample_select(const int32_t* rowptr, const int32_t* col, cons
 }
 
 extern "C" int64_t npi_sample_workspace_elems(int64_t N) {
-    if (N < 0 || N >= 0x7fffffff) return -1;
+    if (!count_ok(N)) return -1;
     return ceil_div(N, RELABEL_CHUNK) + 1;
 }
 
@@ -503,7 +492,7 @@ extern "C" int npi_sample_relabel_count(const int32_t* out_src, const int64_t* o
                                         int add_self_loops, int32_t* scratch, int64_t N, int32_t* workspace, int32_t* info,
                                         void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(N >= 0 && N < 0x7fffffff && n >= 0 && n < 0x7fffffff && n_out >= 0 && n_out <= 0x7fffffff,
+    NPI_REQUIRE(count_ok(N) && count_ok(n) && n_out >= 0 && n_out <= NPI_INDEX_LIMIT,
                 "npi_sample_relabel_count: bad size");
     NPI_REQUIRE(offsets && workspace && info, "npi_sample_relabel_count: null pointer");
     NPI_REQUIRE(N == 0 || scratch, "npi_sample_relabel_count: null pointer");
@@ -511,8 +500,8 @@ extern "C" int npi_sample_relabel_count(const int32_t* out_src, const int64_t* o
     NPI_REQUIRE(((uintptr_t)scratch & 15) == 0, "npi_sample_relabel_count: scratch must be 16-byte aligned");
     const int64_t nb = ceil_div(N, RELABEL_CHUNK);
     if (N > 0 && (n_out > 0 || (add_self_loops && n > 0)))
-        relabel_mark_kernel<<<grid_for(n_out > n ? n_out : n, 256), 256, 0, stream>>>(out_src, offsets, n, n_out, targets, add_self_loops,
-                                                                                     scratch, N);
+        relabel_mark_kernel<<<stride_grid(n_out > n ? n_out : n, 256, 4096), 256, 0, stream>>>(out_src, offsets, n, n_out, targets,
+                                                                                              add_self_loops, scratch, N);
     if (nb > 0) relabel_count_kernel<<<(unsigned)nb, RELABEL_BLOCK, 0, stream>>>(scratch, N, workspace);
     relabel_scan_kernel<<<1, 1024, 0, stream>>>(workspace, nb, offsets, n, n_out, info);
     return check_launch("npi_sample_relabel_count");
@@ -523,7 +512,7 @@ extern "C" int npi_sample_relabel(int32_t* scratch, int64_t N, const int32_t* wo
                                   int64_t* edge_src, int64_t* edge_dst, int64_t* e_id, int64_t* res_n_id, int32_t* status,
                                   void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(N >= 0 && N < 0x7fffffff && n >= 0 && n < 0x7fffffff && E >= 0 && E <= 0x7fffffff && U >= 0 && U <= N,
+    NPI_REQUIRE(count_ok(N) && count_ok(n) && E >= 0 && E <= NPI_INDEX_LIMIT && U >= 0 && U <= N,
                 "npi_sample_relabel: bad size");
     NPI_REQUIRE(workspace && (N == 0 || scratch), "npi_sample_relabel: null pointer");
     NPI_REQUIRE(U == 0 || n_id, "npi_sample_relabel: null pointer");
@@ -533,8 +522,8 @@ extern "C" int npi_sample_relabel(int32_t* scratch, int64_t N, const int32_t* wo
     const int64_t nb = ceil_div(N, RELABEL_CHUNK);
     if (nb > 0) relabel_positions_kernel<<<(unsigned)nb, RELABEL_BLOCK, 0, stream>>>(scratch, N, workspace, nb, U, n_id, status);
     if (E > 0 || (res_n_id != nullptr && n > 0))
-        relabel_edges_kernel<<<grid_for(E > n ? E : n, 256), 256, 0, stream>>>(scratch, N, out_src, out_eid, out_tgt, E, targets, n, edge_src,
-                                                                              edge_dst, e_id, res_n_id);
+        relabel_edges_kernel<<<stride_grid(E > n ? E : n, 256, 4096), 256, 0, stream>>>(scratch, N, out_src, out_eid, out_tgt, E, targets, n,
+                                                                                       edge_src, edge_dst, e_id, res_n_id);
     if (N > 0) (void)hipMemsetAsync(scratch, 0, (size_t)N * sizeof(int32_t), stream);   // the scratch is left as it was found
     return check_launch("npi_sample_relabel");
 }
@@ -543,14 +532,14 @@ extern "C" int npi_sample_union(const int32_t* src_g, const int32_t* dst_g, int6
                                 int64_t N, int32_t* workspace, int64_t n_id_cap, int64_t* n_id, int32_t* src_l, int32_t* dst_l,
                                 int64_t* sub_b_id, int32_t* info, int32_t* status, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(N >= 0 && N < 0x7fffffff && n >= 0 && n < 0x7fffffff && E >= 0 && E < 0x7fffffff && n_id_cap >= 0 && n_id_cap <= N,
+    NPI_REQUIRE(count_ok(N) && count_ok(n) && count_ok(E) && n_id_cap >= 0 && n_id_cap <= N,
                 "npi_sample_union: bad size");
     if (E == 0 && n == 0) return NPI_OK;
     NPI_REQUIRE(workspace && info && (N == 0 || scratch) && (n_id_cap == 0 || n_id), "npi_sample_union: null pointer");
     NPI_REQUIRE((E == 0 || (src_g && dst_g && src_l && dst_l)) && (n == 0 || (b_id && sub_b_id)), "npi_sample_union: null pointer");
     NPI_REQUIRE(((uintptr_t)scratch & 15) == 0, "npi_sample_union: scratch must be 16-byte aligned");
     const int64_t nb = ceil_div(N, RELABEL_CHUNK);
-    const unsigned grid = grid_for(E > n ? E : n, 256);
+    const unsigned grid = stride_grid(E > n ? E : n, 256, 4096);
     union_mark_kernel<<<grid, 256, 0, stream>>>(src_g, dst_g, E, b_id, n, scratch, N, status);
     if (nb > 0) relabel_count_kernel<<<(unsigned)nb, RELABEL_BLOCK, 0, stream>>>(scratch, N, workspace);
     relabel_scan_kernel<<<1, 1024, 0, stream>>>(workspace, nb, nullptr, 0, E, info);
@@ -563,7 +552,7 @@ extern "C" int npi_sample_union(const int32_t* src_g, const int32_t* dst_g, int6
 }
 
 extern "C" int64_t npi_sample_coalesce_workspace_bytes(int64_t E) {
-    if (E < 0 || E >= (int64_t)0x7fffffff) return -1;
+    if (!count_ok(E)) return -1;
     return PairSort::bytes(E);
 }
 
@@ -571,15 +560,13 @@ extern "C" int npi_sample_coalesce(const int32_t* src_l, const int32_t* dst_l, c
                                    int64_t* edge_dst, int64_t* e_id, int32_t* info, void* workspace, int64_t workspace_bytes,
                                    void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(E >= 0 && E < (int64_t)0x7fffffff && U >= 0 && U < (int64_t)0x7fffffff, "npi_sample_coalesce: bad size");
+    NPI_REQUIRE(count_ok(E) && count_ok(U), "npi_sample_coalesce: bad size");
     if (E == 0) return NPI_OK;
     NPI_REQUIRE(src_l && dst_l && eid && edge_src && edge_dst && e_id && info && workspace, "npi_sample_coalesce: null pointer");
     NPI_REQUIRE(((uintptr_t)workspace & 15) == 0, "npi_sample_coalesce: workspace must be 16-byte aligned");
+    if (workspace_short("npi_sample_coalesce", workspace_bytes, PairSort::bytes(E))) return NPI_ERR_WORKSPACE;
     PairSort ps;
-    if (!ps.carve(workspace, workspace_bytes, E)) {
-        set_error("npi_sample_coalesce: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)PairSort::bytes(E));
-        return NPI_ERR_WORKSPACE;
-    }
+    (void)ps.carve(workspace, workspace_bytes, E);         // (the length was checked above)
     const int bits = key_bits(U);                        // local ids lie in [0, U)
     const unsigned eb = (unsigned)ceil_div(E, 256);
     coalesce_keys_kernel<<<eb, 256, 0, stream>>>(dst_l, E, ps.keys_a, ps.vals_a);

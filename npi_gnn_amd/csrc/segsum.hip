@@ -135,7 +135,7 @@ __device__ __forceinline__ float wave_max(float v) {
     return bcast_f(v, WAVE - 1);
 }
 // wave-wide sum in the same fixed DPP order (deterministic): the partial dots of the fused GATConv forward's scores
-// (gat.hip's wave_sum_xor adds in butterfly order: not interchangeable bit for bit)
+// (npi_common.h's wave_sum adds in butterfly order: not interchangeable bit for bit)
 __device__ __forceinline__ float wave_sum_dpp(float v) {
 #define NPI_DPP_ADD(CTRL, ROWS) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWS, 0xf, false))
     NPI_DPP_ADD(0x111, 0xf);

@@ -3,7 +3,7 @@
 // `train_test_split_edges` (host `torch.randperm`, a dense [N, N] mask for the held-out negatives, `to_undirected` through
 // `torch_sparse.coalesce`) and the reference's 5-fold key split (src/generate_edgelist.py:460-494, src/train.py:108-184).
 //
-// RULE S (include/npi_gnn.h states it).  Wrapping uint64, mix64 / G the sampler's:
+// RULE S (include/npi_gnn.h states it).  Wrapping uint64, mix64 / G are draw.h's:
 //     base = mix64(mix64(mix64(key) + 5 G));   r_e = mix64(base + G (e + 1)),   e = the column's index in the INPUT
 // The kept columns (both ids in range; with `upper` also src < dst) come out in ascending (r_e, e).  npi_split_permute:
 //   split_keep_kernel     keep flag per column; an id out of range is reported, never dereferenced
@@ -17,19 +17,14 @@
 // npi_split_canonical rewrites Rule P's candidates (s, d) as (min, max) for the held-out negatives of one id space;
 // npi_split_undirected writes both orientations as int32 pairs and hands them to npi_sample_coalesce (sample.hip).
 // One lane per entry, grid-stride; integers only; the one atomic is the status OR.  Nothing allocates or keeps state.
+#include "draw.h"
 #include "sort.h"
 
 namespace npi {
 
 constexpr int SPLIT_BLOCK = 256;
-constexpr uint64_t SPLIT_G = 0x9E3779B97F4A7C15ull;
 
-__host__ __device__ __forceinline__ uint64_t split_mix64(uint64_t z) {
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ uint64_t split_word(uint64_t base, int32_t e) { return split_mix64(base + SPLIT_G * ((uint64_t)e + 1)); }
+__device__ __forceinline__ uint64_t split_word(uint64_t base, int32_t e) { return draw_word(base, (uint64_t)e + 1); }
 
 __device__ __forceinline__ bool split_in_range(int64_t s, int64_t d, int64_t n_src, int64_t n_dst) {
     return s >= 0 && s < n_src && d >= 0 && d < n_dst;
@@ -137,14 +132,8 @@ static int64_t split_words_bytes(int64_t n) { return align_up((n > 0 ? n : 1) * 
 
 using namespace npi;
 
-// enough workgroups for 8 wavefronts on every SIMD of 256 CUs; more work than that strides
-static unsigned split_grid(int64_t work) {
-    const int64_t g = ceil_div(work, SPLIT_BLOCK);
-    return (unsigned)(g < 2048 ? g : 2048);
-}
-
 extern "C" int64_t npi_split_workspace_bytes(int64_t E) {
-    if (E < 0 || E >= (int64_t)0x7fffffff) return -1;
+    if (!count_ok(E)) return -1;
     return split_sort_bytes(E) + split_words_bytes(E + 1);
 }
 
@@ -152,8 +141,8 @@ extern "C" int npi_split_permute(const int64_t* src, const int64_t* dst, int64_t
                                  int64_t* out_src, int64_t* out_dst, int64_t* e_id, int32_t* info, int32_t* status, void* workspace,
                                  int64_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(E >= 0 && E < (int64_t)0x7fffffff, "npi_split_permute: bad size (E must lie in [0, 2^31 - 1))");
-    NPI_REQUIRE(n_src >= 1 && n_src < (int64_t)0x7fffffff && n_dst >= 1 && n_dst < (int64_t)0x7fffffff, "npi_split_permute: bad id bound");
+    NPI_REQUIRE(count_ok(E), "npi_split_permute: bad size (E must lie in [0, 2^31 - 1))");
+    NPI_REQUIRE(id_bound_ok(n_src) && id_bound_ok(n_dst), "npi_split_permute: bad id bound");
     NPI_REQUIRE((flags & ~NPI_SPLIT_UPPER) == 0, "npi_split_permute: unknown flag");
     NPI_REQUIRE(info, "npi_split_permute: null pointer (info is required)");
     if (E == 0) {
@@ -162,15 +151,12 @@ extern "C" int npi_split_permute(const int64_t* src, const int64_t* dst, int64_t
     }
     NPI_REQUIRE(src && dst && out_src && out_dst && e_id && workspace, "npi_split_permute: null pointer");
     NPI_REQUIRE(((uintptr_t)workspace & 15) == 0, "npi_split_permute: workspace must be 16-byte aligned");
-    if (workspace_bytes < npi_split_workspace_bytes(E)) {
-        set_error("npi_split_permute: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)npi_split_workspace_bytes(E));
-        return NPI_ERR_ARG;
-    }
+    if (workspace_short("npi_split_permute", workspace_bytes, npi_split_workspace_bytes(E))) return NPI_ERR_ARG;
     PairSort ps;
     (void)ps.carve(workspace, split_sort_bytes(E), E);          // (the length was checked above)
     int32_t* pos = (int32_t*)((char*)workspace + split_sort_bytes(E));
-    const uint64_t base = split_mix64(split_mix64(split_mix64((uint64_t)key) + 5 * SPLIT_G));
-    const unsigned grid = split_grid(E + 1);
+    const uint64_t base = mix64(draw_root(key, DRAW_RULE_S));     // Rule S alone mixes its root once more
+    const unsigned grid = stride_grid(E + 1, SPLIT_BLOCK, 2048);
 
     split_keep_kernel<<<grid, SPLIT_BLOCK, 0, stream>>>(src, dst, E, n_src, n_dst, flags & NPI_SPLIT_UPPER, pos, status);
     exclusive_scan_i32(pos, E + 1, ps.counts, stream);          // (the sorter's histograms are free until the first sort)
@@ -184,15 +170,15 @@ extern "C" int npi_split_permute(const int64_t* src, const int64_t* dst, int64_t
 
 extern "C" int npi_split_canonical(int32_t* cand_src, int32_t* cand_dst, int64_t W, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(W >= 0 && W < (int64_t)0x7fffffff, "npi_split_canonical: bad window size");
+    NPI_REQUIRE(count_ok(W), "npi_split_canonical: bad window size");
     if (W == 0) return NPI_OK;
     NPI_REQUIRE(cand_src && cand_dst, "npi_split_canonical: null pointer");
-    split_canonical_kernel<<<split_grid(W), SPLIT_BLOCK, 0, stream>>>(cand_src, cand_dst, W);
+    split_canonical_kernel<<<stride_grid(W, SPLIT_BLOCK, 2048), SPLIT_BLOCK, 0, stream>>>(cand_src, cand_dst, W);
     return check_launch("npi_split_canonical");
 }
 
 // 2 E entries go through the coalesce: both have to stay below 2^31 - 1, and so has the id N of the placeholder pair
-static bool undirected_size_ok(int64_t E) { return E >= 0 && 2 * E < (int64_t)0x7fffffff; }
+static bool undirected_size_ok(int64_t E) { return E >= 0 && 2 * E < NPI_INDEX_LIMIT; }
 
 extern "C" int64_t npi_split_undirected_workspace_bytes(int64_t E) {
     if (!undirected_size_ok(E)) return -1;
@@ -204,7 +190,7 @@ extern "C" int npi_split_undirected(const int64_t* src, const int64_t* dst, int6
                                     void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     NPI_REQUIRE(undirected_size_ok(E), "npi_split_undirected: bad size (2 E must lie in [0, 2^31 - 1))");
-    NPI_REQUIRE(N >= 1 && N < (int64_t)0x7fffffff - 1, "npi_split_undirected: bad id bound");
+    NPI_REQUIRE(N >= 1 && N < NPI_INDEX_LIMIT - 1, "npi_split_undirected: bad id bound");
     NPI_REQUIRE(info, "npi_split_undirected: null pointer (info is required)");
     if (E == 0) {
         if (hipMemsetAsync(info, 0, sizeof(int32_t), stream) != hipSuccess) return check_launch("npi_split_undirected");
@@ -212,15 +198,11 @@ extern "C" int npi_split_undirected(const int64_t* src, const int64_t* dst, int6
     }
     NPI_REQUIRE(src && dst && out_src && out_dst && e_id && workspace, "npi_split_undirected: null pointer");
     NPI_REQUIRE(((uintptr_t)workspace & 15) == 0, "npi_split_undirected: workspace must be 16-byte aligned");
-    if (workspace_bytes < npi_split_undirected_workspace_bytes(E)) {
-        set_error("npi_split_undirected: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                  (long long)npi_split_undirected_workspace_bytes(E));
-        return NPI_ERR_ARG;
-    }
+    if (workspace_short("npi_split_undirected", workspace_bytes, npi_split_undirected_workspace_bytes(E))) return NPI_ERR_ARG;
     const int64_t pitch = split_words_bytes(2 * E);
     char* ws = (char*)workspace;
     int32_t *row = (int32_t*)ws, *col = (int32_t*)(ws + pitch), *eid = (int32_t*)(ws + 2 * pitch);
-    split_orient_kernel<<<split_grid(E), SPLIT_BLOCK, 0, stream>>>(src, dst, E, N, row, col, eid, status);
+    split_orient_kernel<<<stride_grid(E, SPLIT_BLOCK, 2048), SPLIT_BLOCK, 0, stream>>>(src, dst, E, N, row, col, eid, status);
     if (check_launch("npi_split_undirected") != NPI_OK) return NPI_ERR_LAUNCH;
     const int rc = npi_sample_coalesce(row, col, eid, 2 * E, N + 1, out_src, out_dst, e_id, info, ws + 3 * pitch,
                                        workspace_bytes - 3 * pitch, stream_);

@@ -167,7 +167,7 @@ extern "C" int npi_subgraph_fill(const int32_t* ptr, const int32_t* nbr, const u
                                  int32_t* status, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     NPI_REQUIRE(B >= 0 && B < 0x3fffffff, "npi_subgraph_fill: bad size");
-    NPI_REQUIRE(n_nodes >= 0 && n_pairs >= 0 && n_nodes <= 0x7fffffff && n_pairs <= 0x7fffffff, "npi_subgraph_fill: bad totals");
+    NPI_REQUIRE(n_nodes >= 0 && n_pairs >= 0 && n_nodes <= NPI_INDEX_LIMIT && n_pairs <= NPI_INDEX_LIMIT, "npi_subgraph_fill: bad totals");
     if (status != nullptr) (void)hipMemsetAsync(status, 0, sizeof(int32_t), stream);
     if (B == 0) return NPI_OK;
     NPI_REQUIRE(ptr && nbr && ok && keys && node_off && pair_off && node_id && batch && edge_src && edge_dst,

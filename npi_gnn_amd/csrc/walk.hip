@@ -2,38 +2,18 @@
 // node2vec-master/src/main.py (alias-sampled walks, then gensim) and PyG 1.4.2 `torch_geometric.nn.models.Node2Vec` over
 // `torch_cluster.random_walk`: the walks by rejection (no alias tables), the pairs in the layout npi_pair_score takes.
 //
-// RULE W (include/npi_gnn.h states it).  Wrapping uint64 throughout; mix64, G, C, mulhi are the negative sampler's:
+// RULE W (include/npi_gnn.h states it).  Wrapping uint64 throughout; mix64, G, C, mulhi and the row search are draw.h's:
 //     root = mix64(mix64(key) + 3 G);  base_w = mix64(root ^ (w C));  word(i) = mix64(base_w + G i),  i = 1, 2, ...
 // Attempt n (counted over the WHOLE walk) draws pick = word(2n + 1), accept = word(2n + 2); the candidate col[rowptr[v] + mulhi(pick, d)]
 // is accepted iff (accept >> 32) < thr, thr one of three integers in [0, 2^32] chosen by where the candidate lies relative to the
 // previous node (the same node / a neighbour of it: a binary search of its SORTED by-source row / neither).  No float anywhere.
 // One lane per walk, grid-stride: a chain of dependent gathers, few registers, no LDS; the kernel relies on occupancy.
-#include "npi_common.h"
+#include "draw.h"
 
 namespace npi {
 
 constexpr int WALK_BLOCK = 256;
-constexpr uint64_t WALK_G = 0x9E3779B97F4A7C15ull;
-constexpr uint64_t WALK_C = 0xD6E8FEB86659FD93ull;
 constexpr uint64_t WALK_ONE = (uint64_t)1 << 32;           // the threshold that accepts every word
-
-__host__ __device__ __forceinline__ uint64_t walk_mix64(uint64_t z) {
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// is x a column of row u?  Rows ascend; empty rows, rows of one entry and rows with repeated columns all occur.
-__device__ __forceinline__ bool walk_is_edge(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int32_t u, int32_t x) {
-    int lo = rowptr[u];
-    const int end = rowptr[u + 1];
-    int hi = end;
-    while (lo < hi) {                                      // first position with col >= x
-        const int mid = lo + ((hi - lo) >> 1);
-        if (col[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo < end && col[lo] == x;
-}
 
 // UNIFORM: all three thresholds are 2^32 -- every first attempt is accepted, so neither the accept word nor the search is needed
 // and step t uses word(2t - 1): the same walks as the general kernel gives for these thresholds.
@@ -53,7 +33,7 @@ random_walk_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict
             for (int64_t t = 0; t <= L; ++t) row[t] = -1;
             continue;
         }
-        const uint64_t base = walk_mix64(root ^ ((uint64_t)w * WALK_C));
+        const uint64_t base = draw_stream(root, (uint64_t)w);
         uint64_t n = 0;                                    // attempts made so far, over the whole walk
         int32_t prev = -1, v = (int32_t)s;
         row[0] = s;
@@ -63,18 +43,18 @@ random_walk_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict
             int32_t x = v;                                 // a dead end: the walk stays, no word is consumed
             if (d > 0) {
                 if constexpr (UNIFORM) {
-                    x = col[lo + (int)__umul64hi(walk_mix64(base + WALK_G * (2 * n + 1)), (uint64_t)d)];
+                    x = col[lo + (int)draw_below(draw_word(base, 2 * n + 1), (uint64_t)d)];
                     ++n;
                 } else {
                     bool ok = false;
                     for (int a = 0; a < tries && !ok; ++a, ++n) {
-                        const uint64_t pick = walk_mix64(base + WALK_G * (2 * n + 1));
-                        const uint64_t accept = walk_mix64(base + WALK_G * (2 * n + 2));
-                        x = col[lo + (int)__umul64hi(pick, (uint64_t)d)];
+                        const uint64_t pick = draw_word(base, 2 * n + 1);
+                        const uint64_t accept = draw_word(base, 2 * n + 2);
+                        x = col[lo + (int)draw_below(pick, (uint64_t)d)];
                         uint64_t thr = WALK_ONE;
                         if (t > 1) {
                             if (x == prev) thr = thr_ret;
-                            else thr = (search && walk_is_edge(rowptr, col, prev, x)) ? thr_nbr : thr_far;
+                            else thr = (search && row_has(rowptr, col, prev, x)) ? thr_nbr : thr_far;
                         }
                         ok = (accept >> 32) < thr;
                     }
@@ -107,7 +87,7 @@ walk_pairs_kernel(const int64_t* __restrict__ walks, uint32_t W, int64_t L, uint
         const uint32_t j = r / W, w = r - j * W;
         const int64_t* __restrict__ row = walks + (int64_t)w * (L + 1) + j;
         src[m] = row[0];
-        dst[m] = pos ? row[k] : (int64_t)__umul64hi(walk_mix64(nbase + WALK_G * (uint64_t)(m - n_pos + 1)), (uint64_t)N);
+        dst[m] = pos ? row[k] : (int64_t)draw_below(draw_word(nbase, (uint64_t)(m - n_pos + 1)), (uint64_t)N);
     }
 }
 
@@ -115,52 +95,45 @@ walk_pairs_kernel(const int64_t* __restrict__ walks, uint32_t W, int64_t L, uint
 
 using namespace npi;
 
-// enough workgroups for 8 wavefronts on every SIMD of 256 CUs; more work than that strides
-static unsigned walk_grid(int64_t work) {
-    const int64_t g = ceil_div(work, WALK_BLOCK);
-    return (unsigned)(g < 2048 ? g : 2048);
-}
-
-static const int64_t WALK_LIMIT = 0x7fffffff;
-
 extern "C" int npi_random_walk(const int32_t* rowptr, const int32_t* col, int64_t N, const int64_t* start, int64_t W, int64_t L,
                                int64_t key, int64_t thr_ret, int64_t thr_nbr, int64_t thr_far, int64_t tries, int64_t* walks,
                                int32_t* status, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(W >= 0 && W < WALK_LIMIT, "npi_random_walk: bad walk count");
-    NPI_REQUIRE(L >= 0 && L < WALK_LIMIT, "npi_random_walk: bad walk length");
-    NPI_REQUIRE(N >= 1 && N < WALK_LIMIT, "npi_random_walk: bad id bound");
-    NPI_REQUIRE(tries >= 1 && tries < WALK_LIMIT, "npi_random_walk: tries below 1");
+    NPI_REQUIRE(count_ok(W), "npi_random_walk: bad walk count");
+    NPI_REQUIRE(count_ok(L), "npi_random_walk: bad walk length");
+    NPI_REQUIRE(id_bound_ok(N), "npi_random_walk: bad id bound");
+    NPI_REQUIRE(tries >= 1 && tries < NPI_INDEX_LIMIT, "npi_random_walk: tries below 1");
     NPI_REQUIRE((uint64_t)thr_ret <= WALK_ONE && (uint64_t)thr_nbr <= WALK_ONE && (uint64_t)thr_far <= WALK_ONE,
                 "npi_random_walk: a threshold outside [0, 2^32]");
     NPI_REQUIRE(rowptr && col, "npi_random_walk: null pointer");
     if (W == 0) return NPI_OK;
     NPI_REQUIRE(start && walks, "npi_random_walk: null pointer");
-    const uint64_t root = walk_mix64(walk_mix64((uint64_t)key) + 3 * WALK_G);
+    const uint64_t root = draw_root(key, DRAW_RULE_W);
+    const unsigned grid = stride_grid(W, WALK_BLOCK, 2048);
     if ((uint64_t)thr_ret == WALK_ONE && (uint64_t)thr_nbr == WALK_ONE && (uint64_t)thr_far == WALK_ONE)
-        random_walk_kernel<true><<<walk_grid(W), WALK_BLOCK, 0, stream>>>(rowptr, col, N, start, W, L, root, thr_ret, thr_nbr, thr_far,
-                                                                         (int)tries, walks, status);
+        random_walk_kernel<true><<<grid, WALK_BLOCK, 0, stream>>>(rowptr, col, N, start, W, L, root, thr_ret, thr_nbr, thr_far, (int)tries,
+                                                                  walks, status);
     else
-        random_walk_kernel<false><<<walk_grid(W), WALK_BLOCK, 0, stream>>>(rowptr, col, N, start, W, L, root, thr_ret, thr_nbr, thr_far,
-                                                                          (int)tries, walks, status);
+        random_walk_kernel<false><<<grid, WALK_BLOCK, 0, stream>>>(rowptr, col, N, start, W, L, root, thr_ret, thr_nbr, thr_far, (int)tries,
+                                                                   walks, status);
     return check_launch("npi_random_walk");
 }
 
 extern "C" int npi_walk_pairs(const int64_t* walks, int64_t W, int64_t L, int64_t c, int64_t S, int64_t N, int64_t key, int64_t* src,
                               int64_t* dst, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(W >= 0 && W < WALK_LIMIT, "npi_walk_pairs: bad walk count");
-    NPI_REQUIRE(L >= 0 && L < WALK_LIMIT && S >= 0 && S < WALK_LIMIT, "npi_walk_pairs: bad size");
-    NPI_REQUIRE(N >= 1 && N < WALK_LIMIT, "npi_walk_pairs: bad id bound");
+    NPI_REQUIRE(count_ok(W), "npi_walk_pairs: bad walk count");
+    NPI_REQUIRE(count_ok(L) && count_ok(S), "npi_walk_pairs: bad size");
+    NPI_REQUIRE(id_bound_ok(N), "npi_walk_pairs: bad id bound");
     NPI_REQUIRE(c >= 2 && c <= L + 1, "npi_walk_pairs: the context size lies in [2, L + 1]");
     // M = J W (c - 1 + S): every factor is below 2^31, so the two products are taken one at a time in 64 bits
     const int64_t R = (L + 2 - c) * W;
-    NPI_REQUIRE(R < WALK_LIMIT && R * (c - 1 + S) < WALK_LIMIT, "npi_walk_pairs: more than 2^31 - 2 pairs");
+    NPI_REQUIRE(R < NPI_INDEX_LIMIT && R * (c - 1 + S) < NPI_INDEX_LIMIT, "npi_walk_pairs: more than 2^31 - 2 pairs");
     if (W == 0) return NPI_OK;
     NPI_REQUIRE(walks && src && dst, "npi_walk_pairs: null pointer");
     const int64_t M = R * (c - 1 + S);
-    const uint64_t nbase = walk_mix64(walk_mix64((uint64_t)key) + 4 * WALK_G);
-    walk_pairs_kernel<<<walk_grid(M), WALK_BLOCK, 0, stream>>>(walks, (uint32_t)W, L, (uint32_t)(c - 1), (uint32_t)S, N, nbase,
-                                                             (uint32_t)(R * (c - 1)), (uint32_t)M, src, dst);
+    const uint64_t nbase = draw_root(key, DRAW_RULE_W_NEG);
+    walk_pairs_kernel<<<stride_grid(M, WALK_BLOCK, 2048), WALK_BLOCK, 0, stream>>>(walks, (uint32_t)W, L, (uint32_t)(c - 1), (uint32_t)S, N,
+                                                                                   nbase, (uint32_t)(R * (c - 1)), (uint32_t)M, src, dst);
     return check_launch("npi_walk_pairs");
 }

@@ -25,28 +25,9 @@ from typing import Optional, Tuple, Union
 import torch
 
 from . import graph as _graph
+from ._draw import _LIMIT, check_edge_index, epoch_seed, next_draw, pair_size
 from ._lib import NpiError, check, load, ptr, require_gpu, stream_ptr
 from .graph import build_side
-from .sampler import epoch_seed
-
-_LIMIT = 2 ** 31 - 1            # W, K and the id bounds stay below it (include/npi_gnn.h)
-
-
-def _pair_size(size) -> Tuple[int, int]:
-    """``size``: ``(n_src, n_dst)``, or an int ``N`` for one id space"""
-    entries = (size, size) if isinstance(size, int) and not isinstance(size, bool) else size
-    if not isinstance(entries, (tuple, list)) or len(entries) != 2 or \
-            any(isinstance(n, bool) or not isinstance(n, int) for n in entries):
-        raise ValueError(f"NegativeSampler: size is an int N or a pair (n_src, n_dst) of ints, got {size!r}")
-    n_src, n_dst = entries
-    if n_src < 1 or n_dst < 1 or n_src >= _LIMIT or n_dst >= _LIMIT:
-        raise ValueError(f"NegativeSampler: size entries lie in [1, 2^31 - 1), got {size!r}")
-    return n_src, n_dst
-
-
-def _check_edge_index(edge_index) -> None:
-    if not isinstance(edge_index, torch.Tensor) or edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
-        raise ValueError("edge_index must be a LongTensor of shape [2, E]")
 
 
 class NegativeSampler:
@@ -60,8 +41,8 @@ class NegativeSampler:
     return at most (counted once, when the sampler is built).  The sort workspace belongs to the sampler and is reused."""
 
     def __init__(self, edge_index: torch.Tensor, size: Union[int, Tuple[int, int]], seed: int = 0, allow_loops: bool = True):
-        _check_edge_index(edge_index)
-        self.n_src, self.n_dst = _pair_size(size)
+        check_edge_index(edge_index)
+        self.n_src, self.n_dst = pair_size(size, "NegativeSampler")
         self.device = require_gpu(edge_index)
         self.edge_index, self.seed, self.allow_loops, self.draw = edge_index, int(seed), bool(allow_loops), 0
         n_src, n_dst = self.n_src, self.n_dst
@@ -114,7 +95,7 @@ class NegativeSampler:
             self._check_window(int(window))
         if torch.cuda.is_current_stream_capturing():
             raise NpiError("NegativeSampler.pairs reads a size back from the device and cannot run inside a stream capture")
-        key = self._key(draw)
+        key = epoch_seed(self.seed, next_draw(self, draw))
         M = min(M, self.num_non_edges // 2 if canonical else self.num_non_edges)
         dev, lib, side = self.device, load(), self.side
         out = torch.empty((2, M), dtype=torch.int64, device=dev)
@@ -173,7 +154,7 @@ class NegativeSampler:
         K = int(src.numel())
         if K >= _LIMIT:
             raise NpiError("NegativeSampler.corrupt: more than 2^31 - 2 slots in one call")
-        key = self._key(draw)
+        key = epoch_seed(self.seed, next_draw(self, draw))
         out = torch.empty(K, dtype=torch.int64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         side = self.side
@@ -181,13 +162,6 @@ class NegativeSampler:
                                           ptr(status), stream_ptr(dev)), "npi_negative_targets")
         _graph.note_status(status)
         return out
-
-    def _key(self, draw: Optional[int]) -> int:
-        """the key of a call: that of ``draw``, or of the sampler's counter, which it then counts up"""
-        if draw is None:
-            draw = self.draw
-            self.draw = draw + 1
-        return epoch_seed(self.seed, int(draw))
 
     def __repr__(self):
         return f"NegativeSampler(size=({self.n_src}, {self.n_dst}), edges={self.num_edges}, non_edges={self.num_non_edges})"

@@ -37,24 +37,9 @@ from typing import List, Optional, Sequence, Union
 import torch
 
 from . import graph as _graph
+from ._draw import epoch_seed                                 # noqa: F401  (tools and tests import it from here)
 from ._lib import NpiError, check, load, ptr, require_gpu, stream_ptr
 from .graph import BipartiteGraph, CSRGraph, build_side
-
-_M64 = (1 << 64) - 1
-
-
-def _mix64(z: int) -> int:
-    z &= _M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
-    return z ^ (z >> 31)
-
-
-def epoch_seed(seed: int, epoch: int) -> int:
-    """The ``seed`` argument of ``npi_sample_select`` for one epoch, as a signed 64-bit integer: a splitmix64 step over
-    ``seed`` and ``epoch`` (every hop of every batch of the epoch uses it; the hop index is a separate argument of the key)."""
-    z = _mix64(_mix64(int(seed)) + 0x9E3779B97F4A7C15 * (int(epoch) + 1))
-    return z - (1 << 64) if z >= (1 << 63) else z
 
 
 def epoch_batches(n: int, batch_size: int, shuffle: bool, drop_last: bool, seed: int, epoch: int) -> List[torch.Tensor]:

@@ -31,9 +31,9 @@ from typing import Iterator, Optional, Tuple, Union
 import torch
 
 from . import graph as _graph
+from ._draw import _LIMIT, check_edge_index, epoch_seed, next_draw, num_nodes, pair_size
 from ._lib import NPI_SPLIT_UPPER, NpiError, check, load, ptr, require_gpu, stream_ptr
-from .negative import _LIMIT, NegativeSampler, _check_edge_index, _pair_size
-from .sampler import epoch_seed
+from .negative import NegativeSampler
 
 
 @dataclass
@@ -77,9 +77,7 @@ def _check_folds(k) -> int:
 
 def _num_nodes(N, who: str) -> int:
     """one id space: an int in [1, 2^31 - 2) (the undirected form needs one id above every node's)"""
-    if isinstance(N, bool) or not isinstance(N, int) or N < 1 or N >= _LIMIT - 1:
-        raise ValueError(f"{who}: the number of nodes is an int in [1, 2^31 - 2), got {N!r}")
-    return N
+    return num_nodes(N, who, _LIMIT - 1, "the number of nodes")
 
 
 def _no_capture(who: str) -> None:
@@ -112,7 +110,7 @@ def _undirected(src: torch.Tensor, dst: torch.Tensor, N: int) -> torch.Tensor:
 def to_undirected(edge_index: torch.Tensor, num_nodes: int) -> torch.Tensor:
     """PyG's ``to_undirected(edge_index, num_nodes)``: both orientations of every column, sorted by ``(row, col)``, equal pairs
     once.  A column with an id outside ``[0, num_nodes)`` is dropped and reported (``graph.check_pending()`` raises)."""
-    _check_edge_index(edge_index)
+    check_edge_index(edge_index)
     N = _num_nodes(num_nodes, "to_undirected")
     require_gpu(edge_index)
     return _undirected(edge_index[0].contiguous(), edge_index[1].contiguous(), N)
@@ -130,9 +128,9 @@ class EdgeSplitter:
     been asked for -- the ``NegativeSampler`` over the whole list belong to the splitter and are reused."""
 
     def __init__(self, edge_index: torch.Tensor, size: Union[int, Tuple[int, int]], seed: int = 0):
-        _check_edge_index(edge_index)
+        check_edge_index(edge_index)
         self.upper = isinstance(size, int)
-        self.n_src, self.n_dst = (_num_nodes(size, "EdgeSplitter"),) * 2 if self.upper else _pair_size(size)
+        self.n_src, self.n_dst = (_num_nodes(size, "EdgeSplitter"),) * 2 if self.upper else pair_size(size, "NegativeSampler")
         self.device = require_gpu(edge_index)
         self.num_edges = int(edge_index.size(1))
         if self.num_edges >= _LIMIT:
@@ -145,7 +143,7 @@ class EdgeSplitter:
     def permutation(self, draw: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The kept columns in the order of draw ``draw``: ``(edges [2, K], e_id [K])``, ``e_id`` the columns of ``edge_index``"""
         _no_capture("EdgeSplitter.permutation")
-        return self._permutation(self._draw(draw))
+        return self._permutation(next_draw(self, draw))
 
     def _permutation(self, draw: int) -> Tuple[torch.Tensor, torch.Tensor]:
         dev, lib, E = self.device, load(), self.num_edges
@@ -170,7 +168,7 @@ class EdgeSplitter:
         the result does not depend on it."""
         v, t = _check_ratios(val_ratio, test_ratio)
         _no_capture("EdgeSplitter.split")
-        draw = self._draw(draw)
+        draw = next_draw(self, draw)
         edges, e_id = self._permutation(draw)
         K = int(e_id.numel())
         n_v, n_t = int(math.floor(v * K)), int(math.floor(t * K))
@@ -190,7 +188,7 @@ class EdgeSplitter:
         contiguous folds (Rule S 3); fold ``f`` tests on its range and trains on the complement, as kept (no undirected form)."""
         k = _check_folds(k)
         _no_capture("EdgeSplitter.kfold")
-        counted, draw = draw is None, self._draw(draw)
+        counted, draw = draw is None, next_draw(self, draw)
         edges, e_id = self._permutation(draw)
         K = int(e_id.numel())
         if k > K:
@@ -227,13 +225,6 @@ class EdgeSplitter:
                 self._neg = NegativeSampler(self.edge_index, (self.n_src, self.n_dst), seed=self.seed)
         return self._neg.pairs(M, draw=draw, window=window, canonical=self.upper)
 
-    def _draw(self, draw: Optional[int]) -> int:
-        """the draw number of a call: the one given, or the splitter's counter, which it then counts up"""
-        if draw is None:
-            draw = self.draw
-            self.draw = draw + 1
-        return int(draw)
-
     def __repr__(self):
         return f"EdgeSplitter(size=({self.n_src}, {self.n_dst}), edges={self.num_edges}, upper={self.upper})"
 
@@ -242,7 +233,7 @@ def train_test_split_edges(edge_index: torch.Tensor, num_nodes: int, val_ratio: 
                            seed: int = 0) -> EdgeSplit:
     """PyG's ``train_test_split_edges(data, val_ratio, test_ratio)`` on an edge list: ``EdgeSplitter(edge_index, num_nodes,
     seed).split(val_ratio, test_ratio)``.  One splitter -- one sort of the whole list for the negatives -- per call."""
-    _check_edge_index(edge_index)
+    check_edge_index(edge_index)
     if isinstance(num_nodes, bool) or not isinstance(num_nodes, int):
         raise ValueError(f"train_test_split_edges: num_nodes is an int (one id space), got {num_nodes!r}")
     _check_ratios(val_ratio, test_ratio)

@@ -31,12 +31,10 @@ from torch import nn
 
 from . import functional as F_
 from . import graph as _graph
+from ._draw import _LIMIT, check_edge_index, epoch_seed, next_draw, num_nodes as _num_nodes
 from ._lib import NPI_PAIR_LOSS_GAE, NpiError, check, load, ptr, require_gpu, stream_ptr
 from .graph import build_side
-from .negative import _check_edge_index
-from .sampler import epoch_seed
 
-_LIMIT = 2 ** 31 - 1            # W, N, L and the pair count stay below it (include/npi_gnn.h)
 _ONE = 2 ** 32                  # the threshold that accepts every candidate
 
 
@@ -54,12 +52,6 @@ def walk_thresholds(p: float, q: float) -> Tuple[int, int, int]:
     return tuple(min(_ONE, int(math.floor(_ONE * (v / mx)))) for v in a)      # (2^32 * x is exact: the product cannot round)
 
 
-def _num_nodes(num_nodes) -> int:
-    if isinstance(num_nodes, bool) or not isinstance(num_nodes, int) or num_nodes < 1 or num_nodes >= _LIMIT:
-        raise ValueError(f"RandomWalker: num_nodes is an int in [1, 2^31 - 1), got {num_nodes!r}")
-    return num_nodes
-
-
 class RandomWalker:
     """Walks over the graph ``edge_index`` ``[2, E]`` (a GPU LongTensor, PyG layout, one id space of ``num_nodes`` nodes): a step
     goes from a node to the target of one of its out-edges.  An edge is a column of ``edge_index`` as it is: no self loop is added
@@ -70,8 +62,8 @@ class RandomWalker:
     the next call takes when it is not given one; such a call counts it up."""
 
     def __init__(self, edge_index: torch.Tensor, num_nodes: int, seed: int = 0, p: float = 1.0, q: float = 1.0, tries: int = 64):
-        _check_edge_index(edge_index)
-        self.num_nodes = _num_nodes(num_nodes)
+        check_edge_index(edge_index)
+        self.num_nodes = _num_nodes(num_nodes, "RandomWalker")
         self.thresholds = walk_thresholds(p, q)
         self.tries = int(tries)
         if self.tries < 1 or self.tries >= _LIMIT:
@@ -102,7 +94,7 @@ class RandomWalker:
         W = int(start.numel())
         if W >= _LIMIT:
             raise NpiError("RandomWalker.walks: more than 2^31 - 2 walks in one call")
-        key = self._key(draw)
+        key = epoch_seed(self.seed, next_draw(self, draw))
         out = torch.empty((W, walk_length + 1), dtype=torch.int64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         side, thr = self.side, self.thresholds
@@ -110,13 +102,6 @@ class RandomWalker:
                                      thr[2], self.tries, ptr(out), ptr(status), stream_ptr(dev)), "npi_random_walk")
         _graph.note_status(status)
         return out
-
-    def _key(self, draw: Optional[int]) -> int:
-        """the key of a call: that of ``draw``, or of the walker's counter, which it then counts up"""
-        if draw is None:
-            draw = self.draw
-            self.draw = draw + 1
-        return epoch_seed(self.seed, int(draw))
 
     def __repr__(self):
         return f"RandomWalker(num_nodes={self.num_nodes}, edges={self.num_edges}, p={self.p}, q={self.q}, tries={self.tries})"
@@ -148,7 +133,7 @@ def walk_pairs(walks: torch.Tensor, context_size: int, num_negative_samples: int
     dev = require_gpu(walks)
     walks = walks.contiguous()
     W, L = int(walks.size(0)), int(walks.size(1)) - 1
-    c, S, N = int(context_size), int(num_negative_samples), _num_nodes(num_nodes)
+    c, S, N = int(context_size), int(num_negative_samples), _num_nodes(num_nodes, "RandomWalker")
     if c < 2 or c > L + 1:
         raise ValueError(f"walk_pairs: context_size lies in [2, walk_length + 1] = [2, {L + 1}], got {context_size}")
     if S < 0:
@@ -175,7 +160,7 @@ class Node2Vec(nn.Module):
                  q: float = 1, num_negative_samples: Optional[int] = None, seed: int = 0, tries: int = 64):
         super().__init__()
         assert walk_length >= context_size
-        self.num_nodes, self.embedding_dim = _num_nodes(num_nodes), int(embedding_dim)
+        self.num_nodes, self.embedding_dim = _num_nodes(num_nodes, "RandomWalker"), int(embedding_dim)
         self.walk_length, self.context_size, self.walks_per_node = int(walk_length), int(context_size), int(walks_per_node)
         if self.context_size < 2 or self.walks_per_node < 1:
             raise ValueError("Node2Vec: context_size must be at least 2 and walks_per_node at least 1")
@@ -215,11 +200,9 @@ class Node2Vec(nn.Module):
         rw = self.walker(edge_index)
         if subset is None:
             subset = torch.arange(self.num_nodes, device=rw.device)
-        if draw is None:
-            draw = self.draw
-            self.draw = draw + 1
-        walks = rw.walks(subset.repeat(self.walks_per_node), self.walk_length, draw=int(draw))
-        pairs, n_pos = walk_pairs(walks, self.context_size, self.num_negative_samples, self.num_nodes, epoch_seed(self.seed, int(draw)))
+        draw = next_draw(self, draw)
+        walks = rw.walks(subset.repeat(self.walks_per_node), self.walk_length, draw=draw)
+        pairs, n_pos = walk_pairs(walks, self.context_size, self.num_negative_samples, self.num_nodes, epoch_seed(self.seed, draw))
         return walks, pairs, n_pos
 
     def loss(self, edge_index: torch.Tensor, subset: Optional[torch.Tensor] = None) -> torch.Tensor:

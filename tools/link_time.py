@@ -18,15 +18,14 @@ usage: python tools/link_time.py [--steps 10] [--warmup 2] [--nodes N --edges E 
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import npi_gnn_amd as npi                                     # noqa: E402
 from npi_gnn_amd.synth import bipartite_edge_index            # noqa: E402
+from _timing import device_ms, dump_json, row_summary, wall   # noqa: E402
 
 EPS = 1e-15
 
@@ -37,23 +36,6 @@ def torch_loss(zs, zd, ei, n_pos, kind):
         return -torch.log(torch.sigmoid(x[:n_pos]) + EPS).mean() - torch.log(1 - torch.sigmoid(x[n_pos:]) + EPS).mean()
     y = (torch.arange(x.numel(), device=x.device) < n_pos).float()
     return torch.nn.functional.binary_cross_entropy_with_logits(x, y)
-
-
-def device_ms(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return out, e0.elapsed_time(e1)
-
-
-def wall(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return out, 1e3 * (time.perf_counter() - t0)
 
 
 def main():
@@ -109,16 +91,13 @@ def main():
                 rows[kind].append({"forward_ms": fwd_ms, "step_wall_ms": step_ms, "torch_forward_ms": torch_fwd_ms,
                                    "torch_step_wall_ms": torch_step_ms})
     npi.graph.check_pending()
-    res = {kind: {k: {"median": statistics.median(r[k] for r in rs), "min": min(r[k] for r in rs), "max": max(r[k] for r in rs)}
-                  for k in rs[0]} for kind, rs in rows.items()}
+    res = {kind: row_summary(rs) for kind, rs in rows.items()}
     res.update(steps=args.steps, nodes=N, edges=int(ei.size(1)), features=F, pairs=2 * P,
                not_measured=["the pair-graph build and the two aggregations separately", "kernel times from a profiler",
                              "a prebuilt BipartiteGraph of the pairs", "one id space", "widths other than --features",
                              "NegativeSampler negatives (uniform random pairs stand in)"])
     print(json.dumps(res, indent=1), flush=True)
-    if args.json:
-        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-        json.dump(res, open(args.json, "w"), indent=1)
+    dump_json(res, args.json)
 
 
 if __name__ == "__main__":

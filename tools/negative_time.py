@@ -17,9 +17,7 @@ usage: python tools/negative_time.py [--draws 10] [--warmup 2] [--nodes N --edge
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
@@ -27,35 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import npi_gnn_amd as npi                                     # noqa: E402
 from npi_gnn_amd import negative as NEG                       # noqa: E402
 from npi_gnn_amd.synth import bipartite_edge_index            # noqa: E402
-
-
-class TimedLib:
-    """the C-ABI library with HIP events around the negative-sampling entry points"""
-
-    def __init__(self, lib):
-        self._lib, self.events = lib, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith("npi_negative_") or name.endswith("_bytes"):
-            return fn
-
-        def timed(*args):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            rc = fn(*args)
-            e1.record()
-            self.events.append((name, e0, e1))
-            return rc
-        return timed
-
-    def take(self):
-        torch.cuda.synchronize()
-        out = {}
-        for name, e0, e1 in self.events:
-            out[name] = out.get(name, 0.0) + e0.elapsed_time(e1)
-        self.events = []
-        return out
+from _timing import TimedLib, dump_json, row_summary, wall    # noqa: E402
 
 
 def torch_pairs(edge_codes, n_src, n_dst, M, W, gen):
@@ -73,14 +43,6 @@ def torch_pairs(edge_codes, n_src, n_dst, M, W, gen):
         W *= 2
 
 
-def wall(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return out, 1e3 * (time.perf_counter() - t0)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--draws", type=int, default=10)
@@ -96,7 +58,7 @@ def main():
     neg, build_ms = wall(lambda: npi.NegativeSampler(ei, size=N, seed=0, allow_loops=False))
     print(f"sampler construction (one column-sorted CSR build of {E} edges + the non-edge count): {build_ms:.1f} ms; {neg}", flush=True)
     edge_codes = torch.unique(ei[0] * N + ei[1])
-    timed = TimedLib(NEG.load())
+    timed = TimedLib(NEG.load(), "npi_negative_")
     NEG.load = lambda: timed                                  # the module's handle on the library, for this process only
     gen = torch.Generator(device=dev)
     gen.manual_seed(0)
@@ -125,13 +87,10 @@ def main():
             rows.append({"candidates_ms": ev["npi_negative_candidates"], "distinct_ms": ev["npi_negative_distinct"],
                          "pairs_wall_ms": pairs_ms, "torch_composed_wall_ms": torch_ms, "targets_ms": ev["npi_negative_targets"],
                          "corrupt_wall_ms": corrupt_ms, "window": W, "consumed": neg.last_consumed})
-    res = {k: {"median": statistics.median(r[k] for r in rows), "min": min(r[k] for r in rows), "max": max(r[k] for r in rows)}
-           for k in rows[0]}
+    res = row_summary(rows)
     res.update(draws=len(rows), nodes=N, edges=E, pairs_per_draw=E, non_edges=neg.num_non_edges, construction_ms=build_ms)
     print(json.dumps(res, indent=1), flush=True)
-    if args.json:
-        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-        json.dump(res, open(args.json, "w"), indent=1)
+    dump_json(res, args.json)
 
 
 if __name__ == "__main__":

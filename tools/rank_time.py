@@ -19,31 +19,13 @@ usage: python tools/rank_time.py [--steps 10] [--warmup 2] [--sizes 1048576 1677
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import npi_gnn_amd as npi                                     # noqa: E402
-
-
-def device_ms(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return out, e0.elapsed_time(e1)
-
-
-def wall(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return out, 1e3 * (time.perf_counter() - t0)
+from _timing import device_ms, dump_json, row_summary, wall   # noqa: E402
 
 
 def torch_metrics(scores, y):
@@ -115,15 +97,12 @@ def main():
                 if i >= args.warmup:
                     rows.append(row)
             npi.graph.check_pending()
-            res["cases"][f"{kind}_{M}"] = {k: {"median": statistics.median(r[k] for r in rows), "min": min(r[k] for r in rows),
-                                               "max": max(r[k] for r in rows)} for k in rows[0]}
+            res["cases"][f"{kind}_{M}"] = row_summary(rows)
             print(f"M={M} {kind}: " + ", ".join(f"{k} {v['median']:.3f}" for k, v in res["cases"][f"{kind}_{M}"].items()), flush=True)
     res["not_measured"] = ["kernel times from a profiler", "the curve functions (roc_curve / precision_recall_curve)", "GAE.test",
                            "sizes other than --sizes", "the n_pos form"]
     print(json.dumps(res, indent=1), flush=True)
-    if args.json:
-        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-        json.dump(res, open(args.json, "w"), indent=1)
+    dump_json(res, args.json)
 
 
 if __name__ == "__main__":

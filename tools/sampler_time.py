@@ -35,6 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import npi_gnn_amd as npi                                     # noqa: E402
 from npi_gnn_amd import sampler as S                          # noqa: E402
 from npi_gnn_amd.synth import bipartite_edge_index            # noqa: E402
+from _timing import TimedLib, dump_json, row_summary, wall    # noqa: E402
 
 U64 = np.uint64
 GAMMA = U64(0x9E3779B97F4A7C15)
@@ -72,35 +73,6 @@ def numpy_hop(rowptr, col, eid, targets, k, hop, seed, loops):
     return n_id, e_id, np.stack([np.searchsorted(n_id, src), tgt])
 
 
-class TimedLib:
-    """the C-ABI library with HIP events around the sampling entry points"""
-
-    def __init__(self, lib):
-        self._lib, self.events = lib, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith("npi_sample_") or name.endswith(("_elems", "_bytes")):
-            return fn
-
-        def timed(*args):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            rc = fn(*args)
-            e1.record()
-            self.events.append((name, e0, e1))
-            return rc
-        return timed
-
-    def take(self):
-        torch.cuda.synchronize()
-        out = {}
-        for name, e0, e1 in self.events:
-            out[name] = out.get(name, 0.0) + e0.elapsed_time(e1)
-        self.events = []
-        return out
-
-
 def torch_union_coalesce(b_id, src_g, dst_g, eid, tmp):
     """PyG 1.4.2 ``__produce_subgraph__`` behind the hops, composed from torch ops on the device (``tmp``: an N-entry LongTensor kept
     between calls, as PyG's ``self.tmp``); the minimum instead of ``scatter_``'s whichever-comes-last, so that the result is defined"""
@@ -118,13 +90,6 @@ def subgraph_mode(args, sampler, timed, order, seed, dev):
     """the ``--subgraph`` run (module docstring)"""
     tmp = torch.empty(args.nodes, dtype=torch.int64, device=dev)
     rows = []
-
-    def wall(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return out, 1e3 * (time.perf_counter() - t0)
     for i, pos in enumerate(order):
         b_id = pos.to(dev)
         _, whole = wall(lambda: sampler.sample_subgraph(b_id, seed))
@@ -143,8 +108,7 @@ def subgraph_mode(args, sampler, timed, order, seed, dev):
             rows.append({"union_ms": ev["npi_sample_union"], "coalesce_ms": ev["npi_sample_coalesce"], "stage_wall_ms": stage,
                          "torch_composed_wall_ms": composed, "sample_subgraph_wall_ms": whole, "entries": int(src_g.numel()),
                          "num_nodes": sub.num_nodes, "edges": int(sub.e_id.numel())})
-    res = {k: {"median": statistics.median(r[k] for r in rows), "min": min(r[k] for r in rows), "max": max(r[k] for r in rows)}
-           for k in rows[0]}
+    res = row_summary(rows)
     res["batches"] = len(rows)
     print(json.dumps(res, indent=1), flush=True)
     print("(every subgraph equal to the torch composition's)", flush=True)
@@ -173,31 +137,23 @@ def main():
     print(f"in-degree: max {int(deg.max())}, rows above 2048 entries {int((deg > 2048).sum())}", flush=True)
     seed = S.epoch_seed(0, 0)
     order = S.epoch_batches(args.nodes, bs, True, False, 0, 0)[: args.warmup + args.batches]
-    timed = TimedLib(S.load())
+    timed = TimedLib(S.load(), "npi_sample_")
     S.load = lambda: timed                                   # the sampler module's handle on the library, for this process only
     if args.subgraph:
-        res = subgraph_mode(args, sampler, timed, order, seed, dev)
-        if args.json:
-            os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-            json.dump(res, open(args.json, "w"), indent=1)
+        dump_json(subgraph_mode(args, sampler, timed, order, seed, dev), args.json)
         return
     rows, flows = [], []
     for i, pos in enumerate(order):
         targets = pos.to(dev)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        flow = sampler.sample(targets, seed)
-        torch.cuda.synchronize()
-        wall = 1e3 * (time.perf_counter() - t0)
+        flow, flow_ms = wall(lambda: sampler.sample(targets, seed))
         ev = timed.take()
         if i >= args.warmup:
             rows.append({"counts_ms": ev["npi_sample_counts"], "select_ms": ev["npi_sample_select"],
-                         "relabel_ms": ev["npi_sample_relabel_count"] + ev["npi_sample_relabel"], "data_flow_wall_ms": wall,
+                         "relabel_ms": ev["npi_sample_relabel_count"] + ev["npi_sample_relabel"], "data_flow_wall_ms": flow_ms,
                          "sources_outer": flow[0].size[0], "edges": sum(int(b.e_id.numel()) for b in flow)})
             if len(flows) < args.numpy_batches:
                 flows.append((pos.numpy(), flow))
-    res = {k: {"median": statistics.median(r[k] for r in rows), "min": min(r[k] for r in rows), "max": max(r[k] for r in rows)}
-           for k in rows[0]}
+    res = row_summary(rows)
     res["batches"] = len(rows)
     print(json.dumps(res, indent=1), flush=True)
     # the numpy restatement on the same batches
@@ -226,9 +182,7 @@ def main():
         res["numpy_data_flow_ms"] = {"median": statistics.median(np_ms), "batches": len(np_ms)}
         print(f"numpy restatement, whole DataFlow: median {statistics.median(np_ms):.0f} ms over {len(np_ms)} batches "
               "(blocks equal to the device's)", flush=True)
-    if args.json:
-        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-        json.dump(res, open(args.json, "w"), indent=1)
+    dump_json(res, args.json)
 
 
 if __name__ == "__main__":

@@ -16,22 +16,13 @@ usage: python tools/split_time.py [--steps 10] [--warmup 3] [--cases 41648:5085 
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import npi_gnn_amd as npi                                     # noqa: E402
-
-
-def wall(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return out, 1e3 * (time.perf_counter() - t0)
+from _timing import dump_json, row_summary, wall              # noqa: E402
 
 
 def torch_order(ei):
@@ -77,8 +68,7 @@ def main():
                 rows.append({"permutation_ms": perm_ms, "split_ms": split_ms, "to_undirected_ms": und_ms,
                              "torch_randperm_index_ms": t_order_ms, "torch_unique_codes_ms": t_und_ms})
         npi.graph.check_pending()
-        out = {k: {"median": statistics.median(r[k] for r in rows), "min": min(r[k] for r in rows), "max": max(r[k] for r in rows)}
-               for k in rows[0]}
+        out = row_summary(rows)
         out["first_split_with_sampler_build_ms"] = build_ms
         out["kept"], out["held_out_negatives"] = int(edges.shape[1]), int(s.val_neg_edge_index.shape[1] + s.test_neg_edge_index.shape[1])
         res["cases"][case] = out
@@ -86,9 +76,7 @@ def main():
               + f", first split {build_ms:.1f}", flush=True)
     res["not_measured"] = ["kernel times from a profiler", "kfold", "two id spaces", "PyG's dense-mask negatives (cannot run at 1M nodes)"]
     print(json.dumps(res, indent=1), flush=True)
-    if args.json:
-        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-        json.dump(res, open(args.json, "w"), indent=1)
+    dump_json(res, args.json)
 
 
 if __name__ == "__main__":

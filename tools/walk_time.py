@@ -17,9 +17,7 @@ usage: python tools/walk_time.py [--steps 10] [--warmup 2] [--json OUT] [--small
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
@@ -29,26 +27,10 @@ import npi_gnn_amd as npi                                     # noqa: E402
 from npi_gnn_amd import walk as npi_walk                      # noqa: E402
 from npi_gnn_amd.sampler import epoch_seed                    # noqa: E402
 from npi_gnn_amd.synth import bipartite_edge_index            # noqa: E402
+from _timing import device_ms, dump_json, summary, wall       # noqa: E402
 
 EPS = 1e-15
 L, C, S, D, SUBSET = 80, 10, 9, 64, 4096
-
-
-def device_ms(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return out, e0.elapsed_time(e1)
-
-
-def wall(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return out, 1e3 * (time.perf_counter() - t0)
 
 
 def torch_walk(rowptr, col, start, length):
@@ -79,10 +61,6 @@ def torch_loss(z, rw, c, s, n):
     both, n_pos = torch_pairs(rw, c, s, n)
     x = (z[both[0]] * z[both[1]]).sum(1)
     return -torch.log(torch.sigmoid(x[:n_pos]) + EPS).mean() - torch.log(1 - torch.sigmoid(x[n_pos:]) + EPS).mean()
-
-
-def summary(vals):
-    return {"median": statistics.median(vals), "min": min(vals), "max": max(vals)}
 
 
 def measure(name, ei, N, args, dev):
@@ -169,9 +147,7 @@ def main():
                not_measured=["kernel times from a profiler", "the memory traffic of the walk kernel", "a torch composition of the p/q bias",
                              "walks_per_node > 1", "another box"])
     print(json.dumps(res, indent=1), flush=True)
-    if args.json:
-        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-        json.dump(res, open(args.json, "w"), indent=1)
+    dump_json(res, args.json)
 
 
 if __name__ == "__main__":
