@@ -1072,6 +1072,64 @@ int64_t npi_split_undirected_workspace_bytes(int64_t E);
 int npi_split_undirected(const int64_t* src, const int64_t* dst, int64_t E, int64_t N, int64_t* out_src, int64_t* out_dst,
                          int64_t* e_id, int32_t* info, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Top-k link prediction: the last stage of a link-prediction run -- for each query row the k target rows it most likely links to
+ * and has no known edge to.  Replaces the dense route of PyG 1.4.2, `InnerProductDecoder.forward_all` (`torch.matmul(z, z.t())`, an
+ * [N, N] matrix) followed by a mask and `torch.topk`, and the reference's per-case loops on the host (src/case_study*.py): the
+ * scores are formed tile by tile on the matrix cores, masked and reduced to each row's best k on the chip; no score matrix is
+ * written.
+ *
+ * RULE K -- the k best targets of each query, from two f32 tables, a list of query rows, a set of excluded pairs and k.
+ *   1. Score.  score(i, j) = the f32 fmaf chain acc = fmaf(z_src[i][c], z_dst[j][c], acc) over c = 0 .. F-1 ascending, from acc =
+ *              +0: what v_mfma_f32_32x32x2_f32 computes per output element.  It depends on the two rows alone: not on the tile,
+ *              the split or the place in the query list the pair falls into.
+ *   2. Candidates of query i: every j in [0, n_dst) except (i, j) in the exclusion set; j == i under NPI_TOPK_NO_LOOPS (one id
+ *              space only); and j with a NaN score.  A NaN score of a pair that is not excluded otherwise raises
+ *              NPI_STATUS_BAD_SCORE; it is never returned.
+ *   3. Order.  Descending score with -0.0 equal to +0.0 -- ascending key of Rule R 1 --, ties by ascending j.  A total order:
+ *              the answer is unique and independent of tiling, of the split count and of the order candidates are met in.
+ *              +-inf are ordinary scores.
+ *   4. Output. Row r of scores / ids holds the first min(k, #candidates) candidates of query rows[r] in that order, the score
+ *              rebuilt from the key (-0.0 comes out as +0.0); the remaining slots hold id -1 and score -inf.
+ *   5. Bad ids. A query id outside [0, n_src) is never dereferenced: its whole row is -1 / -inf and NPI_STATUS_BAD_SOURCE_ID is
+ *              raised.
+ *
+ *   rows      : int64 [R] query ids into z_src, in any order, repeats allowed; NULL: the rows 0 .. R-1
+ *   z_src     : f32 [n_src, F], leading dimension ld_src (elements);  z_dst : f32 [n_dst, F], ld_dst.  They may be the same pointer
+ *               (one id space).  16-byte loads when F % 4 == 0 and both bases and pitches are 16-byte aligned, else guarded scalar
+ *               loads: any F >= 1 and any pitch >= F
+ *   k         : 1 <= k <= NPI_TOPK_MAX
+ *   ex_rowptr : int32 [n_src + 1], ex_col : int32: the excluded pairs as a by-source CSR with every row's columns ASCENDING
+ *               (npi_csr_build_ex with NPI_CSR_SORT_COLUMNS, no self loops; repeated columns allowed); both NULL: none
+ *   flags     : NPI_TOPK_NO_LOOPS or 0
+ *   splits    : the targets are cut into this many column ranges, each reduced on its own and merged afterwards, so that few
+ *               queries still fill the chip; 0: chosen from R and n_dst alone (nothing is read from the device).  Every value
+ *               gives bitwise the same output (more than there are tiles of 128 targets, or than 64, count as that many)
+ *   scores    : f32 [R, k];  ids : int64 [R, k]
+ *   status    : int32 device word as npi_csr_build_ex's (may be NULL): OR-ed into, never cleared here
+ *   workspace : npi_topk_links_workspace_bytes(R, n_dst, k, splits) bytes, 16-byte aligned, caller-owned (k words of 8 bytes per
+ *               query row and split)
+ * Nothing is allocated, nothing read back: the call may run inside a stream capture.  No float atomics; the only atomic is the
+ * status OR.  Refused with NPI_ERR_ARG before any launch: R, n_src or n_dst outside [0, 2^31 - 1), F outside [1, 2^31 - 1), a
+ * leading dimension below F, k outside [1, NPI_TOPK_MAX], an unknown flag, NPI_TOPK_NO_LOOPS with n_src != n_dst, only one of
+ * ex_rowptr / ex_col, negative splits; with R > 0 a null scores, ids or workspace, a null table that has rows, a workspace
+ * misaligned or shorter than the query says.  R == 0 returns NPI_OK without a launch.  npi_topk_links_workspace_bytes returns -1
+ * for R or n_dst outside [0, 2^31 - 1), k outside [1, NPI_TOPK_MAX] or negative splits.
+ *
+ * Out of scope: gradients through the selection, bf16 tables, k > NPI_TOPK_MAX, approximate search, per-pair weights, and a
+ * by-target query direction (swap the tables and flip the edge list).
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_TOPK_MAX 128
+#define NPI_TOPK_NO_LOOPS 1
+int64_t npi_topk_links_workspace_bytes(int64_t R, int64_t n_dst, int64_t k, int64_t splits);   /* -1: bad size */
+int npi_topk_links(const int64_t* rows /* NULL: rows 0..R-1 */, int64_t R,
+                   const float* z_src, int64_t ld_src, int64_t n_src,
+                   const float* z_dst, int64_t ld_dst, int64_t n_dst, int64_t F, int64_t k,
+                   const int32_t* ex_rowptr, const int32_t* ex_col /* by-source CSR, columns ascending; both NULL: none */,
+                   int flags /* NPI_TOPK_NO_LOOPS 1 */, int64_t splits,
+                   float* scores, int64_t* ids, void* workspace, int64_t workspace_bytes,
+                   int32_t* status, void* stream);
+
 /* Evaluation loop(reference src/methods.py:87-105 compares one element per Python
  * iteration, one device sync each).  counts[4] += [TP, FN, TN, FP] for pred = first arg-max of scores[i, 0..C):
  * pred 1 & y 1 -> TP, pred 1 & y 0 -> FP, pred 0 & y 1 -> FN, anything else -> TN (the reference's else

@@ -5,11 +5,13 @@
     loss = model.recon_loss(z, pos_edge_index)                 # negatives drawn on the device, as many as positives
     loss.backward()
     auc, ap = model.test(z, pos_edge_index, neg_edge_index)    # 0-d float64 device tensors: float(auc) is PyG's number
+    prob, ids = model.predict(z, k, pos_edge_index)            # [R, k] each: the k most likely NEW links of every source row
 
 ``InnerProductDecoder.forward`` is ``functional.pair_scores`` (one launch over the pair list, no sort), ``GAE.recon_loss`` is
 ``functional.link_loss`` (one forward launch, no logits written; the backward is the layers' own aggregation: no float atomics,
 bitwise reproducible), ``GAE.test`` is ``rank.rank_metrics`` (ROC-AUC and average precision of the decoder's outputs: one device
-sort, no copy to the host).  ``InnerProductDecoder.forward_all`` -- the dense ``[N, N]`` product -- is not provided.
+sort, no copy to the host).  ``InnerProductDecoder.forward_all`` -- the dense ``[N, N]`` product -- is not provided:
+``InnerProductDecoder.topk`` / ``GAE.predict`` (``topk.topk_links``) give each row's best ``k`` of it without the matrix.
 CPU tensors raise ``NpiError``: there is no CPU path.
 """
 from __future__ import annotations
@@ -22,6 +24,7 @@ from torch import nn
 from . import functional as F_
 from .negative import NegativeSampler
 from .rank import rank_metrics
+from .topk import topk_links
 
 
 def _reset(module) -> None:
@@ -43,6 +46,14 @@ class InnerProductDecoder(nn.Module):
     def forward(self, z, edge_index, sigmoid: bool = True) -> torch.Tensor:
         value = F_.pair_scores(z, edge_index)
         return torch.sigmoid(value) if sigmoid else value
+
+    def topk(self, z, k: int, exclude=None, rows: Optional[torch.Tensor] = None, sigmoid: bool = True):
+        """``(scores, ids)`` of ``topk.topk_links(z, k, exclude, rows)``: per query row the ``k`` best targets that ``exclude`` does
+        not hold, ``[R, k]`` each, the scores through ``torch.sigmoid`` as in ``forward`` (``sigmoid=False``: the logits; a slot
+        without a candidate holds id ``-1`` and logit ``-inf``, probability 0).  What ``forward_all`` followed by a mask and
+        ``torch.topk`` would give, without the ``[N, N]`` matrix."""
+        value, ids = topk_links(z, k, exclude=exclude, rows=rows)
+        return (torch.sigmoid(value) if sigmoid else value), ids
 
 
 class GAE(nn.Module):
@@ -94,3 +105,12 @@ class GAE(nn.Module):
             pos_pred = self.decode(z, pos_edge_index, sigmoid=True)
             neg_pred = self.decode(z, neg_edge_index, sigmoid=True)
             return rank_metrics(torch.cat([pos_pred, neg_pred]), n_pos=int(pos_pred.numel()))
+
+    def predict(self, z, k: int, known_edge_index, rows: Optional[torch.Tensor] = None, sigmoid: bool = True):
+        """The ``k`` most likely NEW links of every query row (``rows``: None, every source): ``(scores, ids)``, ``[R, k]`` each, by
+        ``topk.topk_links`` with ``known_edge_index`` (the ``[2, E]`` LongTensor, or a ``KnownLinks`` of it built once) excluded --
+        and ``(v, v)`` too when ``z`` is one id space, as ``recon_loss`` draws no such negative.  Scores through ``torch.sigmoid``
+        unless ``sigmoid=False``.  The inner product is scored whatever the decoder, as in ``recon_loss``."""
+        one = isinstance(z, torch.Tensor) or (isinstance(z, (tuple, list)) and len(z) == 2 and z[0] is z[1])
+        value, ids = topk_links(z, k, exclude=known_edge_index, rows=rows, allow_loops=not one)
+        return (torch.sigmoid(value) if sigmoid else value), ids

@@ -13,6 +13,7 @@
 // No float atomics, no atomics at all but the status OR; every sum has a fixed order that depends on M alone, so the result is a
 // pure function of the multiset of (score, label) pairs.  Nothing allocates or reads back.
 #include "sort.h"
+#include "rank_key.h"
 
 namespace npi {
 
@@ -21,17 +22,7 @@ constexpr int RANK_WAVES = RANK_THREADS / WAVE;
 constexpr int RANK_ITEMS = 4;                                   // one 16-byte lane of keys and one of labels per thread
 constexpr int RANK_TILE = RANK_THREADS * RANK_ITEMS;            // 1,024 positions of the sorted stream (or of the curve) per workgroup
 
-// score bits -> key.  s = score + 0.0f, done on the bits (-0.0 is the one value the addition changes), then the complement of
-// pool.hip's ascending-orderable transform: ascending key == descending score.  A NaN passes through as it is.
-__device__ __forceinline__ uint32_t rank_key(uint32_t bits) {
-    if (bits == 0x80000000u) bits = 0u;
-    const uint32_t u = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
-    return ~u;
-}
-__device__ __forceinline__ float rank_score(uint32_t key) {
-    const uint32_t u = ~key;
-    return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
-}
+// rank_key / rank_score: rank_key.h (shared with topk.hip)
 
 __global__ void __launch_bounds__(RANK_THREADS)
 rank_keys_kernel(const float* __restrict__ scores, const int64_t* __restrict__ y, int M, int n_pos, uint32_t* __restrict__ keys,

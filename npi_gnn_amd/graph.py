@@ -45,6 +45,11 @@ def pending_status(device=None) -> list:
     return out
 
 
+class BadSourceIdError(IndexError, ValueError):
+    """A source id outside its table, reported by a status word: an ``IndexError`` to the samplers' callers (torch's indexing raises
+    one there) and a ``ValueError`` to ``topk_links``' (a bad value in ``rows``)."""
+
+
 def raise_on_status(values) -> None:
     if any(int(v) & 1 for v in values):
         raise IndexError("edge_index holds a node id outside [0, num_nodes): the edges were dropped by the graph build "
@@ -59,8 +64,9 @@ def raise_on_status(values) -> None:
         raise ValueError("npi_sample_select / npi_sample_relabel: the offsets or counts they were given belong to another call; "
                          "the entries concerned were not written")
     if any(int(v) & _lib.NPI_STATUS_BAD_SOURCE_ID for v in values):
-        raise IndexError("NegativeSampler.corrupt / RandomWalker.walks: a source id outside [0, n_src): its slot (its whole walk) "
-                         "holds -1 (npi_negative_targets / npi_random_walk)")
+        raise BadSourceIdError("NegativeSampler.corrupt / RandomWalker.walks / topk_links: a source id outside [0, n_src): its slot "
+                               "(its whole walk, its whole row of results) holds -1 (npi_negative_targets / npi_random_walk / "
+                               "npi_topk_links)")
     if any(int(v) & _lib.NPI_STATUS_NO_NEGATIVE for v in values):
         raise ValueError("NegativeSampler.corrupt: a source found no non-edge target within its tries (it is joined to every "
                          "target, or tries ran out): its slot holds -1 (npi_negative_targets)")
