@@ -1130,6 +1130,60 @@ int npi_topk_links(const int64_t* rows /* NULL: rows 0..R-1 */, int64_t R,
                    float* scores, int64_t* ids, void* workspace, int64_t workspace_bytes,
                    int32_t* status, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Filtered link ranks: the ranking evaluation that goes with top-k prediction -- at which position does each held-out true link
+ * (s, t) come out among all targets s has no known edge to?  What MRR, Hits@K and mean rank in the filtered setting are made of
+ * (the protocol of the knowledge-graph literature and of the later PyG / OGB evaluators).  The dense route is the [N, N] product of
+ * `InnerProductDecoder.forward_all`, a mask and a compare-and-sum against the gathered target score; here the scan is
+ * npi_topk_links' -- tiles of 64 queries x 128 targets on the matrix cores, known edges masked on the chip -- and what is kept
+ * per query is four integer counts.
+ *
+ * RULE F -- the filtered counts of each query pair, from two f32 tables, Q query pairs (s_q, t_q), a set of excluded pairs and a
+ *           no-loops flag.
+ *   1. Score and key.  Rule K 1 and Rule K 3: score(i, j) is the ascending f32 fmaf chain the MFMA computes per element, its key
+ *              the ascending-orderable key of Rule R 1 (descending score, -0.0 equal to +0.0).  The target's own score
+ *              score(s_q, t_q) is computed on the matrix cores by the same chain.
+ *   2. Competitors of query q: every j in [0, n_dst) with j != t_q, (s_q, j) not in the exclusion set, j != s_q under
+ *              NPI_LINK_RANK_NO_LOOPS, and a non-NaN score.  The target itself is never a competitor and is always ranked, also
+ *              when (s_q, t_q) is in the exclusion set or is a loop: a known edge is ranked against the non-edges.
+ *   3. Counts. counts[q] = { greater, equal, equal_before, candidates } (int64): the competitors with key < key(t_q); those with
+ *              the same key; those of `equal` with j < t_q; all competitors.  scores[q] is the target's score rebuilt from its
+ *              key (-0.0 comes out as +0.0).
+ *   4. Consistency with Rule K.  greater + equal_before is the 0-based position t_q takes in npi_topk_links' list of s_q when the
+ *              pair itself is not excluded.
+ *   5. Bad input.  s_q outside [0, n_src) or t_q outside [0, n_dst): nothing is dereferenced, the row is -1, -1, -1, -1 with
+ *              score -inf, and NPI_STATUS_BAD_PAIR_ID is raised.  A NaN target score: the same row, NPI_STATUS_BAD_SCORE.  A NaN
+ *              competitor score raises NPI_STATUS_BAD_SCORE and is not counted (Rule K 2).
+ *   6. The output is independent of `splits`, of the order and repetition of the queries, and of the call, bitwise.
+ *
+ *   src, dst  : int64 [Q] each: the query pairs, in any order, repeats allowed
+ *   z_src, z_dst, ld_src, ld_dst, n_src, n_dst, F, ex_rowptr, ex_col, splits, status : as npi_topk_links takes them (16-byte loads
+ *               when F % 4 == 0 and both bases and pitches are 16-byte aligned, else guarded scalar loads: any F >= 1 and any
+ *               pitch >= F; the exclusion set a by-source CSR with columns ascending; splits 0: chosen as npi_topk_links chooses)
+ *   flags     : NPI_LINK_RANK_NO_LOOPS or 0
+ *   counts    : int64 [Q, 4];  scores : f32 [Q]
+ *   workspace : npi_link_ranks_workspace_bytes(Q, n_dst, splits) bytes, 16-byte aligned, caller-owned (four int32 partial counts
+ *               per query and split, one key per query)
+ * Nothing is allocated, nothing read back: the call may run inside a stream capture.  Integer counts: no float atomics, the only
+ * atomic is the status OR.  Refused with NPI_ERR_ARG before any launch: Q, n_src or n_dst outside [0, 2^31 - 1), F outside
+ * [1, 2^31 - 1), a leading dimension below F, an unknown flag, NPI_LINK_RANK_NO_LOOPS with n_src != n_dst, only one of ex_rowptr /
+ * ex_col, negative splits; with Q > 0 a null src, dst, counts, scores or workspace, a null table that has rows, a workspace
+ * misaligned or shorter than the query says.  Q == 0 returns NPI_OK without a launch.  npi_link_ranks_workspace_bytes returns -1
+ * for Q or n_dst outside [0, 2^31 - 1) or negative splits.
+ *
+ * Out of scope: the by-target direction (swap the tables and flip the lists), grouping queries by source to share rows, bf16
+ * tables, gradients, and sampled-negative ranking (that is npi_rank_metrics / GAE.test).
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_LINK_RANK_NO_LOOPS 1
+int64_t npi_link_ranks_workspace_bytes(int64_t Q, int64_t n_dst, int64_t splits);   /* -1: bad size */
+int npi_link_ranks(const int64_t* src, const int64_t* dst, int64_t Q,
+                   const float* z_src, int64_t ld_src, int64_t n_src,
+                   const float* z_dst, int64_t ld_dst, int64_t n_dst, int64_t F,
+                   const int32_t* ex_rowptr, const int32_t* ex_col /* by-source CSR, columns ascending; both NULL: none */,
+                   int flags /* NPI_LINK_RANK_NO_LOOPS 1 */, int64_t splits,
+                   int64_t* counts /* [Q, 4] */, float* scores /* [Q] */, void* workspace, int64_t workspace_bytes,
+                   int32_t* status, void* stream);
+
 /* Evaluation loop(reference src/methods.py:87-105 compares one element per Python
  * iteration, one device sync each).  counts[4] += [TP, FN, TN, FP] for pred = first arg-max of scores[i, 0..C):
  * pred 1 & y 1 -> TP, pred 1 & y 0 -> FP, pred 0 & y 1 -> FN, anything else -> TN (the reference's else

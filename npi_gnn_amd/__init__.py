@@ -20,9 +20,10 @@ from .walk import Node2Vec, RandomWalker, random_walk  # noqa: F401
 from .rank import average_precision_score, precision_recall_curve, rank_metrics, roc_auc_score, roc_curve  # noqa: F401
 from .split import EdgeSplitter, to_undirected, train_test_split_edges  # noqa: F401
 from .topk import KnownLinks, topk_links  # noqa: F401
+from .link_rank import LinkRanks, link_ranks, ranking_metrics  # noqa: F401
 
 __all__ = ["CSRGraph", "GraphBatch", "as_graph", "set_debug", "GCNNorm", "gat_conv", "gcn_conv", "sage_conv", "segsum",
            "GATConv", "GCNConv", "SAGEConv", "Schedule", "GraphedStack", "NeighborSampler", "DataFlow", "Block", "SubgraphBatch", "NegativeSampler", "negative_sampling",
            "structured_negative_sampling", "InnerProductDecoder", "GAE", "RandomWalker", "random_walk", "Node2Vec", "pair_scores", "link_loss", "rank_metrics",
            "roc_auc_score", "average_precision_score", "roc_curve", "precision_recall_curve", "EdgeSplitter",
-           "train_test_split_edges", "to_undirected", "KnownLinks", "topk_links", "NpiError", "load", "LIB_PATH"]
+           "train_test_split_edges", "to_undirected", "KnownLinks", "topk_links", "LinkRanks", "link_ranks", "ranking_metrics", "NpiError", "load", "LIB_PATH"]

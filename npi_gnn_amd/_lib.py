@@ -4,7 +4,8 @@ There is NO CPU fallback: every wrapper raises if the library is missing or if a
 on an AMD GPU.  PyTorch only lends device memory and the current HIP stream.  The link-prediction entry points in the
 order of a run: ``npi_split_*`` (train / val / test parts and folds of the edge list), ``npi_sample_*`` (batches), ``npi_negative_*`` (negatives), ``npi_random_walk`` / ``npi_walk_pairs`` (node2vec
 walks and their skip-gram pair list), ``npi_pair_score`` (scores and loss), ``npi_rank_metrics`` (ROC-AUC, average precision and
-the score curve of an evaluation), ``npi_topk_links`` (the k most likely new links of every query row).
+the score curve of an evaluation), ``npi_topk_links`` (the k most likely new links of every query row), ``npi_link_ranks`` (the
+filtered rank of every held-out link among the targets its source has no known edge to).
 """
 from __future__ import annotations
 
@@ -41,6 +42,7 @@ NPI_PAIR_LOSS_GAE = 1
 NPI_PAIR_LOSS_BCE = 2
 NPI_TOPK_MAX = 128               # largest k of npi_topk_links
 NPI_TOPK_NO_LOOPS = 1            # flag of npi_topk_links: one id space, (v, v) is no candidate
+NPI_LINK_RANK_NO_LOOPS = 1       # flag of npi_link_ranks: one id space, (v, v) is no competitor
 NPI_HUB_MAX = 128               # hubs per plan (npi_hub_plan; mask words of NPI_HUB_MAX / 32 per source row)
 
 
@@ -182,6 +184,8 @@ PROTOTYPES = {
     "npi_split_undirected": (c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "npi_topk_links_workspace_bytes": (_I, [_I, _I, _I, _I]),
     "npi_topk_links": (c_int, [_P, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, c_int, _I, _P, _P, _P, _I, _P, _P]),
+    "npi_link_ranks_workspace_bytes": (_I, [_I, _I, _I]),
+    "npi_link_ranks": (c_int, [_P, _P, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, c_int, _I, _P, _P, _P, _I, _P, _P]),
 }
 
 _lib = None

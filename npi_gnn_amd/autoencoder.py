@@ -6,12 +6,14 @@
     loss.backward()
     auc, ap = model.test(z, pos_edge_index, neg_edge_index)    # 0-d float64 device tensors: float(auc) is PyG's number
     prob, ids = model.predict(z, k, pos_edge_index)            # [R, k] each: the k most likely NEW links of every source row
+    m = model.test_ranking(z, test_edge_index, pos_edge_index)  # filtered MRR / mean rank / Hits@K of held-out links
 
 ``InnerProductDecoder.forward`` is ``functional.pair_scores`` (one launch over the pair list, no sort), ``GAE.recon_loss`` is
 ``functional.link_loss`` (one forward launch, no logits written; the backward is the layers' own aggregation: no float atomics,
 bitwise reproducible), ``GAE.test`` is ``rank.rank_metrics`` (ROC-AUC and average precision of the decoder's outputs: one device
 sort, no copy to the host).  ``InnerProductDecoder.forward_all`` -- the dense ``[N, N]`` product -- is not provided:
-``InnerProductDecoder.topk`` / ``GAE.predict`` (``topk.topk_links``) give each row's best ``k`` of it without the matrix.
+``InnerProductDecoder.topk`` / ``GAE.predict`` (``topk.topk_links``) give each row's best ``k`` of it without the matrix, and
+``InnerProductDecoder.ranks`` / ``GAE.test_ranking`` (``link_rank.link_ranks``) the rank of a held-out link within it.
 CPU tensors raise ``NpiError``: there is no CPU path.
 """
 from __future__ import annotations
@@ -24,6 +26,7 @@ from torch import nn
 from . import functional as F_
 from .negative import NegativeSampler
 from .rank import rank_metrics
+from .link_rank import link_ranks, ranking_metrics
 from .topk import topk_links
 
 
@@ -54,6 +57,12 @@ class InnerProductDecoder(nn.Module):
         ``torch.topk`` would give, without the ``[N, N]`` matrix."""
         value, ids = topk_links(z, k, exclude=exclude, rows=rows)
         return (torch.sigmoid(value) if sigmoid else value), ids
+
+    def ranks(self, z, edge_index: torch.Tensor, exclude=None):
+        """``link_rank.link_ranks(z, edge_index, exclude)``: for every pair of ``edge_index [2, Q]`` the counts of the targets that
+        ``exclude`` does not hold and that score above, or equal to, the pair's own target (a ``LinkRanks``; ``score`` holds the
+        logits) -- what ``forward_all``, a mask and a compare-and-sum would give, without the ``[N, N]`` matrix."""
+        return link_ranks(z, edge_index, exclude=exclude)
 
 
 class GAE(nn.Module):
@@ -114,3 +123,12 @@ class GAE(nn.Module):
         one = isinstance(z, torch.Tensor) or (isinstance(z, (tuple, list)) and len(z) == 2 and z[0] is z[1])
         value, ids = topk_links(z, k, exclude=known_edge_index, rows=rows, allow_loops=not one)
         return (torch.sigmoid(value) if sigmoid else value), ids
+
+    def test_ranking(self, z, pos_edge_index: torch.Tensor, known_edge_index, ks=(1, 3, 10), ties: str = "average"):
+        """The filtered ranking metrics of the held-out links ``pos_edge_index``: ``{"mrr", "mean_rank", "hits@k" ...}`` (0-d float64
+        device tensors) by ``link_rank.ranking_metrics`` -- every positive ranked against all targets its source has no edge to in
+        ``known_edge_index`` (the ``[2, E]`` LongTensor, or a ``KnownLinks`` of it built once), and never against ``(v, v)`` when
+        ``z`` is one id space, as in ``predict``.  Where ``test`` compares with sampled negatives, this says whether ``predict(z,
+        k, ...)`` shows the true partner within its ``k`` slots.  The inner product is scored whatever the decoder."""
+        one = isinstance(z, torch.Tensor) or (isinstance(z, (tuple, list)) and len(z) == 2 and z[0] is z[1])
+        return ranking_metrics(z, pos_edge_index, exclude=known_edge_index, ks=ks, ties=ties, allow_loops=not one)

@@ -2,47 +2,24 @@
 // not excluded -- what a user of PyG 1.4.2 gets from `InnerProductDecoder.forward_all` (a dense [N, N] product), a mask and
 // `torch.topk`, and the reference from its per-case loops on the host (src/case_study*.py) -- without the score matrix ever
 // leaving the chip.  Two kernels:
-//   topk_tiles_kernel  grid (blocks of 64 query rows) x (S column splits).  A workgroup walks its split's z_dst rows in tiles of
-//                      128, ascending.  Per tile: the 64 x 128 scores on v_mfma_f32_32x32x2_f32 (both operands K-contiguous, the
-//                      A . B^T form of gemm_f32.hip's edge kernel: [row][BK + 4] LDS images, double-buffered k-steps of 32, the
-//                      next tile's first k-step already in flight), the accumulators go to LDS as KEYS (rank_key.h), and every
-//                      wavefront takes 16 rows: it marks the row's excluded columns (a cursor into the row's sorted CSR segment,
-//                      placed by one binary search at the split's first column, moving forward only), compares the row's 128
-//                      keys with the row's current k-th best lane-parallel (__ballot) and inserts the survivors into the row's
-//                      sorted list of 128 (key << 32 | id) words -- two registers per lane while the row is being worked on, LDS
-//                      otherwise.  After the first tiles almost nothing survives.  At the end each (row, split) writes its k
-//                      best to the workspace.
+//   topk_tiles_kernel  grid (blocks of 64 query rows) x (S column splits).  The scan is score_tile.h's: per tile of 128 targets
+//                      the 64 x 128 scores on v_mfma_f32_32x32x2_f32 as KEYS (rank_key.h) in LDS, the excluded columns marked.
+//                      The consumer here is the SELECTION: every wavefront compares a row's 128 keys with the row's current k-th
+//                      best lane-parallel (__ballot) and inserts the survivors into the row's sorted list of 128 (key << 32 | id)
+//                      words -- two registers per lane while the row is being worked on, LDS otherwise.  After the first tiles
+//                      almost nothing survives.  At the end each (row, split) writes its k best to the workspace.
 //   topk_merge_kernel  one wavefront per query row: the S partial lists merged under the same order, scores (rebuilt from the
 //                      key) and ids written.
-// The k order of the products: the LDS image of a k-step stores column 8 g + e of a row at position 8 g + 4 (e & 1) + (e >> 1),
-// so that the 16-byte fragment of lane half h holds columns 8 g + h, 8 g + 2 + h, 8 g + 4 + h, 8 g + 6 + h and MFMA s of a group
-// multiplies columns 8 g + 2 s (half 0) and 8 g + 2 s + 1 (half 1): an ascending fmaf chain per output element, whatever tile,
-// split or position in the query list the pair falls into (columns past F are zeros in both operands: fmaf(0, 0, acc) = acc).
 // The (key, id) words are distinct within a row and totally ordered, so the k smallest of a row do not depend on the order in
 // which they are met: no float atomics, no atomics at all but the status OR.  LDS: 2 x 27 KiB staging + 34 KiB keys + 64 KiB
-// lists + 1 KiB row state = 153 KiB, one workgroup per CU.
-#include "dot_lanes.h"
+// lists + 1.25 KiB row state = 153 KiB, one workgroup per CU.
 #include "rank_key.h"
+#include "score_tile.h"
 
 namespace npi {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int TK_THREADS = 256;
-constexpr int TK_BM = 64;                                // query rows per workgroup: 2 x 2 wavefronts of 32 rows x 64 columns
-constexpr int TK_BN = 128;                               // target rows per tile
-constexpr int TK_BK = 32;
-constexpr int TK_KPITCH = TK_BK + 4;                     // [row][k] image, fragment reads free of bank conflicts (gemm_f32.hip)
-constexpr int TK_AF = TK_BM * TK_KPITCH, TK_BF = TK_BN * TK_KPITCH;
-constexpr int TK_SPITCH = TK_BN + 8;                     // key tile: rows r and r + 4 of one accumulator store 32 banks apart
 constexpr int TK_LIST = NPI_TOPK_MAX;                    // list positions kept per row (the first k are the answer)
-constexpr int TK_ROWS_PER_WAVE = TK_BM / (TK_THREADS / WAVE);
-constexpr int TK_MAX_SPLITS = 64;
-constexpr int TK_TARGET_WORKGROUPS = 512;                // two per CU of an MI355X: what the default split count aims at
 static_assert(TK_LIST == 2 * WAVE, "a row's list is two words per lane");
-
-// keys no score has (both are bit patterns of negative NaNs under rank_key): not a candidate / a NaN score
-constexpr uint32_t TK_KEY_OUT = 0xffffffffu, TK_KEY_NAN = 0xfffffffeu, TK_KEY_LAST = 0xff800000u /* -inf */;
 constexpr uint64_t TK_EMPTY = ~(uint64_t)0;              // key TK_KEY_OUT, id -1: an unused list slot
 
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
@@ -88,20 +65,29 @@ struct TopList {
     }
 };
 
-// four columns k .. k + 3 of a table row (zeros past F); VEC: one 16-byte load (F % 4 == 0, aligned rows)
-template <bool VEC>
-__device__ __forceinline__ float4 load_k4(const float* __restrict__ row, int k, int F) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (VEC) {
-        if (k < F) v = *reinterpret_cast<const float4*>(row + k);
-    } else {
-        if (k + 0 < F) v.x = row[k + 0];
-        if (k + 1 < F) v.y = row[k + 1];
-        if (k + 2 < F) v.z = row[k + 2];
-        if (k + 3 < F) v.w = row[k + 3];
+// the selection consumer of score_tile.h's scan: a row's candidates of one tile offered to the row's list
+struct TopkSelect {
+    static constexpr bool UNROLL_ROWS = false;
+    uint64_t* __restrict__ lists;
+    int k, bad_score;
+    __device__ __forceinline__ void row(int, int r, const uint32_t* krow, int c0, int, int lane) {
+        TopList L;
+        L.a0 = lists[r * TK_LIST + lane];
+        L.a1 = lists[r * TK_LIST + WAVE + lane];
+        bool changed = false;
+#pragma unroll
+        for (int h = 0; h < TK_BN / WAVE; ++h) {
+            const uint32_t key = krow[h * WAVE + lane];
+            bad_score |= key == TK_KEY_NAN ? 1 : 0;
+            const uint64_t x = ((uint64_t)key << 32) | ((uint32_t)c0 + (uint32_t)(h * WAVE + lane));
+            changed |= L.offer(x, key <= TK_KEY_LAST, k, lane);
+        }
+        if (changed) {
+            lists[r * TK_LIST + lane] = L.a0;
+            lists[r * TK_LIST + WAVE + lane] = L.a1;
+        }
     }
-    return v;
-}
+};
 
 template <bool VEC>
 __global__ void __launch_bounds__(TK_THREADS, 1)
@@ -109,180 +95,19 @@ topk_tiles_kernel(const int64_t* __restrict__ rows, int R, const float* __restri
                   const float* __restrict__ zd, int64_t ldd, int n_dst, int F, int k, const int32_t* __restrict__ ex_rowptr,
                   const int32_t* __restrict__ ex_col, int no_loops, int tiles_per_split, uint64_t* __restrict__ ws,
                   int32_t* __restrict__ status) {
-    __shared__ __attribute__((aligned(16))) float stage[2][TK_AF + TK_BF];
-    __shared__ uint32_t keys[TK_BM * TK_SPITCH];
+    __shared__ ScoreTileShared sh;
     __shared__ uint64_t lists[TK_BM * TK_LIST];
-    __shared__ int qid[TK_BM], ex_cur[TK_BM], ex_end[TK_BM], ex_next[TK_BM];
 
     const int t = threadIdx.x;
     const int lane = t & 63, wave = uniform_i(t >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int li = lane & 31, lh = lane >> 5;
     const int64_t m0 = (int64_t)blockIdx.x * TK_BM;
     const int S = gridDim.y, split = blockIdx.y;
-    const int n_tiles = (int)(((int64_t)n_dst + TK_BN - 1) / TK_BN);
-    const int tile_beg = min((int)min((int64_t)split * tiles_per_split, (int64_t)n_tiles), n_tiles);
-    const int tile_end = (int)min((int64_t)tile_beg + tiles_per_split, (int64_t)n_tiles);
-    const int nk = (F + TK_BK - 1) / TK_BK;
 
-    // ---- the rows of this workgroup: ids, exclusion cursors at the split's first column, empty lists
     for (int i = t; i < TK_BM * TK_LIST; i += TK_THREADS) lists[i] = TK_EMPTY;
-    if (t < TK_BM) {
-        const int64_t r = m0 + t;
-        int q = -1, cur = 0, end = 0, next = 0x7fffffff;
-        if (r < R) {
-            const int64_t id = rows != nullptr ? rows[r] : r;
-            if ((uint64_t)id < (uint64_t)n_src) q = (int)id;
-            else if (status != nullptr && split == 0) atomicOr(status, NPI_STATUS_BAD_SOURCE_ID);
-        }
-        if (q >= 0 && ex_rowptr != nullptr) {
-            const int cbeg = (int)min((int64_t)tile_beg * TK_BN, (int64_t)n_dst);
-            int lo = ex_rowptr[q];
-            end = ex_rowptr[q + 1];
-            int hi = end;
-            while (lo < hi) {                                                     // first entry with column >= cbeg
-                const int mid = lo + ((hi - lo) >> 1);
-                if (ex_col[mid] < cbeg) lo = mid + 1; else hi = mid;
-            }
-            cur = lo;
-            if (cur < end) next = ex_col[cur];
-        }
-        qid[t] = q;
-        ex_cur[t] = cur;
-        ex_end[t] = end;
-        ex_next[t] = next;
-    }
-    __syncthreads();
-
-    // ---- staging: thread t moves float4 #(t & 7) of rows (t >> 3) + 32 p: two of the query tile, four of the target tile
-    const int srow = t >> 3, sk = (t & 7) * 4;
-    const int soff = ((t & 7) >> 1) * 8 + (t & 1) * 2;                            // the permuted image (file header)
-    const int qa0 = qid[srow], qa1 = qid[srow + 32];
-    const float* __restrict__ pa0 = zs + (int64_t)max(qa0, 0) * lds_;
-    const float* __restrict__ pa1 = zs + (int64_t)max(qa1, 0) * lds_;
-    float4 ra0, ra1, rb0, rb1, rb2, rb3;
-    auto gload = [&](int tile, int kt) {
-        const int kk = kt * TK_BK + sk;
-        const int64_t j0 = (int64_t)tile * TK_BN + srow;
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        ra0 = qa0 >= 0 ? load_k4<VEC>(pa0, kk, F) : z;
-        ra1 = qa1 >= 0 ? load_k4<VEC>(pa1, kk, F) : z;
-        rb0 = j0 + 0 < n_dst ? load_k4<VEC>(zd + (j0 + 0) * ldd, kk, F) : z;
-        rb1 = j0 + 32 < n_dst ? load_k4<VEC>(zd + (j0 + 32) * ldd, kk, F) : z;
-        rb2 = j0 + 64 < n_dst ? load_k4<VEC>(zd + (j0 + 64) * ldd, kk, F) : z;
-        rb3 = j0 + 96 < n_dst ? load_k4<VEC>(zd + (j0 + 96) * ldd, kk, F) : z;
-    };
-    auto put = [&](float* img, int row, const float4& v) {
-        float* d = img + row * TK_KPITCH + soff;
-        *reinterpret_cast<float2*>(d) = make_float2(v.x, v.z);
-        *reinterpret_cast<float2*>(d + 4) = make_float2(v.y, v.w);
-    };
-    auto lstore = [&](int buf) {
-        put(stage[buf], srow, ra0);
-        put(stage[buf], srow + 32, ra1);
-        put(stage[buf] + TK_AF, srow, rb0);
-        put(stage[buf] + TK_AF, srow + 32, rb1);
-        put(stage[buf] + TK_AF, srow + 64, rb2);
-        put(stage[buf] + TK_AF, srow + 96, rb3);
-    };
-
-    int buf = 0;
-    if (tile_beg < tile_end) {
-        gload(tile_beg, 0);
-        lstore(0);
-    }
-    __syncthreads();
-    int bad_score = 0;
-    for (int tile = tile_beg; tile < tile_end; ++tile) {
-        f32x16 acc[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[j][q] = 0.f;
-        for (int kt = 0; kt < nk; ++kt) {
-            const bool last = kt + 1 == nk;
-            const bool more = !last || tile + 1 < tile_end;
-            if (more) gload(last ? tile + 1 : tile, last ? 0 : kt + 1);
-            const float* as = stage[buf] + (wm * 32 + li) * TK_KPITCH + lh * 4;
-            const float* bs = stage[buf] + TK_AF + (wn * 64 + li) * TK_KPITCH + lh * 4;
-#pragma unroll
-            for (int g = 0; g < TK_BK / 8; ++g) {
-                const float4 a = *reinterpret_cast<const float4*>(as + g * 8);
-                const float4 b0 = *reinterpret_cast<const float4*>(bs + g * 8);
-                const float4 b1 = *reinterpret_cast<const float4*>(bs + 32 * TK_KPITCH + g * 8);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b0.x, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b1.x, acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b0.y, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b1.y, acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b0.z, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b1.z, acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b0.w, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b1.w, acc[1], 0, 0, 0);
-            }
-            if (more) lstore(buf ^ 1);
-            __syncthreads();
-            buf ^= 1;
-        }
-
-        // ---- the tile's scores as keys: C/D map of the 32x32 MFMA, col = lane & 31, row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5)
-        const int c0 = tile * TK_BN;                                              // < n_dst
-        const int cn = (int)min((int64_t)TK_BN, (int64_t)n_dst - c0);             // columns of this tile that exist
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = wn * 64 + j * 32 + li;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int row = wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh;
-                const float v = acc[j][q];
-                const uint32_t key = col < cn ? (v != v ? TK_KEY_NAN : rank_key(__float_as_uint(v))) : TK_KEY_OUT;
-                keys[row * TK_SPITCH + col] = key;
-            }
-        }
-        __syncthreads();
-
-        // ---- every wavefront its 16 rows: exclusions, then the filter against the row's k-th best
-        for (int rr = 0; rr < TK_ROWS_PER_WAVE; ++rr) {
-            const int r = wave * TK_ROWS_PER_WAVE + rr;
-            const int q = uniform_i(qid[r]);
-            if (q < 0) continue;                                                  // a bad id, or past R: nothing is selected
-            uint32_t* __restrict__ krow = keys + r * TK_SPITCH;
-            if (uniform_i(ex_next[r]) - c0 < cn) {                                // (sorted columns: ex_next >= c0)
-                int cur = uniform_i(ex_cur[r]);
-                const int end = uniform_i(ex_end[r]);
-                for (;;) {
-                    const int idx = cur + lane;
-                    const int col = idx < end ? ex_col[idx] - c0 : 0x7fffffff;
-                    const bool in = col < cn;
-                    if (in && col >= 0) krow[col] = TK_KEY_OUT;
-                    const int n = __popcll(__ballot(in));                         // a prefix of the lanes
-                    cur += n;
-                    if (n < WAVE) break;
-                }
-                if (lane == 0) {
-                    ex_cur[r] = cur;
-                    ex_next[r] = cur < end ? ex_col[cur] : 0x7fffffff;
-                }
-            }
-            if (no_loops && lane == 0 && q - c0 >= 0 && q - c0 < cn) krow[q - c0] = TK_KEY_OUT;
-            TopList L;
-            L.a0 = lists[r * TK_LIST + lane];
-            L.a1 = lists[r * TK_LIST + WAVE + lane];
-            bool changed = false;
-#pragma unroll
-            for (int h = 0; h < TK_BN / WAVE; ++h) {
-                const uint32_t key = krow[h * WAVE + lane];
-                bad_score |= key == TK_KEY_NAN ? 1 : 0;
-                const uint64_t x = ((uint64_t)key << 32) | ((uint32_t)c0 + (uint32_t)(h * WAVE + lane));
-                changed |= L.offer(x, key <= TK_KEY_LAST, k, lane);
-            }
-            if (changed) {
-                lists[r * TK_LIST + lane] = L.a0;
-                lists[r * TK_LIST + WAVE + lane] = L.a1;
-            }
-        }
-        // (the next write of `keys` comes after the barriers of the next tile's k-steps: nk >= 1)
-    }
-    if (status != nullptr && __any(bad_score) && lane == 0) atomicOr(status, NPI_STATUS_BAD_SCORE);
+    const ScoreTileArgs args{rows, nullptr, R, zs, lds_, n_src, zd, ldd, n_dst, F, ex_rowptr, ex_col, no_loops, tiles_per_split, status};
+    TopkSelect select{lists, k, 0};
+    score_tiles<VEC, false>(args, sh, select);
+    if (status != nullptr && __any(select.bad_score) && lane == 0) atomicOr(status, NPI_STATUS_BAD_SCORE);
 
     // ---- the partial lists: ws[(row * S + split) * k + p]
     for (int rr = 0; rr < TK_ROWS_PER_WAVE; ++rr) {
@@ -324,15 +149,6 @@ topk_merge_kernel(const uint64_t* __restrict__ ws, int R, int S, int k, float* _
         }
     }
 }
-
-static int64_t topk_tiles(int64_t n_dst) { return ceil_div(n_dst, TK_BN); }
-// S: the caller's, or enough splits for TK_TARGET_WORKGROUPS workgroups; never more than there are tiles, or than TK_MAX_SPLITS
-static int64_t topk_splits(int64_t R, int64_t n_dst, int64_t splits) {
-    int64_t s = splits > 0 ? splits : ceil_div(TK_TARGET_WORKGROUPS, max(ceil_div(R, TK_BM), (int64_t)1));
-    s = min(s, min(topk_tiles(n_dst), (int64_t)TK_MAX_SPLITS));
-    return max(s, (int64_t)1);
-}
-
 }  // namespace npi
 
 using namespace npi;
