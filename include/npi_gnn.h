@@ -585,6 +585,61 @@ int npi_gat_att_grad(const float* hfeat, int64_t ldh, const float* g_dst, const 
                      int64_t workspace_elems, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GATConv with ATTENTION DROPOUT inside the fused launches (PyG 1.4.2 GATConv.message: alpha = F.dropout(softmax(alpha), p)).
+ * The launches recompute alpha per entry in both orientations; they recompute the dropout decision the same way, as a pure
+ * function of (key, edge, head) keyed on the entry's eid, which the by-target and the by-source CSR both carry -- no [nnz, H]
+ * mask, no alpha array, and a step is reproducible from (seed, draw).
+ *
+ * Rule D (the mask; the counter-based generator of the other rules, npi_gnn_amd/csrc/draw.h; wrapping uint64 throughout):
+ *     key    = epoch_seed(seed, draw)                       as every other rule (npi_sample_select's description)
+ *     root   = mix64(mix64(key) + 6 G)                      draw_root(key, DRAW_RULE_D), G = 0x9E3779B97F4A7C15
+ *     k      = eid                    an entry that is column eid of edge_index (0 <= eid < 2^31)
+ *            = 2^32 + i               the self loop the CSR build appends at node i (eid < 0; rowidx == col == i on both sides)
+ *     word_h = mix64(mix64(root ^ (k C)) + G (h + 1))       draw_word(draw_stream(root, k), h + 1), C = 0xD6E8FEB86659FD93, h = 0 .. H-1
+ *     T      = floor(p 2^64)          p taken as the double it is; exact integers on the host: int(Fraction(p) * 2**64)
+ *     dropped(k, h)  <=>  word_h < T ;   kappa(k, h) = 0 if dropped else float32(1 / (1 - p))
+ * The calls take key (int64), T = `threshold` and kappa's kept value `scale` (float), never p: the host alone rounds.  T is an
+ * unsigned 64-bit number; like `key` it travels as the int64_t with the same 64 bits (T - 2^64 from 2^63 on).
+ * In numpy (uint64 arrays wrap):
+ *     def mix64(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)
+ *     root = mix64(mix64(uint64(key)) + 6 * G);  k = where(eid >= 0, eid, 2**32 + col).astype(uint64)
+ *     keep[:, h] = where(mix64(mix64(root ^ (k * C)) + G * (h + 1)) < T, 0, float32(1 / (1 - p)))
+ * Known answers (seed 0, draw 0): root = 0x6f163edb947c9e05, T(0.6) = 11068046444225730560; k = 0: words 0x16487dc5ae5a7950,
+ * 0x36d77e7754a4d63d (heads 0, 1: both dropped at p = 0.6); k = 1: 0xedeff920902a8ec7, 0xb36d8fb43721e4f1 (both kept).
+ *
+ * The arithmetic of the layer changes in three places (m, s stay the statistics of the UNDROPPED scores, D_i = <dOut_i, out_i - b>
+ * is the unchanged npi_gat_rowdot_colsum_relu):
+ *     out_i = sum_p alpha_p kappa_p h_j + b;   dz_p = alpha_p (kappa_p <dOut_i, h_j> - D_i) leaky_relu'(z_p);
+ *     dh_j  = sum_i alpha_ij kappa_ij dOut_i  (+ the rank-1 terms from dz)
+ * Every call below is its sibling -- same arguments, same contract, the same NPI_ERR_ARG refusals before any launch -- followed by
+ *     eid [nnz_max]: the eid array of the CSR side that is walked (NULL: NPI_ERR_ARG), key, threshold, scale.
+ * Dropped entries are still gathered.  npi_gat_dropout_keep writes kappa itself, keep [nnz_max, H] f32 in the side's entry order
+ * (0 behind the last entry): the same mask for a layer composed from the per-op calls, and for tests.
+ * ------------------------------------------------------------------------------------------ */
+int npi_gat_aggregate_fused_heads_dropout(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* item_row,
+                                          int64_t item_edges, int64_t N, int64_t nnz_max, const float* x, int64_t ldx, const float* x2,
+                                          int64_t split, float* out, int64_t ldo, int64_t H, int64_t C, const float* a_dst,
+                                          const float* att, float negative_slope, const float* bias, int relu, float* m, float* s,
+                                          float* carry, float* row_scales_out, void* stream,
+                                          const int32_t* eid, int64_t key, int64_t threshold, float scale);
+int npi_gat_backward_fused_heads_dropout(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
+                                         const int32_t* item_row, int64_t item_edges, int64_t N, int64_t nnz_max,
+                                         const float* dout, int64_t ldd, const float* dout2, int64_t split, const float* hfeat,
+                                         int64_t ldh, float* out, int64_t ldo, int64_t H, int64_t C, const float* tpack,
+                                         const float* a_src, float slope, float* dz, float* carry, float* row_scales_out,
+                                         float* g_src_out, float* workspace, int64_t workspace_elems, void* stream,
+                                         const int32_t* eid, int64_t key, int64_t threshold, float scale);
+int npi_gat_edge_grad_dropout(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
+                              int64_t N, int64_t nnz_max, const float* hfeat, int64_t ldh,
+                              const float* hfeat2, int64_t split,
+                              const float* dout, int64_t ldd, int64_t H, int64_t C,
+                              const float* a_dst, const float* a_src, const float* m, const float* s,
+                              const float* D, float negative_slope, int swap, float* dz, float* alpha_out, void* stream,
+                              const int32_t* eid, int64_t key, int64_t threshold, float scale);
+int npi_gat_dropout_keep(const int32_t* rowptr, const int32_t* col, const int32_t* eid, int64_t N, int64_t nnz_max, int64_t H,
+                         int64_t key, int64_t threshold, float scale, float* keep, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Between-layer steps of Net_1 (reference src/classes.py:63-64,67-68,71-72),
  * forward only: PyG 1.4.2 TopKPooling(ratio) and the [global_max_pool || global_mean_pool] readout.
  * `batch` is the PyG Batch vector (int64, non-decreasing); graph_ptr[B+1] its segment starts.

@@ -112,6 +112,14 @@ PROTOTYPES = {
                                             _P]),
     "npi_gat_aggregate_fused_heads": (c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, c_float, _P, c_int, _P, _P,
                                                _P, _P, _P]),
+    # the three launches with attention dropout under Rule D: the sibling's arguments, then eid, key, threshold (the uint64's bits), scale
+    "npi_gat_aggregate_fused_heads_dropout": (c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, c_float, _P, c_int,
+                                                       _P, _P, _P, _P, _P, _P, _I, _I, c_float]),
+    "npi_gat_backward_fused_heads_dropout": (c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, c_float, _P,
+                                                      _P, _P, _P, _P, _I, _P, _P, _I, _I, c_float]),
+    "npi_gat_edge_grad_dropout": (c_int, [_P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, c_float,
+                                          c_int, _P, _P, _P, _P, _I, _I, c_float]),
+    "npi_gat_dropout_keep": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, c_float, _P, _P]),
     "npi_gat_scores": (c_int, [_P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "npi_gat_aggregate_ex": (c_int, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, c_float, c_int,
                                      _P, _P, _P, _P, _P, _P, _P, _P]),

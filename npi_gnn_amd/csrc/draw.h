@@ -20,6 +20,7 @@ enum DrawRule : uint64_t {
     DRAW_RULE_W = 3,                                       // Rule W: walks, per walk                 (npi_random_walk)
     DRAW_RULE_W_NEG = 4,                                   // Rule W's negatives of the pair list     (npi_walk_pairs)
     DRAW_RULE_S = 5,                                       // Rule S: the order of a split            (npi_split_permute)
+    DRAW_RULE_D = 6,                                       // Rule D: the attention-dropout mask      (npi_gat_*_dropout)
 };
 
 __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
@@ -32,6 +33,27 @@ __host__ __device__ __forceinline__ uint64_t draw_stream(uint64_t root, uint64_t
 inline uint64_t draw_root(int64_t key, DrawRule rule) { return mix64(mix64((uint64_t)key) + (uint64_t)rule * DRAW_G); }
 // (n is an id bound or a row length, below 2^31 - 1 at every caller: the result fits 32 bits, signed or not)
 __device__ __forceinline__ uint32_t draw_below(uint64_t word, uint64_t n) { return (uint32_t)__umul64hi(word, n); }
+
+// Rule D, the attention-dropout mask of GATConv: a pure function of (key, edge, head), the same on the by-target and the by-source
+// side because both carry the entry's eid.  root = draw_root(key, DRAW_RULE_D); the slot of an entry is its eid (a column of
+// edge_index, 0 <= eid < 2^31) or, for the self loop the CSR build appends at node i (eid < 0, rowidx == col == i), 2^32 + i;
+// head h of slot k is DROPPED iff draw_word(draw_stream(root, k), h + 1) < threshold, threshold = floor(p 2^64) (the host rounds);
+// a kept weight is scaled by float32(1 / (1 - p)).
+__host__ __device__ __forceinline__ uint64_t drop_slot(int32_t eid, int32_t col) {
+    return eid >= 0 ? (uint64_t)(uint32_t)eid : (1ull << 32) + (uint64_t)(uint32_t)col;
+}
+__host__ __device__ __forceinline__ bool drop_kept(uint64_t stream, int h, uint64_t threshold) {
+    return draw_word(stream, (uint64_t)h + 1) >= threshold;
+}
+// bit h of the result: head h of the entry is kept (NH <= 32 heads)
+template <int NH>
+__host__ __device__ __forceinline__ int drop_keep_bits(uint64_t root, uint64_t threshold, int32_t eid, int32_t col) {
+    const uint64_t stream = draw_stream(root, drop_slot(eid, col));
+    int bits = 0;
+#pragma unroll
+    for (int h = 0; h < NH; ++h) bits |= drop_kept(stream, h, threshold) ? (1 << h) : 0;
+    return bits;
+}
 
 // is x a column of row `row`?  Rows ascend; empty rows, rows of one entry and rows with repeated columns all occur.
 __device__ __forceinline__ bool row_has(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int32_t row, int32_t x) {

@@ -10,6 +10,7 @@
 // fused backward does not cover), the attention-gradient reductions and the entry points of the weighted aggregations, which
 // are segsum.hip's kernel in its W_GAT_* modes; the per-row statistics and row sums live in segscan.hip.
 #include "segsum.h"
+#include "draw.h"
 
 namespace npi {
 
@@ -283,7 +284,9 @@ static bool rows16(const void* p, int64_t ld, int64_t C) { return C % 4 == 0 && 
 //   dalpha_p = <dout_i[h], hfeat_j[h]>;  de_p = alpha_p (dalpha_p - D_i);  dz_p = de_p * lrelu'(z_p)
 // one wave per 256-entry item; dout_i is reloaded when the row changes, hfeat_j gathered per entry
 constexpr int EDGE_HMAX = 8;        // heads whose per-entry dots are staged through LDS
-template <int NCH>
+// DROP (npi_gat_edge_grad_dropout): attention dropout under Rule D (draw.h) -- dz_p = alpha_p (kappa_p dalpha_p - D_i) lrelu'(z_p),
+// kappa recomputed from the entry's eid by the lane that turns the entry's dot into dz; the same factor in both `swap` orientations
+template <int NCH, bool DROP = false>
 __global__ void __launch_bounds__(256)
 gat_edge_grad_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                      const int32_t* __restrict__ rowidx, int N, int n_items, int item_edges,
@@ -291,7 +294,8 @@ gat_edge_grad_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restri
                      int H, int C, const float* __restrict__ a_dst, const float* __restrict__ a_src,
                      const float* __restrict__ m, const float* __restrict__ s, const float* __restrict__ D,
                      float slope, float* __restrict__ dz, float* __restrict__ alpha_out,
-                     const float* __restrict__ hfeat2, int split, int swap) {
+                     const float* __restrict__ hfeat2, int split, int swap,
+                     const int32_t* __restrict__ eid = nullptr, uint64_t drop_root = 0, uint64_t drop_threshold = 0, float drop_scale = 1.f) {
     // swap == 0: rows are TARGETS (dout rows, a_dst / m / s / D by row), columns SOURCES (hfeat gathered, a_src by column).
     // swap != 0: the same edges seen from a by-source CSR -- rows are sources (`dout` holds their hfeat rows, a_src by
     //            row), columns targets (`hfeat` holds the gathered dOut rows; a_dst / m / s / D by column).
@@ -325,6 +329,9 @@ gat_edge_grad_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restri
         const int nb = min(WAVE, k1 - kb);
         const int cv = (lane < nb) ? col[kb + lane] : 0;
         const int rv = (lane < nb) ? rowidx[kb + lane] : 0;
+        int ev = 0;
+        if constexpr (DROP) ev = (lane < nb) ? eid[kb + lane] : 0;
+        (void)ev;
         if (NCH == 1 && H == 1) {
             // One head, one chunk: 8 entries at a time.  Each lane has the partial dot product of its 4 columns for
             // each of the 8 entries; instead of 8 full wave reductions (6 cross-lane steps each) the 8 values are
@@ -401,7 +408,10 @@ gat_edge_grad_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restri
                         const int64_t ii = (int64_t)(swap ? cu : i) * H + h;
                         const float z = a_dst[ii] + a_src[(int64_t)(swap ? i : cu) * H + h];
                         const float alpha = expf(lrelu(z, slope) - m[ii]) / (s[ii] + 1e-16f);
-                        const float de = alpha * (p - D[ii]);
+                        float pk = p;
+                        if constexpr (DROP)
+                            pk *= drop_kept(draw_stream(drop_root, drop_slot(bcast_i(ev, j + u), cu)), h, drop_threshold) ? drop_scale : 0.f;
+                        const float de = alpha * (pk - D[ii]);
                         dz[(int64_t)(kb + j + u) * H + h] = de * (z > 0.f ? 1.f : slope);
                         if (alpha_out) alpha_out[(int64_t)(kb + j + u) * H + h] = alpha;
                     }
@@ -414,11 +424,16 @@ gat_edge_grad_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restri
                 const int t = t0 + lane;
                 const int en = min(t / H, nb - 1), h = t - (t / H) * H;
                 const int i = __shfl(rv, en, WAVE), cu = __shfl(cv, en, WAVE);
+                int ee = 0;
+                if constexpr (DROP) ee = __shfl(ev, en, WAVE);
+                (void)ee;
                 if (t >= nb * H) continue;
                 const int64_t ii = (int64_t)(swap ? cu : i) * H + h;
                 const float z = a_dst[ii] + a_src[(int64_t)(swap ? i : cu) * H + h];
                 const float alpha = expf(lrelu(z, slope) - m[ii]) / (s[ii] + 1e-16f);
-                const float de = alpha * (pb[t] - D[ii]);
+                float pk = pb[t];
+                if constexpr (DROP) pk *= drop_kept(draw_stream(drop_root, drop_slot(ee, cu)), h, drop_threshold) ? drop_scale : 0.f;
+                const float de = alpha * (pk - D[ii]);
                 dz[(int64_t)kb * H + t] = de * (z > 0.f ? 1.f : slope);
                 if (alpha_out) alpha_out[(int64_t)kb * H + t] = alpha;
             }
@@ -567,6 +582,25 @@ gat_rank1_add_kernel(float* __restrict__ dh, int64_t ld, const float* __restrict
     *reinterpret_cast<float4*>(dh + i * ld + f) = v;
 }
 
+// keep[p, h] = kappa of entry p and head h under Rule D (0 or `scale`), in the side's entry order; 0 behind the last entry
+__global__ void __launch_bounds__(256)
+gat_dropout_keep_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const int32_t* __restrict__ eid, int N,
+                        int64_t nnz_max, int H, uint64_t root, uint64_t threshold, float scale, float* __restrict__ keep) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= nnz_max) return;
+    const bool live = p < rowptr[N];
+    const uint64_t stream = live ? draw_stream(root, drop_slot(eid[p], col[p])) : 0;
+    for (int h = 0; h < H; ++h) keep[p * H + h] = (live && drop_kept(stream, h, threshold)) ? scale : 0.f;
+}
+
+// the arguments of Rule D as the C ABI takes them (null: no dropout)
+struct DropArgs {
+    const int32_t* eid;
+    int64_t key;
+    uint64_t threshold;
+    float scale;
+};
+
 }  // namespace npi
 
 using namespace npi;
@@ -588,12 +622,28 @@ extern "C" int npi_gat_pack_targets(const float* a_dst, const float* m, const fl
     return check_launch("npi_gat_pack_targets");
 }
 
-extern "C" int npi_gat_backward_fused_heads(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
-                                                const int32_t* item_row, int64_t item_edges, int64_t N, int64_t nnz_max,
-                                                const float* dout, int64_t ldd, const float* dout2, int64_t split, const float* hfeat,
-                                                int64_t ldh, float* out, int64_t ldo, int64_t H, int64_t C, const float* tpack,
-                                                const float* a_src, float slope, float* dz, float* carry, float* row_scales_out,
-                                                float* g_src_out, float* workspace, int64_t workspace_elems, void* stream_) {
+// Rule D into the parameter block of a fused launch; false (error set): a null eid
+static bool set_drop(SegParams& P, const DropArgs* drop, const char* who) {
+    if (drop == nullptr) return true;
+    if (drop->eid == nullptr) {
+        set_error("%s: null eid (attention dropout is keyed on the entries' edge ids)", who);
+        return false;
+    }
+    P.eid = drop->eid;
+    P.drop_root = draw_root(drop->key, DRAW_RULE_D);
+    P.drop_threshold = drop->threshold;
+    P.drop_scale = drop->scale;
+    return true;
+}
+
+// the body of npi_gat_backward_fused_heads and npi_gat_backward_fused_heads_dropout (drop: null = the plain layer)
+static int gat_backward_fused_heads_run(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
+                                        const int32_t* item_row, int64_t item_edges, int64_t N, int64_t nnz_max,
+                                        const float* dout, int64_t ldd, const float* dout2, int64_t split, const float* hfeat,
+                                        int64_t ldh, float* out, int64_t ldo, int64_t H, int64_t C, const float* tpack,
+                                        const float* a_src, float slope, float* dz, float* carry, float* row_scales_out,
+                                        float* g_src_out, float* workspace, int64_t workspace_elems, const DropArgs* drop,
+                                        void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const int64_t F = H * C;
     NPI_REQUIRE(row_scales_out == nullptr || (F == 256 && ldd % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)dout % 16) == 0 &&
@@ -620,7 +670,9 @@ extern "C" int npi_gat_backward_fused_heads(const int32_t* rowptr, const int32_t
     P.tpack = reinterpret_cast<const float4*>(tpack);                          // [n_cols, H, 4], indexed by the COLUMN id over both parts
     P.hrow = hfeat; P.ldh = ldh; P.rowidx = rowidx; P.dz_out = dz;            // dz: [nnz_max, H]
     P.scale_out = row_scales_out;
-    const int mode = H == 1 ? W_GAT_SRC_FUSED : H == 2 ? W_GAT_SRC_FUSED_H2 : H == 4 ? W_GAT_SRC_FUSED_H4 : W_GAT_SRC_FUSED_H8;
+    if (!set_drop(P, drop, "npi_gat_backward_fused_heads")) return NPI_ERR_ARG;
+    const int mode = (H == 1 ? W_GAT_SRC_FUSED : H == 2 ? W_GAT_SRC_FUSED_H2 : H == 4 ? W_GAT_SRC_FUSED_H4 : W_GAT_SRC_FUSED_H8) |
+                     (drop ? W_DROP : 0);
     // g_src_out [N] (one head): the row sums of dz from the same launch -- the lanes that compute dz scan it by row; rows cut by an
     // item boundary are added up by the chain kernel of segscan.hip behind it (workspace: npi_seg_scan_workspace_elems(nnz_max, 1))
     const int64_t n_items = num_items_of(nnz_max, (int)item_edges);
@@ -637,6 +689,32 @@ extern "C" int npi_gat_backward_fused_heads(const int32_t* rowptr, const int32_t
     const int rc = segsum_run(P, mode, 0, nnz_max, NPI_F32, stream);
     if (rc != NPI_OK || g_src_out == nullptr) return rc;
     return seg_chain_sum(rowptr, P.rs_head, P.rs_tail, P.rs_tail_row, g_src_out, N, n_items, (int)item_edges, stream);
+}
+
+extern "C" int npi_gat_backward_fused_heads(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
+                                                const int32_t* item_row, int64_t item_edges, int64_t N, int64_t nnz_max,
+                                                const float* dout, int64_t ldd, const float* dout2, int64_t split, const float* hfeat,
+                                                int64_t ldh, float* out, int64_t ldo, int64_t H, int64_t C, const float* tpack,
+                                                const float* a_src, float slope, float* dz, float* carry, float* row_scales_out,
+                                                float* g_src_out, float* workspace, int64_t workspace_elems, void* stream_) {
+    return gat_backward_fused_heads_run(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, dout, ldd, dout2, split, hfeat, ldh, out,
+                                        ldo, H, C, tpack, a_src, slope, dz, carry, row_scales_out, g_src_out, workspace,
+                                        workspace_elems, nullptr, stream_);
+}
+
+// The same launch with attention dropout under Rule D (draw.h; include/npi_gnn.h): `eid` [nnz_max] of this by-source side; the rows
+// are weighted with alpha kappa and dz = alpha (kappa <dOut_i, h_j> - D_i) leaky_relu'(z)
+extern "C" int npi_gat_backward_fused_heads_dropout(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
+                                                    const int32_t* item_row, int64_t item_edges, int64_t N, int64_t nnz_max,
+                                                    const float* dout, int64_t ldd, const float* dout2, int64_t split,
+                                                    const float* hfeat, int64_t ldh, float* out, int64_t ldo, int64_t H, int64_t C,
+                                                    const float* tpack, const float* a_src, float slope, float* dz, float* carry,
+                                                    float* row_scales_out, float* g_src_out, float* workspace, int64_t workspace_elems,
+                                                    void* stream_, const int32_t* eid, int64_t key, int64_t threshold, float scale) {
+    const DropArgs drop{eid, key, (uint64_t)threshold, scale};
+    return gat_backward_fused_heads_run(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, dout, ldd, dout2, split, hfeat, ldh, out,
+                                        ldo, H, C, tpack, a_src, slope, dz, carry, row_scales_out, g_src_out, workspace,
+                                        workspace_elems, &drop, stream_);
 }
 
 extern "C" int npi_gat_rank1_add(float* dh, int64_t ld, const float* g_dst, const float* g_src, const float* att,
@@ -775,11 +853,11 @@ extern "C" int npi_gat_aggregate_scores(const int32_t* rowptr, const int32_t* co
 // One head, C <= 256: the forward aggregation WITH the softmax statistics (W_GAT_DST_FUSED): out, m, s in one launch; no
 // statistics pass, no per-entry score array, no gather of the sources' scores (npi_gat_softmax_stats_ex +
 // npi_gat_aggregate_scores do the same in two): the source half of every score is recomputed from the gathered row
-extern "C" int npi_gat_aggregate_fused(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* item_row,
-                                           int64_t item_edges, int64_t N, int64_t nnz_max, const float* x, int64_t ldx,
-                                           const float* x2, int64_t split, float* out, int64_t ldo, int64_t C, const float* a_dst,
-                                           const float* att, float slope, const float* bias, int relu, float* m, float* s,
-                                           float* carry, float* row_scales_out, void* stream_) {
+static int gat_aggregate_fused_run(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* item_row,
+                                   int64_t item_edges, int64_t N, int64_t nnz_max, const float* x, int64_t ldx,
+                                   const float* x2, int64_t split, float* out, int64_t ldo, int64_t C, const float* a_dst,
+                                   const float* att, float slope, const float* bias, int relu, float* m, float* s,
+                                   float* carry, float* row_scales_out, const DropArgs* drop, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     NPI_REQUIRE(row_scales_out == nullptr || (C == 256 && ldx % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)x % 16) == 0 &&
                                               ((uintptr_t)out % 16) == 0 && (x2 == nullptr || ((uintptr_t)x2 % 16) == 0)),
@@ -799,19 +877,29 @@ extern "C" int npi_gat_aggregate_fused(const int32_t* rowptr, const int32_t* col
     P.carry = carry; P.bias = bias;
     P.H = 1; P.C = (int)C; P.a_dst = a_dst; P.att = att; P.slope = slope; P.m_out = m; P.s_out = s; P.relu = relu ? 1 : 0;
     P.scale_out = row_scales_out;                // the scales of the rows as they are stored: bias and ReLU applied
-    return segsum_run(P, W_GAT_DST_FUSED, 0, nnz_max, NPI_F32, stream);
+    if (!set_drop(P, drop, "npi_gat_aggregate_fused")) return NPI_ERR_ARG;
+    return segsum_run(P, W_GAT_DST_FUSED | (drop ? W_DROP : 0), 0, nnz_max, NPI_F32, stream);
+}
+
+extern "C" int npi_gat_aggregate_fused(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* item_row,
+                                           int64_t item_edges, int64_t N, int64_t nnz_max, const float* x, int64_t ldx,
+                                           const float* x2, int64_t split, float* out, int64_t ldo, int64_t C, const float* a_dst,
+                                           const float* att, float slope, const float* bias, int relu, float* m, float* s,
+                                           float* carry, float* row_scales_out, void* stream_) {
+    return gat_aggregate_fused_run(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, x, ldx, x2, split, out, ldo, C, a_dst, att,
+                                   slope, bias, relu, m, s, carry, row_scales_out, nullptr, stream_);
 }
 
 // The same launch for 2 / 4 / 8 heads (W_GAT_DST_FUSED_H2/4/8; the shapes of the fused backward: 32 / 64 / 128 channels per head,
 // H C <= 256): a_dst, m, s are [N, H], att [H, 2C].  One head forwards to the mode above; no other shape has a kernel
-extern "C" int npi_gat_aggregate_fused_heads(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* item_row,
-                                             int64_t item_edges, int64_t N, int64_t nnz_max, const float* x, int64_t ldx,
-                                             const float* x2, int64_t split, float* out, int64_t ldo, int64_t H, int64_t C,
-                                             const float* a_dst, const float* att, float slope, const float* bias, int relu,
-                                             float* m, float* s, float* carry, float* row_scales_out, void* stream_) {
+static int gat_aggregate_fused_heads_run(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* item_row,
+                                         int64_t item_edges, int64_t N, int64_t nnz_max, const float* x, int64_t ldx,
+                                         const float* x2, int64_t split, float* out, int64_t ldo, int64_t H, int64_t C,
+                                         const float* a_dst, const float* att, float slope, const float* bias, int relu,
+                                         float* m, float* s, float* carry, float* row_scales_out, const DropArgs* drop, void* stream_) {
     if (H == 1)
-        return npi_gat_aggregate_fused(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, x, ldx, x2, split, out, ldo, C, a_dst, att,
-                                       slope, bias, relu, m, s, carry, row_scales_out, stream_);
+        return gat_aggregate_fused_run(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, x, ldx, x2, split, out, ldo, C, a_dst, att,
+                                       slope, bias, relu, m, s, carry, row_scales_out, drop, stream_);
     hipStream_t stream = (hipStream_t)stream_;
     NPI_REQUIRE(H == 2 || H == 4 || H == 8, "npi_gat_aggregate_fused_heads: heads must be 1, 2, 4 or 8");
     NPI_REQUIRE((C == 32 || C == 64 || C == 128) && H * C <= 256,
@@ -834,15 +922,40 @@ extern "C" int npi_gat_aggregate_fused_heads(const int32_t* rowptr, const int32_
     P.x2 = x2; P.split = (int)split;
     P.carry = carry; P.bias = bias;
     P.H = (int)H; P.C = (int)C; P.a_dst = a_dst; P.att = att; P.slope = slope; P.m_out = m; P.s_out = s; P.relu = relu ? 1 : 0;
-    return segsum_run(P, H == 2 ? W_GAT_DST_FUSED_H2 : H == 4 ? W_GAT_DST_FUSED_H4 : W_GAT_DST_FUSED_H8, 0, nnz_max, NPI_F32, stream);
+    if (!set_drop(P, drop, "npi_gat_aggregate_fused_heads")) return NPI_ERR_ARG;
+    return segsum_run(P, (H == 2 ? W_GAT_DST_FUSED_H2 : H == 4 ? W_GAT_DST_FUSED_H4 : W_GAT_DST_FUSED_H8) | (drop ? W_DROP : 0), 0, nnz_max,
+                      NPI_F32, stream);
 }
 
-extern "C" int npi_gat_edge_grad_ex(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
-                                    int64_t N, int64_t nnz_max, const float* hfeat, int64_t ldh,
-                                    const float* hfeat2, int64_t split,
-                                    const float* dout, int64_t ldd, int64_t H, int64_t C,
-                                    const float* a_dst, const float* a_src, const float* m, const float* s,
-                                    const float* D, float slope, int swap, float* dz, float* alpha_out, void* stream_) {
+extern "C" int npi_gat_aggregate_fused_heads(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* item_row,
+                                             int64_t item_edges, int64_t N, int64_t nnz_max, const float* x, int64_t ldx,
+                                             const float* x2, int64_t split, float* out, int64_t ldo, int64_t H, int64_t C,
+                                             const float* a_dst, const float* att, float slope, const float* bias, int relu,
+                                             float* m, float* s, float* carry, float* row_scales_out, void* stream_) {
+    return gat_aggregate_fused_heads_run(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, x, ldx, x2, split, out, ldo, H, C, a_dst,
+                                         att, slope, bias, relu, m, s, carry, row_scales_out, nullptr, stream_);
+}
+
+// The same launch with attention dropout under Rule D (draw.h; include/npi_gnn.h): `eid` [nnz_max] of this by-target side; an entry
+// adds alpha kappa h_j, the statistics m, s stay those of the undropped scores
+extern "C" int npi_gat_aggregate_fused_heads_dropout(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
+                                                     const int32_t* item_row, int64_t item_edges, int64_t N, int64_t nnz_max,
+                                                     const float* x, int64_t ldx, const float* x2, int64_t split, float* out, int64_t ldo,
+                                                     int64_t H, int64_t C, const float* a_dst, const float* att, float slope,
+                                                     const float* bias, int relu, float* m, float* s, float* carry,
+                                                     float* row_scales_out, void* stream_, const int32_t* eid, int64_t key,
+                                                     int64_t threshold, float scale) {
+    const DropArgs drop{eid, key, (uint64_t)threshold, scale};
+    return gat_aggregate_fused_heads_run(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, x, ldx, x2, split, out, ldo, H, C, a_dst,
+                                         att, slope, bias, relu, m, s, carry, row_scales_out, &drop, stream_);
+}
+
+static int gat_edge_grad_run(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
+                             int64_t N, int64_t nnz_max, const float* hfeat, int64_t ldh,
+                             const float* hfeat2, int64_t split,
+                             const float* dout, int64_t ldd, int64_t H, int64_t C,
+                             const float* a_dst, const float* a_src, const float* m, const float* s,
+                             const float* D, float slope, int swap, float* dz, float* alpha_out, const DropArgs* drop, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     NPI_REQUIRE(hfeat2 == nullptr || (split >= 0 && split < 0x7fffffff), "npi_gat_edge_grad_ex: bad split");
     if (hfeat2 == nullptr) { hfeat2 = hfeat; split = 0x7fffffff; }
@@ -860,9 +973,52 @@ extern "C" int npi_gat_edge_grad_ex(const int32_t* rowptr, const int32_t* col, c
     const unsigned grid = (unsigned)ceil_div(n_items, 4);
     const int nch = (int)ceil_div(F, 256);
 #define NPI_EG(NC) gat_edge_grad_kernel<NC><<<grid, 256, 0, stream>>>(rowptr, col, rowidx, (int)N, n_items, chunk, hfeat, ldh, dout, ldd, (int)H, (int)C, a_dst, a_src, m, s, D, slope, dz, alpha_out, hfeat2, (int)split, swap)
-    if (nch == 1) NPI_EG(1); else if (nch == 2) NPI_EG(2); else if (nch == 3) NPI_EG(3); else NPI_EG(4);
+#define NPI_EG_DROP(NC) gat_edge_grad_kernel<NC, true><<<grid, 256, 0, stream>>>(rowptr, col, rowidx, (int)N, n_items, chunk, hfeat, ldh, dout, ldd, (int)H, (int)C, a_dst, a_src, m, s, D, slope, dz, alpha_out, hfeat2, (int)split, swap, drop->eid, draw_root(drop->key, DRAW_RULE_D), drop->threshold, drop->scale)
+    if (drop != nullptr) {
+        NPI_REQUIRE(drop->eid != nullptr, "npi_gat_edge_grad_dropout: null eid (attention dropout is keyed on the entries' edge ids)");
+        if (nch == 1) NPI_EG_DROP(1); else if (nch == 2) NPI_EG_DROP(2); else if (nch == 3) NPI_EG_DROP(3); else NPI_EG_DROP(4);
+    } else if (nch == 1) NPI_EG(1); else if (nch == 2) NPI_EG(2); else if (nch == 3) NPI_EG(3); else NPI_EG(4);
 #undef NPI_EG
+#undef NPI_EG_DROP
     return check_launch("npi_gat_edge_grad");
+}
+
+extern "C" int npi_gat_edge_grad_ex(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
+                                    int64_t N, int64_t nnz_max, const float* hfeat, int64_t ldh,
+                                    const float* hfeat2, int64_t split,
+                                    const float* dout, int64_t ldd, int64_t H, int64_t C,
+                                    const float* a_dst, const float* a_src, const float* m, const float* s,
+                                    const float* D, float slope, int swap, float* dz, float* alpha_out, void* stream_) {
+    return gat_edge_grad_run(rowptr, col, rowidx, N, nnz_max, hfeat, ldh, hfeat2, split, dout, ldd, H, C, a_dst, a_src, m, s, D, slope,
+                             swap, dz, alpha_out, nullptr, stream_);
+}
+
+// npi_gat_edge_grad_ex with attention dropout under Rule D: dz = alpha (kappa <dOut_i, h_j> - D_i) leaky_relu'(z); `eid` [nnz_max] of
+// the side that is walked (alpha_out, when asked for, stays the undropped alpha)
+extern "C" int npi_gat_edge_grad_dropout(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
+                                         int64_t N, int64_t nnz_max, const float* hfeat, int64_t ldh,
+                                         const float* hfeat2, int64_t split,
+                                         const float* dout, int64_t ldd, int64_t H, int64_t C,
+                                         const float* a_dst, const float* a_src, const float* m, const float* s,
+                                         const float* D, float slope, int swap, float* dz, float* alpha_out, void* stream_,
+                                         const int32_t* eid, int64_t key, int64_t threshold, float scale) {
+    const DropArgs drop{eid, key, (uint64_t)threshold, scale};
+    return gat_edge_grad_run(rowptr, col, rowidx, N, nnz_max, hfeat, ldh, hfeat2, split, dout, ldd, H, C, a_dst, a_src, m, s, D, slope,
+                             swap, dz, alpha_out, &drop, stream_);
+}
+
+// keep [nnz_max, H] f32: kappa (0 or `scale`) of every entry and head of one side under Rule D, in the side's entry order (0 behind the
+// last entry) -- the mask of the fused launches as an array, for the composed variant of the layer and for tests
+extern "C" int npi_gat_dropout_keep(const int32_t* rowptr, const int32_t* col, const int32_t* eid, int64_t N, int64_t nnz_max,
+                                    int64_t H, int64_t key, int64_t threshold, float scale, float* keep, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    NPI_REQUIRE(N >= 0 && N < 0x7fffffff && nnz_max >= 0 && nnz_max < 0x7fffffff && H > 0 && H <= 64,
+                "npi_gat_dropout_keep: bad size (1 <= heads <= 64)");
+    if (nnz_max == 0) return NPI_OK;
+    NPI_REQUIRE(rowptr && col && eid && keep, "npi_gat_dropout_keep: null pointer");
+    gat_dropout_keep_kernel<<<(unsigned)ceil_div(nnz_max, 256), 256, 0, stream>>>(rowptr, col, eid, (int)N, nnz_max, (int)H,
+                                                                                 draw_root(key, DRAW_RULE_D), (uint64_t)threshold, scale, keep);
+    return check_launch("npi_gat_dropout_keep");
 }
 
 extern "C" int npi_entry_transpose_map(const int32_t* src_eid, const int32_t* src_rowidx, const int32_t* src_rowptr,

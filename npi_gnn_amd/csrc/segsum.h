@@ -15,12 +15,22 @@ enum { W_NONE = 0, W_ARRAY = 1, W_GAT_DST = 2, W_GAT_SRC = 3, W_GAT_SRC_PRE = 4,
        W_GAT_DST_FUSED = 10,
        // the same forward for 2 / 4 / 8 heads (H C <= 256, C = 32 / 64 / 128): a head is a group of C / 4 lanes, every lane keeps the
        // online softmax of ITS head, every partial row carries (max, sum exp) per head
-       W_GAT_DST_FUSED_H2 = 11, W_GAT_DST_FUSED_H4 = 12, W_GAT_DST_FUSED_H8 = 13 };
-constexpr bool is_fused_mode(int m) { return m == W_GAT_SRC_FUSED || (m >= W_GAT_SRC_FUSED_H2 && m <= W_GAT_SRC_FUSED_H8); }
-constexpr int fused_heads(int m) { return m == W_GAT_SRC_FUSED_H2 ? 2 : m == W_GAT_SRC_FUSED_H4 ? 4 : m == W_GAT_SRC_FUSED_H8 ? 8 : 1; }
+       W_GAT_DST_FUSED_H2 = 11, W_GAT_DST_FUSED_H4 = 12, W_GAT_DST_FUSED_H8 = 13,
+       // a FLAG on the eight fused modes (W_GAT_DST_FUSED* | W_DROP, W_GAT_SRC_FUSED* | W_DROP): attention dropout under Rule D
+       // (draw.h).  The lane that computes an entry's weight also computes kappa = 0 or 1 / (1 - p) per head from the entry's eid;
+       // kappa multiplies the accumulate weight (and, in the backward, the dot inside dz) and never enters the softmax statistics.
+       // Kernels of their own: the instantiations without the flag are the code they were
+       W_DROP = 32 };
+constexpr int base_mode(int m) { return m & ~W_DROP; }
+constexpr bool drop_mode(int m) { return (m & W_DROP) != 0; }
+constexpr bool is_fused_mode(int m) { return base_mode(m) == W_GAT_SRC_FUSED || (base_mode(m) >= W_GAT_SRC_FUSED_H2 && base_mode(m) <= W_GAT_SRC_FUSED_H8); }
+constexpr int fused_heads(int m) {
+    return base_mode(m) == W_GAT_SRC_FUSED_H2 ? 2 : base_mode(m) == W_GAT_SRC_FUSED_H4 ? 4 : base_mode(m) == W_GAT_SRC_FUSED_H8 ? 8 : 1;
+}
 // heads of the fused FORWARD (the online softmax): 0 = not that mode
 constexpr int softmax_heads(int m) {
-    return m == W_GAT_DST_FUSED ? 1 : m == W_GAT_DST_FUSED_H2 ? 2 : m == W_GAT_DST_FUSED_H4 ? 4 : m == W_GAT_DST_FUSED_H8 ? 8 : 0;
+    return base_mode(m) == W_GAT_DST_FUSED ? 1 : base_mode(m) == W_GAT_DST_FUSED_H2 ? 2 : base_mode(m) == W_GAT_DST_FUSED_H4 ? 4
+         : base_mode(m) == W_GAT_DST_FUSED_H8 ? 8 : 0;
 }
 
 // What segsum.hip's row epilogue, lane geometry, launch bounds and dispatch ask about a weight mode, each property named once
@@ -34,7 +44,8 @@ struct ModeTraits {
     bool rank1;              // rank-1 terms of the attention-score gradient in the row epilogue
     bool row_scales;         // may also write the finished rows' power-of-two scales (the EXACT == 2 kernels exist for these only)
 };
-constexpr ModeTraits mode_traits(int m) {
+constexpr ModeTraits mode_traits(int wm) {
+    const int m = base_mode(wm);                             // (W_DROP changes no trait)
     //                                        add    lane   head   norm   smax  fused rank1  scales
     return m == W_NONE            ? ModeTraits{true,  false, false, false, false, 0, false, true}
          : m == W_ARRAY           ? ModeTraits{false, true,  false, false, false, 0, false, true}
@@ -102,6 +113,10 @@ struct SegParams {
     // `rowidx` above is then the by-TARGET CSR's row of every entry, a_dst [N, H] the targets' scores, slope the leaky_relu's
     float* m_out;
     float* s_out;
+    // W_DROP (Rule D, draw.h): the entries' eid (this side's entry order), draw_root(key, DRAW_RULE_D), floor(p 2^64), float32(1 / (1 - p))
+    const int32_t* eid;
+    uint64_t drop_root, drop_threshold;
+    float drop_scale;
 };
 
 // x / out / bias are stored as `dtype` (NPI_F32 or NPI_BF16; the struct's float* are reinterpreted)

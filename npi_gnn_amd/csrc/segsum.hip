@@ -33,7 +33,11 @@
 //              are resolved, and the row's (m, s) come out beside the output for the backward
 //   W_GAT_DST_FUSED_H2/4/8  the same for 2 / 4 / 8 heads (H C <= 256): a head is a group of C / 4 lanes, the score's dot is summed
 //              inside the group, every lane keeps (max, sum exp) of its own head and every partial row carries them per head
+//   ... | W_DROP  the eight fused modes with attention dropout under Rule D (draw.h): the lane that owns an entry's weight computes
+//              kappa = 0 or 1 / (1 - p) per head from the entry's eid; kappa scales what the entry ADDS (and the dot inside dz),
+//              never the softmax statistics -- so every partial row, however it is cut and merged, carries it already
 #include "segsum.h"
+#include "draw.h"
 
 #include <stdlib.h>
 
@@ -721,8 +725,10 @@ __device__ __forceinline__ void resolve_block(const SegParams& P, const Geo& L, 
 // The online softmax's step for one entry of score e, vr = this lane's columns of its gathered row.  One head: every lane holds the
 // same e and m_run, a new maximum is a wave-uniform branch.  Several heads (HF > 1): e, m_run, s_run are those of the lane's own
 // head, and heads reach new maxima at different entries -- which lanes rescale is a select under one wave-uniform "any lane" test
-template <int HF, int VEC>
-__device__ __forceinline__ void softmax_entry(float e, const float (&vr)[VEC], float (&acc)[VEC], float& m_run, float& s_run) {
+// DROP: kap = the entry's dropout factor (of the lane's head): it scales what the entry adds to the row, not (m_run, s_run)
+template <int HF, int VEC, bool DROP = false>
+__device__ __forceinline__ void softmax_entry(float e, const float (&vr)[VEC], float (&acc)[VEC], float& m_run, float& s_run,
+                                              float kap = 1.f) {
     if constexpr (HF > 1) {
         const bool up = e > m_run;
         if (__any(up)) {
@@ -741,15 +747,24 @@ __device__ __forceinline__ void softmax_entry(float e, const float (&vr)[VEC], f
     }
     const float we = expf(e - m_run);
     s_run += we;
+    if constexpr (DROP) {
+        const float wk = we * kap;
 #pragma unroll
-    for (int q = 0; q < VEC; ++q) acc[q] = fmaf(we, vr[q], acc[q]);
+        for (int q = 0; q < VEC; ++q) acc[q] = fmaf(wk, vr[q], acc[q]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) acc[q] = fmaf(we, vr[q], acc[q]);
+    }
 }
 
 // one item: `part` = this wave's two LDS rows ([2][NCH VEC WAVE]: head partial, tail partial), `M` = what it leaves behind;
 // `hstat` (W_GAT_DST_FUSED_H2/4/8 only) = this wave's [2][SM_HEADS][2]: (max, sum exp) per head of the two parts
-template <typename T, int VEC, int NCH, int WMODE, int EXACT>
-__device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC, NCH, WMODE, EXACT>& L, const int item,
+// WM: the weight mode as the kernel is instantiated -- WMODE below, possibly with the W_DROP flag
+template <typename T, int VEC, int NCH, int WM, int EXACT>
+__device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC, NCH, WM, EXACT>& L, const int item,
                                             float* __restrict__ part, ItemMeta* __restrict__ M, float* __restrict__ hstat = nullptr) {
+    constexpr int WMODE = base_mode(WM);
+    constexpr bool DROP = drop_mode(WM);
     constexpr int U = inflight<VEC, NCH>::value;
     constexpr int ROWF = NCH * VEC * WAVE;
     const int lane = lane_id();
@@ -873,7 +888,7 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
             if constexpr (HF > 1) put_stats(0);
             head = false;
         } else {
-            finish_row<T, VEC, NCH, WMODE, EXACT>(P, L, acc, r, row_end - row_start, m_run, s_run);
+            finish_row<T, VEC, NCH, WM, EXACT>(P, L, acc, r, row_end - row_start, m_run, s_run);
         }
 #pragma unroll
         for (int c = 0; c < NCH; ++c)
@@ -916,6 +931,13 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
         (void)rlk;
         float wv = 1.f;
         if (WMODE == W_ARRAY || WMODE == W_GAT_DST_PRE) wv = (lane < nb) ? P.w[kb + lane] : 0.f;
+        // W_DROP: bit h of lane l = head h of entry kb + l is KEPT (Rule D, keyed on the entry's eid: one 4-byte load per entry)
+        int kbits = 0;
+        float alpha_l = 0.f;             // W_GAT_SRC_FUSED | W_DROP: alpha of entry kb + l without its dropout factor (dz needs both)
+        if constexpr (DROP) {
+            if (lane < nb) kbits = drop_keep_bits<(SMX ? HF : HH)>(P.drop_root, P.drop_threshold, P.eid[kb + lane], cv);
+        }
+        (void)kbits; (void)alpha_l;
         float dz_d = 0.f, dz_g = 0.f;    // W_GAT_SRC_FUSED, packed: D of the entry's target and leaky_relu' of its score
         // several heads: lane l holds alpha / D / leaky_relu' of entry kb + l for EVERY head; the lane's own head picks its weight
         float wvh[HH], dzdh[HH], dzgh[HH];
@@ -943,6 +965,10 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
                 wv = expf(lrelu(z, P.slope) - t.y) * t.z;
                 dz_d = t.w;
                 dz_g = z > 0.f ? 1.f : P.slope;
+                if constexpr (DROP) {                        // the rows are weighted with alpha kappa
+                    alpha_l = wv;
+                    wv *= (kbits & 1) ? P.drop_scale : 0.f;
+                }
             } else {
                 wv = 0.f;
             }
@@ -990,7 +1016,12 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
                     const int k = kb + j + u;
                     while (k == row_end) close_row();
                     const float z = rs_a[0] + dt[u];
-                    softmax_entry<HF, VEC>(z > 0.f ? z : z * P.slope, v[u][0], acc[0], m_run, s_run);
+                    if constexpr (DROP) {
+                        const float kap = ((bcast_i(kbits, j + u) >> (HF > 1 ? L.hd[0] : 0)) & 1) ? P.drop_scale : 0.f;
+                        softmax_entry<HF, VEC, true>(z > 0.f ? z : z * P.slope, v[u][0], acc[0], m_run, s_run, kap);
+                    } else {
+                        softmax_entry<HF, VEC>(z > 0.f ? z : z * P.slope, v[u][0], acc[0], m_run, s_run);
+                    }
                 }
                 continue;
             }
@@ -1009,6 +1040,7 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
                         const float t = bcast_f(wvh[h], j + u);
                         ws = (myhead == h) ? t : ws;
                     }
+                    if constexpr (DROP) ws *= ((bcast_i(kbits, j + u) >> myhead) & 1) ? P.drop_scale : 0.f;
                 }
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) {
@@ -1084,7 +1116,12 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
                 for (int q = 0; q < VEC; ++q) dt = fmaf(v[0][q], at_src[q], dt);
                 dt = HF > 1 ? group_sum(dt, hlanes) : wave_sum_dpp(dt);
                 const float z = rs_a[0] + dt;
-                softmax_entry<HF, VEC>(z > 0.f ? z : z * P.slope, v[0], acc[0], m_run, s_run);
+                if constexpr (DROP) {
+                    const float kap = ((bcast_i(kbits, j) >> (HF > 1 ? L.hd[0] : 0)) & 1) ? P.drop_scale : 0.f;
+                    softmax_entry<HF, VEC, true>(z > 0.f ? z : z * P.slope, v[0], acc[0], m_run, s_run, kap);
+                } else {
+                    softmax_entry<HF, VEC>(z > 0.f ? z : z * P.slope, v[0], acc[0], m_run, s_run);
+                }
                 continue;
             }
             float ws = (WMODE == W_ARRAY || WMODE == W_GAT_SRC_PRE || WMODE == W_GAT_SRC_FUSED || WMODE == W_GAT_DST_PRE) ? bcast_f(wv, j) : 1.f;
@@ -1095,6 +1132,7 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
                     const float t = bcast_f(wvh[h], j);
                     ws = (myhead == h) ? t : ws;
                 }
+                if constexpr (DROP) ws *= ((bcast_i(kbits, j) >> myhead) & 1) ? P.drop_scale : 0.f;
             }
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
@@ -1126,8 +1164,13 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
             __builtin_amdgcn_wave_barrier();
             if (lane < nb) {
 #pragma unroll
-                for (int h = 0; h < HH; ++h)
-                    P.dz_out[(int64_t)(kb + lane) * HH + h] = wvh[h] * (pb[lane * HH + h] - dzdh[h]) * dzgh[h];
+                for (int h = 0; h < HH; ++h) {
+                    if constexpr (DROP)          // dz = alpha (kappa <dOut_i, h_j> - D_i) leaky_relu'
+                        P.dz_out[(int64_t)(kb + lane) * HH + h] =
+                            wvh[h] * ((((kbits >> h) & 1) ? P.drop_scale : 0.f) * pb[lane * HH + h] - dzdh[h]) * dzgh[h];
+                    else
+                        P.dz_out[(int64_t)(kb + lane) * HH + h] = wvh[h] * (pb[lane * HH + h] - dzdh[h]) * dzgh[h];
+                }
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -1136,7 +1179,8 @@ __device__ __forceinline__ void segsum_item(const SegParams& P, const Lanes<VEC,
             __builtin_amdgcn_wave_barrier();
             float dzv = 0.f;
             if (lane < nb) {
-                dzv = wv * (pb[lane] - dz_d) * dz_g;
+                if constexpr (DROP) dzv = alpha_l * (((kbits & 1) ? P.drop_scale : 0.f) * pb[lane] - dz_d) * dz_g;
+                else dzv = wv * (pb[lane] - dz_d) * dz_g;
                 P.dz_out[kb + lane] = dzv;
             }
             __builtin_amdgcn_wave_barrier();
@@ -1447,6 +1491,14 @@ static int launch_segsum(const SegParams& P, int wmode, hipStream_t stream) {
         NPI_SEG_MODE(W_GAT_SRC_FUSED_H2);
         NPI_SEG_MODE(W_GAT_SRC_FUSED_H4);
         NPI_SEG_MODE(W_GAT_SRC_FUSED_H8);
+        NPI_SEG_MODE(W_GAT_DST_FUSED | W_DROP);
+        NPI_SEG_MODE(W_GAT_DST_FUSED_H2 | W_DROP);
+        NPI_SEG_MODE(W_GAT_DST_FUSED_H4 | W_DROP);
+        NPI_SEG_MODE(W_GAT_DST_FUSED_H8 | W_DROP);
+        NPI_SEG_MODE(W_GAT_SRC_FUSED | W_DROP);
+        NPI_SEG_MODE(W_GAT_SRC_FUSED_H2 | W_DROP);
+        NPI_SEG_MODE(W_GAT_SRC_FUSED_H4 | W_DROP);
+        NPI_SEG_MODE(W_GAT_SRC_FUSED_H8 | W_DROP);
 #undef NPI_SEG_MODE
         default: break;
     }
@@ -1486,6 +1538,10 @@ int segsum_run(SegParams P, int wmode, int mean, int64_t nnz_max, int dtype, hip
     const int64_t F = P.F;
     if (!item_edges_ok(P.item)) {                             // the CSR's own item size, handed over by the caller next to item_row
         set_error("npi_segsum: item_edges must be 64 or %d (the value the CSR was built with)", NPI_ITEM_EDGES);
+        return NPI_ERR_ARG;
+    }
+    if (drop_mode(wmode) && P.eid == nullptr) {
+        set_error("npi_segsum: the dropout modes need the entries' eid");
         return NPI_ERR_ARG;
     }
     P.n_items = (int)num_items_of(nnz_max, P.item);

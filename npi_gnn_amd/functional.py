@@ -9,10 +9,13 @@ Formulas (PyG 1.4.2):
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+from fractions import Fraction
 from typing import Optional
 
 import torch
 
+from ._draw import epoch_seed
 from ._lib import (NPI_BF16, NPI_F32, NPI_GEMM_A_ZERO_PADDED, NPI_GEMM_EXACT_F32, NPI_GEMM_RESERVE_CUS, NPI_GEMM_SPLIT_F16X2,
                    NPI_GEMM_WORKSPACE_PREPARED, NPI_PAIR_LOGITS, NPI_PAIR_LOSS_BCE, NPI_PAIR_LOSS_GAE, NPI_PREPARE_F16X2, check, load, ptr,
                    require_gpu, stream_ptr)
@@ -1300,6 +1303,54 @@ def _inverse_transpose_map(graph: CSRGraph) -> torch.Tensor:
     return inv
 
 
+def _as_i64(u: int) -> int:
+    """the int64 with the bits of an unsigned 64-bit number (how the C ABI takes Rule D's threshold, as it takes the key)"""
+    return u - (1 << 64) if u >= (1 << 63) else u
+
+
+@dataclass(frozen=True)
+class AttentionDropout:
+    """GATConv's attention dropout as a SEEDED rule (Rule D, ``include/npi_gnn.h``): head ``h`` of an edge is dropped iff a word that
+    is a pure function of ``(seed, draw, edge, h)`` lies below ``floor(p 2^64)``; a kept attention weight is scaled by
+    ``1 / (1 - p)``.  The fused kernels recompute the decision per entry from the entry's ``eid`` in both orientations, so no mask
+    array exists and a step is reproducible from ``(seed, draw)``.  ``gat_conv(..., dropout=AttentionDropout(p, seed, draw))``."""
+    p: float
+    seed: int
+    draw: int = 0
+
+    def __post_init__(self):
+        if isinstance(self.p, bool) or not isinstance(self.p, (int, float)) or not 0.0 <= float(self.p) < 1.0:
+            raise ValueError(f"AttentionDropout: p must be a number in [0, 1), got {self.p!r}")
+        for name in ("seed", "draw"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"AttentionDropout: {name} must be an int, got {v!r}")
+        if self.draw < 0:
+            raise ValueError(f"AttentionDropout: draw must be >= 0, got {self.draw!r}")
+
+    @property
+    def key(self) -> int:
+        """the ``key`` of the C ABI: ``epoch_seed(seed, draw)``, as every other seeded rule"""
+        return epoch_seed(self.seed, self.draw)
+
+    @property
+    def threshold(self) -> int:
+        """``floor(p 2^64)`` in exact integer arithmetic, ``p`` taken as the double it is"""
+        return int(Fraction(float(self.p)) * 2 ** 64)
+
+    @property
+    def scale(self) -> float:
+        """``float32(1 / (1 - p))``: what a kept attention weight is multiplied by"""
+        return float(torch.tensor(1.0 / (1.0 - float(self.p)), dtype=torch.float64).to(torch.float32))
+
+    def args(self, side: CSRSide):
+        """the trailing arguments of the ``*_dropout`` entry points for a launch over ``side``"""
+        return ptr(side.eid), self.key, _as_i64(self.threshold), self.scale
+
+
+_GAT_FUSED_SHAPES = "one head of at most 256 channels (a multiple of 4), or 2 / 4 / 8 heads of 32 / 64 / 128 channels with heads * out <= 256"
+
+
 def gat_fused_shape(H: int, C: int) -> bool:
     """Shapes the fused backward serves (``npi_gat_backward_fused_heads``): ONE gather pass over the by-source entries yields
     the aggregation half of d hfeat AND every entry's score gradient -- one head of <= 256 channels, or 2 / 4 / 8 heads of
@@ -1421,14 +1472,15 @@ def gat_aggregate_scores(side: CSRSide, table, table2, C, scores, m, s, bias=Non
 
 
 def gat_aggregate_fused(side: CSRSide, table, table2, C, a_dst, att2, slope, bias=None, out=None, relu: bool = False,
-                        scales_out: Optional[torch.Tensor] = None, H: int = 1):
+                        scales_out: Optional[torch.Tensor] = None, H: int = 1, dropout: Optional[AttentionDropout] = None):
     """One head of at most 256 channels, or ``H`` = 2 / 4 / 8 heads on the shapes of ``gat_fused_shape``: ``(out, m, s)`` -- the
     forward aggregation together with the softmax statistics ``[n_rows, H]`` of every row, in ONE launch
     (``npi_gat_aggregate_fused_heads``): an online softmax whose scores' source half is recomputed from the gathered
     rows (``att2``: the layer's ``[H, 2C]`` attention vectors) -- no statistics pass, no per-entry score array, no gather of
     ``a_src``.  ``a_dst`` ``[n_rows, H]``; ``table2``: second part of a two-part table.  ``scales_out`` ``[n_rows]`` (one head of 256
     channels): also the power-of-two scale of every stored row (bias and ReLU applied) -- the ``x_scales`` of the next layer's
-    projection."""
+    projection.  ``dropout``: attention dropout under Rule D inside the launch (``npi_gat_aggregate_fused_heads_dropout``): an entry
+    adds ``alpha kappa h_j``; ``m``, ``s`` stay the statistics of the undropped scores."""
     dev = table.device
     table = _f32c(table, "table")
     if table2 is not None:
@@ -1441,13 +1493,15 @@ def gat_aggregate_fused(side: CSRSide, table, table2, C, a_dst, att2, slope, bia
         _check_out(out, side.n_rows, H * C, table, "gat_aggregate_fused")
     m = torch.empty((side.n_rows, H), dtype=torch.float32, device=dev)
     s = torch.empty((side.n_rows, H), dtype=torch.float32, device=dev)
+    lib = load()
+    fn, extra = (lib.npi_gat_aggregate_fused_heads, ()) if dropout is None else (lib.npi_gat_aggregate_fused_heads_dropout, dropout.args(side))
     with _tag_events("gat_fwd_aggregate", dev):
-        check(load().npi_gat_aggregate_fused_heads(ptr(side.rowptr), ptr(side.col), ptr(side.rowidx), ptr(side.item_row), side.item,
-                                                   side.n_rows, side.nnz_max, ptr(table), table.stride(0), ptr(table2),
-                                                   table.size(0) if table2 is not None else 0, ptr(out), out.stride(0), H, C,
-                                                   ptr(a_dst.contiguous()), ptr(_f32c(att2.reshape(-1), "att")), float(slope), ptr(bias),
-                                                   1 if relu else 0, ptr(m), ptr(s), ptr(side.carry(H * C)), ptr(scales_out),
-                                                   stream_ptr(dev)),
+        check(fn(ptr(side.rowptr), ptr(side.col), ptr(side.rowidx), ptr(side.item_row), side.item,
+                 side.n_rows, side.nnz_max, ptr(table), table.stride(0), ptr(table2),
+                 table.size(0) if table2 is not None else 0, ptr(out), out.stride(0), H, C,
+                 ptr(a_dst.contiguous()), ptr(_f32c(att2.reshape(-1), "att")), float(slope), ptr(bias),
+                 1 if relu else 0, ptr(m), ptr(s), ptr(side.carry(H * C)), ptr(scales_out),
+                 stream_ptr(dev), *extra),
               "npi_gat_aggregate_fused_heads")
     return out, m, s
 
@@ -1466,12 +1520,15 @@ def gat_pack_targets(a_dst, m, s, D, out=None):
 
 
 def gat_backward_fused_packed(side: CSRSide, dout, dout2, hrow, C, tpack, a_src_rows, slope, out=None, H: int = 1,
-                              scales_out: Optional[torch.Tensor] = None, rowsum_out: Optional[torch.Tensor] = None):
+                              scales_out: Optional[torch.Tensor] = None, rowsum_out: Optional[torch.Tensor] = None,
+                              dropout: Optional[AttentionDropout] = None):
     """By-SOURCE side: (out [n_rows, H C] = sum_q alpha_q dout[col q], dz [nnz_max, H] per entry and head) in one gather pass;
     ``dout2``: second part of the gathered table; ``tpack`` [n_cols H, 4] indexed by (column id, head); ``hrow`` /
     ``a_src_rows``: features and source scores of the ROW nodes.  H in {1, 2, 4, 8} (npi_gat_backward_fused_heads).
     ``scales_out`` ``[n_rows]`` (H C == 256): also the power-of-two scale of every row of ``out``, for the fp16 x 2 GEMM behind it.
-    ``rowsum_out`` ``[n_rows]`` (one head): also the row sums of dz -- ``seg_rowsum(side, dz, 1)`` -- from the lanes that compute dz."""
+    ``rowsum_out`` ``[n_rows]`` (one head): also the row sums of dz -- ``seg_rowsum(side, dz, 1)`` -- from the lanes that compute dz.
+    ``dropout``: attention dropout under Rule D (``npi_gat_backward_fused_heads_dropout``): ``out = sum_q alpha_q kappa_q dout[col q]``,
+    ``dz = alpha (kappa <dOut_i, h_j> - D_i) leaky_relu'``."""
     dev = dout.device
     dout = _f32c(dout, "dout")
     if dout2 is not None:
@@ -1495,13 +1552,15 @@ def gat_backward_fused_packed(side: CSRSide, dout, dout2, hrow, C, tpack, a_src_
         return out.zero_(), dz
     n_ws = int(load().npi_seg_scan_workspace_elems(side.nnz_max, 1)) if rowsum_out is not None else 0
     ws = torch.empty(n_ws, dtype=torch.float32, device=dev) if n_ws else None
+    lib = load()
+    fn, extra = (lib.npi_gat_backward_fused_heads, ()) if dropout is None else (lib.npi_gat_backward_fused_heads_dropout, dropout.args(side))
     with _tag_events("gat_bwd_fused", dev):
-        check(load().npi_gat_backward_fused_heads(ptr(side.rowptr), ptr(side.col), ptr(side.rowidx), ptr(side.item_row), side.item,
-                                                      side.n_rows, side.nnz_max, ptr(dout), dout.stride(0), ptr(dout2),
-                                                      dout.size(0) if dout2 is not None else 0, ptr(hrow), hrow.stride(0), ptr(out),
-                                                      out.stride(0), H, C, ptr(tpack), ptr(a_src_rows.contiguous()), float(slope), ptr(dz),
-                                                      ptr(side.carry(H * C)), ptr(scales_out), ptr(rowsum_out), ptr(ws), n_ws,
-                                                      stream_ptr(dev)),
+        check(fn(ptr(side.rowptr), ptr(side.col), ptr(side.rowidx), ptr(side.item_row), side.item,
+                 side.n_rows, side.nnz_max, ptr(dout), dout.stride(0), ptr(dout2),
+                 dout.size(0) if dout2 is not None else 0, ptr(hrow), hrow.stride(0), ptr(out),
+                 out.stride(0), H, C, ptr(tpack), ptr(a_src_rows.contiguous()), float(slope), ptr(dz),
+                 ptr(side.carry(H * C)), ptr(scales_out), ptr(rowsum_out), ptr(ws), n_ws,
+                 stream_ptr(dev), *extra),
               "npi_gat_backward_fused_heads")
     return out, dz
 
@@ -1514,10 +1573,11 @@ def gat_rank1_add(dh, g_dst, g_src, att2, H, C):
 
 
 def gat_edge_grad(side: CSRSide, col_feat, col_feat2, row_feat, H, C, a_dst, a_src, m, s, D, slope, swap,
-                  alpha_out=None):
+                  alpha_out=None, dropout: Optional[AttentionDropout] = None):
     """dz per entry of ``side`` (``npi_gat_edge_grad_ex``).  swap = 0: rows are targets (row_feat = dOut rows; a_dst,
     m, s, D by row; a_src by column; col_feat = gathered hfeat).  swap = 1: rows are sources (row_feat = their hfeat;
-    a_src by row; a_dst, m, s, D by column; col_feat = gathered dOut)."""
+    a_src by row; a_dst, m, s, D by column; col_feat = gathered dOut).  ``dropout``: Rule D's factor on the dot inside dz
+    (``npi_gat_edge_grad_dropout``), the same in both orientations."""
     dev = row_feat.device
     dz = torch.empty((max(side.nnz_max, 1), H), dtype=torch.float32, device=dev)
     col_feat = _f32c(col_feat, "col_feat")
@@ -1525,11 +1585,13 @@ def gat_edge_grad(side: CSRSide, col_feat, col_feat2, row_feat, H, C, a_dst, a_s
         col_feat2 = _f32c(col_feat2, "col_feat2")
         if col_feat2.stride(0) != col_feat.stride(0):
             raise ValueError("the two parts of the table must share the row pitch")
-    check(load().npi_gat_edge_grad_ex(ptr(side.rowptr), ptr(side.col), ptr(side.rowidx), side.n_rows, side.nnz_max,
-                                      ptr(col_feat), col_feat.stride(0), ptr(col_feat2),
-                                      col_feat.size(0) if col_feat2 is not None else 0,
-                                      ptr(row_feat), row_feat.stride(0), H, C, ptr(a_dst), ptr(a_src), ptr(m), ptr(s),
-                                      ptr(D), float(slope), int(swap), ptr(dz), ptr(alpha_out), stream_ptr(dev)),
+    lib = load()
+    fn, extra = (lib.npi_gat_edge_grad_ex, ()) if dropout is None else (lib.npi_gat_edge_grad_dropout, dropout.args(side))
+    check(fn(ptr(side.rowptr), ptr(side.col), ptr(side.rowidx), side.n_rows, side.nnz_max,
+             ptr(col_feat), col_feat.stride(0), ptr(col_feat2),
+             col_feat.size(0) if col_feat2 is not None else 0,
+             ptr(row_feat), row_feat.stride(0), H, C, ptr(a_dst), ptr(a_src), ptr(m), ptr(s),
+             ptr(D), float(slope), int(swap), ptr(dz), ptr(alpha_out), stream_ptr(dev), *extra),
           "npi_gat_edge_grad")
     return dz
 
@@ -1563,11 +1625,15 @@ class _GatConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, att, bias, graph: CSRGraph, heads: int, slope: float, relu: bool = False,
-                sch: Schedule = DEFAULT, x_scales: Optional[torch.Tensor] = None, want_scales: bool = False):
+                sch: Schedule = DEFAULT, x_scales: Optional[torch.Tensor] = None, want_scales: bool = False,
+                dropout: Optional[AttentionDropout] = None):
         H = int(heads)
         C = weight.size(1) // H
         att2 = _f32c(att.reshape(H, 2 * C), "att")
         d = graph.by_dst
+        # dropout (Rule D): inside the two fused launches only -- gat_conv sends every other shape / schedule to the composed variant
+        if dropout is not None and not (gat_fused_shape(H, C) and d.nnz_max > 0 and sch.gat_fused_stats):
+            raise ValueError("_GatConvFn: attention dropout runs inside the fused kernels only")
         # x_scales (row_scales(x): computed once for a feature matrix that does not change between steps, or handed on by the
         # layer in front): the projection on two fp16 pieces per operand
         _check_scales(x_scales, x.size(0), "gat_conv(x_scales=)")
@@ -1584,10 +1650,11 @@ class _GatConvFn(torch.autograd.Function):
             # merge their parts' (max, sum exp) where cut rows are resolved (round 5: one pass over col / rowidx and a launch less)
             if want_scales and C == 256:
                 out_scales = torch.empty(d.n_rows, dtype=torch.float32, device=x.device)
-            out, m, s = gat_aggregate_fused(d, hfeat, None, C, a_dst, att2, slope, bias=bias, relu=relu, scales_out=out_scales)
+            out, m, s = gat_aggregate_fused(d, hfeat, None, C, a_dst, att2, slope, bias=bias, relu=relu, scales_out=out_scales,
+                                            dropout=dropout)
         elif H > 1 and gat_fused_shape(H, C) and d.nnz_max > 0 and sch.gat_fused_stats:
             # 2 / 4 / 8 heads: the same launch, a head per group of C / 4 lanes (statistics per head, ReLU in its epilogue)
-            out, m, s = gat_aggregate_fused(d, hfeat, None, C, a_dst, att2, slope, bias=bias, relu=relu, H=H)
+            out, m, s = gat_aggregate_fused(d, hfeat, None, C, a_dst, att2, slope, bias=bias, relu=relu, H=H, dropout=dropout)
         elif H == 1 and C % 4 == 0 and d.nnz_max > 0:
             # the statistics pass leaves the score of every entry; the aggregation reads it back (one coalesced load per
             # 64 entries) instead of gathering a_src[j] per entry and redoing the leaky_relu
@@ -1603,6 +1670,7 @@ class _GatConvFn(torch.autograd.Function):
         ctx.graph, ctx.H, ctx.C, ctx.slope = graph, H, C, float(slope)
         ctx.has_bias = bias is not None
         ctx.sch = sch
+        ctx.dropout = dropout
         ctx.x_scales = xs                                    # (the backward's dW GEMM takes its column scales from them)
         ctx.save_for_backward(x, weight, att2, hfeat, a_dst, a_src, m, s, out,
                               bias if bias is not None else torch.empty(0, device=x.device))
@@ -1642,7 +1710,7 @@ class _GatConvFn(torch.autograd.Function):
             # one head: the by-source row sums of dz (g_src) come out of the same launch
             g_src = torch.empty((N, 1), dtype=torch.float32, device=dev) if (H == 1 and sch.gat_src_rowsum_fused) else None
             dh, dz = gat_backward_fused_packed(sr, grad_out, None, hfeat, C, tpack, a_src, slope, out=dh, H=H, scales_out=dh_scales,
-                                               rowsum_out=g_src)
+                                               rowsum_out=g_src, dropout=ctx.dropout)
             dz = dz.view(-1, H)
             if rank2:
                 return _GatConvFn._backward_rank2(ctx, x, weight, att2, dh, dz, db, C, dh_scales, g_src)
@@ -1680,7 +1748,7 @@ class _GatConvFn(torch.autograd.Function):
         dx = linear_bwd_data(dh, weight, flags=_gflags(sch)) if ctx.needs_input_grad[0] else None
         if overlap:
             main.wait_stream(side)
-        return dx, dw, datt, db, None, None, None, None, None, None, None
+        return dx, dw, datt, db, None, None, None, None, None, None, None, None
 
     @staticmethod
     def _backward_rank2(ctx, x, weight, att2, dh, dz, db, C, dh_scales=None, g_src=None):
@@ -1742,7 +1810,7 @@ class _GatConvFn(torch.autograd.Function):
         datt = gat_rank2_tail(P, weight, A, dw, ctx.needs_input_grad[2])
         if datt is not None:
             datt = datt.view(1, 1, 2 * C)
-        return dx, dw, datt, db, None, None, None, None, None, None, None
+        return dx, dw, datt, db, None, None, None, None, None, None, None, None
 
 
 def _valid_entries(side: CSRSide) -> torch.Tensor:
@@ -1801,7 +1869,11 @@ class _GatDropoutFn(torch.autograd.Function):
         D, db = gat_rowdot_colsum(grad_out, out, bias if ctx.has_bias else None, H, C,
                                   want_colsum=ctx.has_bias and ctx.needs_input_grad[3])
         zeros, ones = torch.zeros((N, H), device=dev), torch.ones((N, H), device=dev)
-        dots = gat_edge_grad(d, hfeat, None, grad_out, H, C, zeros, zeros, zeros, ones, zeros, 1.0, 0)    # <dOut_i, h_j>
+        if C % 4 == 0:
+            dots = gat_edge_grad(d, hfeat, None, grad_out, H, C, zeros, zeros, zeros, ones, zeros, 1.0, 0)    # <dOut_i, h_j>
+        else:                                 # rows that are no multiple of 16 bytes: the per-entry dots of one head at a time
+            dots = torch.stack([edge_dot(d, grad_out[:, h * C:(h + 1) * C], hfeat[:, h * C:(h + 1) * C], graph.num_edges,
+                                         want_entry=True)[0] for h in range(H)], dim=1)
         ri = d.rowidx.long().clamp_(0, max(N - 1, 0))
         zero = torch.zeros((), device=dev)
         gprime = torch.where(e > 0, torch.ones((), device=dev), torch.full((), slope, device=dev))        # e = leaky_relu(z)
@@ -1815,26 +1887,43 @@ class _GatDropoutFn(torch.autograd.Function):
         for h in range(H):
             blk = slice(h * C, (h + 1) * C)
             segsum(graph, sr, grad_out[:, blk], w=alpha_src[:, h].contiguous(), out=dh[:, blk])
-        gat_rank1_add(dh, g_dst, g_src, att2, H, C)
+        if C % 4 == 0:
+            gat_rank1_add(dh, g_dst, g_src, att2, H, C)
+        else:                                 # (npi_gat_rank1_add works on 16-byte lanes: element-wise here, as the softmax backward)
+            dh.view(N, H, C).add_(g_dst.unsqueeze(-1) * att2[:, :C]).add_(g_src.unsqueeze(-1) * att2[:, C:])
         datt = gat_att_grad(hfeat, g_dst, g_src, H, C).view(1, H, 2 * C) if ctx.needs_input_grad[2] else None
         dw = linear_bwd_weight(x, dh, want_bias=False)[0] if ctx.needs_input_grad[1] else None
         dx = linear_bwd_data(dh, weight) if ctx.needs_input_grad[0] else None
         return dx, dw, datt, db, None, None, None, None
 
 
-def gat_dropout_keep(graph: CSRGraph, heads: int, p: float) -> torch.Tensor:
-    """A fresh ``keep`` array for ``gat_conv(..., keep=)``: Bernoulli(1 - p) / (1 - p) per by-target entry and head (torch's
-    generator: the distribution of ``F.dropout``, not its random bits for a given seed)."""
+def gat_dropout_keep(graph, heads: int, p: float, seed: Optional[int] = None, draw: int = 0, side: str = "by_dst") -> torch.Tensor:
+    """A ``keep`` array for ``gat_conv(..., keep=)``.  ``seed`` None: a fresh one, Bernoulli(1 - p) / (1 - p) per by-target entry
+    and head (torch's generator: the distribution of ``F.dropout``, not its random bits for a given seed).  ``seed`` an int: the
+    mask of ``AttentionDropout(p, seed, draw)`` -- Rule D, what the fused kernels recompute per entry -- written out as
+    ``[nnz_max, heads]`` in the entry order of ``side`` (``"by_dst"`` or ``"by_src"``) of a ``CSRGraph`` or ``BipartiteGraph``
+    (``npi_gat_dropout_keep``); slots behind the last entry hold 0."""
     if not 0.0 <= p < 1.0:
         raise ValueError("gat_dropout_keep: p must be in [0, 1)")
-    d = graph.by_dst
-    return torch.empty((max(d.nnz_max, 1), int(heads)), dtype=torch.float32, device=d.rowptr.device).bernoulli_(1.0 - p).div_(1.0 - p)
+    if seed is None:
+        d = graph.by_dst
+        return torch.empty((max(d.nnz_max, 1), int(heads)), dtype=torch.float32, device=d.rowptr.device).bernoulli_(1.0 - p).div_(1.0 - p)
+    if side not in ("by_dst", "by_src"):
+        raise ValueError(f"gat_dropout_keep: side is 'by_dst' or 'by_src', got {side!r}")
+    rule = AttentionDropout(p, seed, draw)
+    sd: CSRSide = getattr(graph, side)
+    dev = sd.rowptr.device
+    keep = torch.zeros((max(sd.nnz_max, 1), int(heads)), dtype=torch.float32, device=dev)
+    check(load().npi_gat_dropout_keep(ptr(sd.rowptr), ptr(sd.col), ptr(sd.eid), sd.n_rows, sd.nnz_max, int(heads), rule.key,
+                                      _as_i64(rule.threshold), rule.scale, ptr(keep), stream_ptr(dev)), "npi_gat_dropout_keep")
+    return keep
 
 
 def gat_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, att: torch.Tensor,
              bias: Optional[torch.Tensor] = None, heads: int = 1, concat: bool = True,
              negative_slope: float = 0.2, relu: bool = False, schedule: Schedule = DEFAULT,
-             keep: Optional[torch.Tensor] = None, x_scales: Optional[torch.Tensor] = None, return_scales: bool = False):
+             keep: Optional[torch.Tensor] = None, x_scales: Optional[torch.Tensor] = None, return_scales: bool = False,
+             dropout: Optional[AttentionDropout] = None):
     """PyG 1.4.2 ``GATConv.forward`` on MI355X; ``att`` is ``[1, H, 2C]``.  ``relu=True`` (an extension, as in
     ``sage_conv``): ``F.relu(conv(x, edge_index))`` with the ReLU in the aggregation's row epilogue and its backward mask in the
     pass that computes the softmax term -- one head; other shapes apply it as a separate pass.  ``keep``: attention dropout in
@@ -1842,9 +1931,20 @@ def gat_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, att: torch.Tenso
     ``x_scales``: ``row_scales(x)`` -- the projection ``x @ W`` then runs on two fp16 pieces per operand (large graphs; EXPERIMENTS
     A34).  Computed ONCE for a feature matrix that does not change between steps, or taken from the layer in front:
     ``return_scales=True`` returns ``(out, out_scales)`` with the scales of the output's rows written by the aggregation launch
-    itself (one head of 256 channels; otherwise ``out_scales`` is None) -- what the next layer takes as its ``x_scales``."""
+    itself (one head of 256 channels; otherwise ``out_scales`` is None) -- what the next layer takes as its ``x_scales``.
+    ``dropout``: an ``AttentionDropout(p, seed, draw)`` -- attention dropout in training mode as a seeded rule, recomputed per entry
+    INSIDE the fused kernels on the shapes of ``gat_fused_shape`` with the default schedule (every option above keeps working);
+    other shapes and ``gat_fused_stats=False`` take the composed variant under the SAME mask (``gat_dropout_keep(seed=)``)."""
     require_gpu(x, weight, att, bias, x_scales)
     graph = as_graph(edge_index, x.size(0))
+    if dropout is not None:
+        if keep is not None:
+            raise ValueError("gat_conv: keep= and dropout= are two ways to say the mask; pass one")
+        if not isinstance(dropout, AttentionDropout):
+            raise TypeError(f"gat_conv: dropout is an AttentionDropout(p, seed, draw), got {type(dropout).__name__}")
+        H = int(heads)
+        if not (gat_fused_shape(H, weight.size(1) // H) and graph.by_dst.nnz_max > 0 and schedule.gat_fused_stats):
+            keep, dropout = gat_dropout_keep(graph, H, dropout.p, seed=dropout.seed, draw=dropout.draw), None
     if keep is not None:
         out = _GatDropoutFn.apply(x, weight, att, bias if concat else None, graph, heads, negative_slope, keep)
         if not concat:
@@ -1854,10 +1954,10 @@ def gat_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, att: torch.Tenso
         return (out, None) if return_scales else out
     if concat:
         if return_scales:
-            out, sc = _GatConvFn.apply(x, weight, att, bias, graph, heads, negative_slope, relu, schedule, x_scales, True)
+            out, sc = _GatConvFn.apply(x, weight, att, bias, graph, heads, negative_slope, relu, schedule, x_scales, True, dropout)
             return out, (sc if sc.numel() else None)
-        return _GatConvFn.apply(x, weight, att, bias, graph, heads, negative_slope, relu, schedule, x_scales, False)
-    out = _GatConvFn.apply(x, weight, att, None, graph, heads, negative_slope, False, schedule, x_scales, False)
+        return _GatConvFn.apply(x, weight, att, bias, graph, heads, negative_slope, relu, schedule, x_scales, False, dropout)
+    out = _GatConvFn.apply(x, weight, att, None, graph, heads, negative_slope, False, schedule, x_scales, False, dropout)
     out = out.view(x.size(0), heads, -1).mean(dim=1)          # head average (concat=False)
     out = out + bias if bias is not None else out
     out = torch.relu(out) if relu else out
@@ -2067,7 +2167,7 @@ class _GatBipartiteFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_src, x_dst, weight, att, bias, graph: BipartiteGraph, heads: int, slope: float, relu: bool, sch: Schedule,
-                shared: bool):
+                shared: bool, dropout: Optional[AttentionDropout] = None):
         H = int(heads)
         C = weight.size(1) // H
         dev = x_src.device
@@ -2094,15 +2194,18 @@ class _GatBipartiteFn(torch.autograd.Function):
             if relu:
                 out = torch.relu_(out)
         elif H == 1 and C % 4 == 0 and C <= 256 and sch.gat_fused_stats:
-            out, m, s = gat_aggregate_fused(d, h_src, None, C, a_dst, att2, slope, bias=bias, relu=relu)
+            out, m, s = gat_aggregate_fused(d, h_src, None, C, a_dst, att2, slope, bias=bias, relu=relu, dropout=dropout)
         elif H > 1 and gat_fused_shape(H, C) and sch.gat_fused_stats:
-            out, m, s = gat_aggregate_fused(d, h_src, None, C, a_dst, att2, slope, bias=bias, relu=relu, H=H)
+            out, m, s = gat_aggregate_fused(d, h_src, None, C, a_dst, att2, slope, bias=bias, relu=relu, H=H, dropout=dropout)
+        elif dropout is not None:                                # (gat_conv_bipartite refuses these before it gets here)
+            raise NotImplementedError("_GatBipartiteFn: attention dropout runs inside the fused kernels only")
         else:
             m, s = gat_softmax_stats(d, a_dst, a_src, H, slope)
             out = _gat_aggregate(graph, d, h_src, H, C, a_dst, a_src, m, s, slope, False, bias=bias)
             if relu:
                 out = torch.relu_(out)
         ctx.graph, ctx.H, ctx.C, ctx.slope, ctx.sch = graph, H, C, float(slope), sch
+        ctx.dropout = dropout
         ctx.relu, ctx.shared, ctx.has_dst, ctx.has_bias = bool(relu), bool(shared), x_dst is not None, bias is not None
         empty = torch.empty(0, device=dev)
         ctx.save_for_backward(x_src, x_dst if x_dst is not None else empty, weight, att2, h_src, h_dst if h_dst is not None else empty,
@@ -2134,7 +2237,8 @@ class _GatBipartiteFn(torch.autograd.Function):
             if gat_fused_shape(H, C):
                 tpack = gat_pack_targets(a_dst, m, s, D)                                 # [N_dst H, 4], gathered by column id
                 g_src = torch.empty((n_src, 1), dtype=torch.float32, device=dev) if (H == 1 and sch.gat_src_rowsum_fused) else None
-                dh, dz = gat_backward_fused_packed(sr, grad_out, None, h_src, C, tpack, a_src, slope, H=H, rowsum_out=g_src)
+                dh, dz = gat_backward_fused_packed(sr, grad_out, None, h_src, C, tpack, a_src, slope, H=H, rowsum_out=g_src,
+                                                   dropout=ctx.dropout)
                 if g_src is None:
                     g_src = seg_rowsum(sr, dz.view(-1, H), H)
             else:
@@ -2144,7 +2248,7 @@ class _GatBipartiteFn(torch.autograd.Function):
                 dh = _gat_aggregate(graph, sr, grad_out, H, C, a_dst, a_src, m, s, slope, True)
             del dz
             if target_term:
-                dz = gat_edge_grad(d, h_src, None, grad_out, H, C, a_dst, a_src, m, s, D, slope, 0)
+                dz = gat_edge_grad(d, h_src, None, grad_out, H, C, a_dst, a_src, m, s, D, slope, 0, dropout=ctx.dropout)
                 g_dst = seg_rowsum(d, dz, H)
                 del dz
         fl = _gflags(sch)
@@ -2178,17 +2282,19 @@ class _GatBipartiteFn(torch.autograd.Function):
                     dx_dst = linear_bwd_data(dh_dst, weight, flags=fl)
         if datt is not None:
             datt = datt.view(1, H, 2 * C)
-        return dx_src, dx_dst, dw, datt, db, None, None, None, None, None, None
+        return dx_src, dx_dst, dw, datt, db, None, None, None, None, None, None, None
 
 
 def gat_conv_bipartite(x, edge_index, weight: torch.Tensor, att: torch.Tensor, bias: Optional[torch.Tensor] = None, size=None,
                        heads: int = 1, concat: bool = True, negative_slope: float = 0.2, relu: bool = False,
-                       schedule: Schedule = DEFAULT, shared: bool = False):
+                       schedule: Schedule = DEFAULT, shared: bool = False, dropout: Optional[AttentionDropout] = None):
     """PyG 1.4.2 ``GATConv.forward((x_src, x_dst), edge_index, size)``: attention over the edge list AS IT IS (with ``size`` given
     PyG neither removes nor adds self loops), ``edge_index[0]`` indexing ``x_src`` and ``edge_index[1]`` the ``N_dst`` output rows.
     ``x_dst`` None: the score has no target term and ``att[..., :C]`` gets a zero gradient.  ``shared``: ``x_dst`` is ``x_src``
-    itself (a tensor ``x`` with ``size=(N, N)``): projected once.  A target without an in-edge gets ``bias`` (or 0).  No attention
-    dropout.  Gradients: ``x_src``, ``x_dst``, ``weight``, ``att``, ``bias``."""
+    itself (a tensor ``x`` with ``size=(N, N)``): projected once.  A target without an in-edge gets ``bias`` (or 0).
+    ``dropout``: an ``AttentionDropout(p, seed, draw)`` -- attention dropout in training mode under Rule D, inside the fused kernels
+    (the shapes of ``gat_fused_shape`` with ``schedule.gat_fused_stats``; anything else is a ``NotImplementedError``: the pair form
+    has no composed variant).  Gradients: ``x_src``, ``x_dst``, ``weight``, ``att``, ``bias``."""
     who = "gat_conv_bipartite"
     x_src, x_dst, n_src, n_dst = _pair_sizes(x, size, who, edge_index)
     if shared and (x_dst is not None and x_dst is not x_src or n_dst != n_src):
@@ -2208,8 +2314,15 @@ def gat_conv_bipartite(x, edge_index, weight: torch.Tensor, att: torch.Tensor, b
         shared = True
     x_src = _f32c(x_src, "x_src")
     x_dst = None if (shared or x_dst is None) else _f32c(x_dst, "x_dst")
+    if dropout is not None:
+        if not isinstance(dropout, AttentionDropout):
+            raise TypeError(f"{who}: dropout is an AttentionDropout(p, seed, draw), got {type(dropout).__name__}")
+        if not (gat_fused_shape(int(heads), weight.size(1) // int(heads)) and schedule.gat_fused_stats):
+            raise NotImplementedError(f"{who}: attention dropout runs inside the fused kernels, which serve {_GAT_FUSED_SHAPES} "
+                                      f"(with schedule.gat_fused_stats); got heads={int(heads)}, out={weight.size(1) // int(heads)}")
     fused_bias = bias if concat else None
-    out = _GatBipartiteFn.apply(x_src, x_dst, weight, att, fused_bias, graph, heads, negative_slope, relu and concat, schedule, shared)
+    out = _GatBipartiteFn.apply(x_src, x_dst, weight, att, fused_bias, graph, heads, negative_slope, relu and concat, schedule, shared,
+                                dropout)
     if concat:
         return out
     out = out.view(n_dst, int(heads), -1).mean(dim=1)

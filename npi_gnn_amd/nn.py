@@ -23,6 +23,7 @@ from torch import nn
 from torch.nn import Parameter
 
 from . import functional as F_
+from ._draw import next_draw
 from .graph import BipartiteGraph, CSRGraph, GraphBatch, as_graph
 from .schedule import DEFAULT, Schedule
 
@@ -115,14 +116,23 @@ class GATConv(nn.Module):
     """``GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0,
     bias=True)`` (PyG 1.4.2): ``weight [in, heads*out]`` and ``att [1, heads, 2*out]`` glorot,
     ``bias`` zeros (``[heads*out]`` if concat else ``[out]``).  Not used by the reference
-    (BASELINE.json configs[4] only).  ``dropout > 0`` in training mode: the composed variant ``functional._GatDropoutFn`` (square
-    form only; the bipartite form refuses attention dropout in training mode)."""
+    (BASELINE.json configs[4] only).  ``dropout > 0`` in training mode, ``seed=None``: a mask from torch's generator and the composed
+    variant ``functional._GatDropoutFn`` (square form only; the bipartite form refuses attention dropout in training mode).
+    ``seed`` an int (an extension): the mask is Rule D's (``functional.AttentionDropout``), recomputed per entry inside the fused
+    kernels in both forms -- every training-mode forward takes the next number of the module's ``draw`` counter (readable and
+    settable, as ``NegativeSampler.draw``: set it back to replay a step); neither ``seed`` nor ``draw`` is in the ``state_dict``."""
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
-                 negative_slope: float = 0.2, dropout: float = 0.0, bias: bool = True, schedule: Schedule = DEFAULT, **kwargs):
+                 negative_slope: float = 0.2, dropout: float = 0.0, bias: bool = True, schedule: Schedule = DEFAULT,
+                 seed: Optional[int] = None, **kwargs):
         super().__init__()
         if not 0.0 <= dropout < 1.0:
             raise ValueError("GATConv: dropout must be in [0, 1)")
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
+            raise ValueError(f"GATConv: seed is None (torch's generator) or an int, got {seed!r}")
+        self.seed = seed
+        if seed is not None:
+            self.draw = 0                         # the next training-mode forward's draw number
         self.schedule = schedule
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
         self.concat, self.negative_slope, self.dropout = concat, negative_slope, dropout
@@ -149,8 +159,9 @@ class GATConv(nn.Module):
         ``e = leaky_relu(<h_dst[i], att[..., :C]> + <h_src[j], att[..., C:]>)`` (no target term without ``x_dst``), softmax over
         the in-edges of target i, ``out[i] = sum alpha h_src[j]`` -- and a tensor ``x`` with ``size=(N, N)``, ``N = x.size(0)``, which
         is the pair form with ``(x, x)``, projected once: whenever ``size`` is given PyG neither removes nor adds self loops.
-        ``edge_index``: the ``[2, E]`` tensor or a ``BipartiteGraph``.  float32, no ``x_scales`` / ``return_scales``, and no
-        attention dropout in training mode (``eval()`` runs)."""
+        ``edge_index``: the ``[2, E]`` tensor or a ``BipartiteGraph``.  float32, no ``x_scales`` / ``return_scales``; attention
+        dropout in training mode needs the module's ``seed`` (Rule D inside the fused kernels, on the shapes
+        ``functional.gat_fused_shape`` names) -- without one only ``eval()`` runs."""
         if isinstance(x, (tuple, list)) or size is not None:
             if isinstance(x, GraphBatch) or isinstance(edge_index, GraphBatch):
                 raise TypeError("GATConv: a GraphBatch is one id space; `size` belongs to the pair form x = (x_src, x_dst)")
@@ -165,18 +176,19 @@ class GATConv(nn.Module):
                     raise TypeError("GATConv: a CSRGraph holds the self-loop-augmented graph; with `size` the attention runs over the "
                                     "edge list as it is -- pass the [2, E] edge_index or a BipartiteGraph")
                 x, shared = (x, None), True
-            if self.dropout > 0 and self.training:
+            if self.dropout > 0 and self.training and self.seed is None:
                 raise NotImplementedError("GATConv: attention dropout (dropout > 0) in training mode is not implemented for the "
                                           "bipartite form; eval() runs, and the square form (tensor x, size=None) has it")
             return F_.gat_conv_bipartite(x, edge_index, self.weight, self.att, self.bias, size=size, heads=self.heads,
                                          concat=self.concat, negative_slope=self.negative_slope, relu=relu, schedule=self.schedule,
-                                         shared=shared)
+                                         shared=shared, dropout=self._seeded_dropout())
         gb = None
         if isinstance(x, GraphBatch):
             gb = _only_batch(x, edge_index, "GATConv")
             x, edge_index = gb.x, gb.graph()
         keep = None
-        if self.dropout > 0 and self.training:
+        rule = self._seeded_dropout()
+        if self.dropout > 0 and self.training and rule is None:
             # F.dropout(alpha, p, training=True): a fresh mask per entry and head.  The fast kernels never hold alpha (both
             # directions recompute it per entry), so a training step with attention dropout takes the composed variant of the
             # layer (functional._GatDropoutFn); in evaluation dropout is the identity and the layer runs as usual
@@ -184,10 +196,16 @@ class GATConv(nn.Module):
             keep = F_.gat_dropout_keep(edge_index, self.heads, self.dropout)
         out = F_.gat_conv(x, edge_index, self.weight, self.att, self.bias, self.heads, self.concat,
                           self.negative_slope, relu=relu, schedule=self.schedule, keep=keep, x_scales=x_scales,
-                          return_scales=return_scales)
+                          return_scales=return_scales, dropout=rule)
         if gb is not None:
             return (gb.with_x(out[0]), out[1]) if return_scales else gb.with_x(out)
         return out
+
+    def _seeded_dropout(self):
+        """the rule of THIS forward -- ``AttentionDropout(dropout, seed, next draw)`` -- or None (eval, dropout = 0, seed=None)"""
+        if self.seed is None or not self.training or self.dropout <= 0:
+            return None
+        return F_.AttentionDropout(self.dropout, self.seed, next_draw(self, None))
 
     def __repr__(self):
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads})"
