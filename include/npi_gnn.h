@@ -1016,6 +1016,82 @@ int npi_pair_score(const int64_t* src, const int64_t* dst, int64_t M, int64_t n_
                    float* loss, void* partials, int64_t partials_bytes, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The variational half of PyG 1.4.2 `torch_geometric/nn/models/autoencoder.py` (VGAE / ARGVA):
+ *     VGAE.reparametrize : mu + torch.randn_like(logvar) * torch.exp(0.5 * logvar)                     (training mode)
+ *     VGAE.kl_loss       : -0.5 * torch.mean(torch.sum(1 + logvar - mu**2 - logvar.exp(), dim=1)),  logvar.clamp(max=MAX_LOGVAR)
+ * some ten elementwise passes over [N, F] tables, a saved randn and a saved exp tensor, and torch's stateful generator -- here ONE
+ * launch forward and ONE backward.  The noise is a pure function of (seed, draw, tick, table, row, column), recomputed in the
+ * backward as Rule D's mask is: no eps and no sigma array exist, and a step is reproducible from (seed, draw, tick).
+ *
+ * Rule N (the seeded standard normal; the counter-based generator of the other rules, npi_gnn_amd/csrc/draw.h, then Box-Muller in
+ * npi_gnn_amd/csrc/gauss.h; wrapping uint64 throughout, G = 0x9E3779B97F4A7C15, C = 0xD6E8FEB86659FD93):
+ *     key    = epoch_seed(seed, draw)                          as every other rule (npi_sample_select's description)
+ *     root   = mix64(mix64(key) + 7 G)                         draw_root(key, DRAW_RULE_N)
+ *     root_t = mix64(root + G (tick + 1))                      draw_word(root, tick + 1); tick = 0 when no tick word is given
+ *     slot   = table * 2^32 + row                              table: 0 (one id space, or z_src), 1 (z_dst); 0 <= row < 2^31 - 1
+ *     w_p    = mix64(mix64(root_t ^ (slot C)) + G (p + 1))     draw_word(draw_stream(root_t, slot), p + 1); p = column >> 1
+ *     u1     = float32((w_p >> 40) + 1) * 2^-24                in (0, 1]: exact
+ *     u2     = float32((w_p >> 16) & 0xFFFFFF) * 2^-24         in [0, 1): exact
+ *     theta  = float32(0x40C90FDB) * u2                        ONE f32 multiply by float32(2 pi)
+ *     r      = sqrt(-2 ln u1)
+ *     eps    = r cos(theta) for an even column, r sin(theta) for an odd one       (Box-Muller; one word serves two columns)
+ * Everything up to theta is exact and bit-identical on the device; ln, cos and sin are defined by their mathematical values at the
+ * f32 inputs u1 and theta, and the device evaluates them with the full-precision logf / sincosf / sqrtf (never the hardware
+ * approximations): |eps_device - eps| <= 16 * 2^-24 * max(1, |eps|).  |eps| <= sqrt(48 ln 2) = 5.77.
+ * `tick` is an optional DEVICE int64 word the kernel reads.  Every other rule bakes its key into the launch by value, so a captured
+ * step replays the same draw; noise that must be fresh on every replay of a HIP graph counts the word up inside the graph
+ * (`tick.add_(1)`), with nothing read back.  The forward and its backward must see the same value of the word.
+ * In numpy (uint64 arrays wrap), eps in float64:
+ *     def mix64(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)
+ *     root_t = mix64(mix64(mix64(uint64(key)) + 7 * G) + G * (tick + 1));  stream = mix64(root_t ^ ((table * 2**32 + row) * C))
+ *     w = mix64(stream[:, None] + G * (arange(ceil(F / 2)) + 1));  u1 = float32((w >> 40) + 1) * float32(2**-24)
+ *     theta = float32(2 * pi) * (float32((w >> 16) & 0xFFFFFF) * float32(2**-24));  r = sqrt(-2 * log(float64(u1)))
+ *     eps[:, 0::2], eps[:, 1::2] = r * cos(float64(theta)), r * sin(float64(theta))            (the last odd column cut off)
+ * Known answers (seed 0, draw 0): key = 0xe220a8397b1dcdaf, root = 0x17b5b595bf33339a, root_t = 0xa7ef72c3db16c2d7 (tick 0),
+ * 0xa8877caa7f09cab9 (tick 1); tick 0: table 0 row 0 words p = 0, 1: 0x889234032688d558, 0x069a7caf18ce8061; table 0 row 1:
+ * 0x205b65805dff0d2e, 0x01ca425f2169d826; table 1 row 0 word 0: 0xe4e0adf25a413b08;
+ * eps[0, 0:4] = 1.1176605005754783, 0.08659600134496356, -1.0901547752580947, -2.475222608957373.
+ *
+ *   mu, logvar : f32 [N, F] with leading dimensions ld_mu, ld_lv (elements, >= F): the two halves of ONE [N, 2 F] encoder output are
+ *                passed as they are (ld = 2 F, the second base F floats on).  16-byte lanes when F % 4 == 0 and every base and
+ *                pitch of the call is 16-byte aligned, else one float per access; a lane owns four columns (two words) either way
+ *   n_total    : the node count the mean runs over: N, or n_src + n_dst when the call is one table of a pair
+ *   key, tick, table : the rule's arguments; tick a device int64* or NULL
+ *   flags      : NPI_GAUSS_SAMPLE (write z), NPI_GAUSS_KL (write kl), or both
+ *   lv = min(logvar, max_logvar);   z = fmaf(eps, expf(0.5f * lv), mu)   [N, F], ld_z
+ *   kl [1]     : -0.5 / n_total * sum over all elements of (1 + lv - mu^2 - exp(lv)).  A DETERMINISTIC sum (npi_pair_score's scheme):
+ *                f32 terms, one fp64 partial per tile of NPI_GAUSS_TILE element slots -- the groups of four columns (the last of a
+ *                row padded with zero terms) in row-major order, 1024 groups per tile: a function of N and F alone, not of the
+ *                grid, the pitches or the lane width -- then a second one-workgroup launch that adds the partials in a fixed
+ *                order.  No float atomics.  Needs `partials`: npi_gauss_workspace_bytes(N, F) bytes, 16-byte aligned, caller-owned
+ *   npi_gauss_sample_kl_bwd : regenerates eps;  c = g_kl[0] / n_total (g_kl a DEVICE f32 word);
+ *                d_mu = g_z + c mu;   d_logvar = [logvar <= max_logvar] (g_z * 0.5 * eps * sigma - 0.5 * c * (1 - exp(lv))).
+ *                A part is present when its flag is set AND its pointer (g_z / g_kl) is not NULL; a missing part contributes 0.
+ *                d_mu or d_logvar may be NULL (not wanted), not both
+ *   npi_gauss_noise : eps [N, F] itself, for tests and for variants composed from other calls (as npi_gat_dropout_keep for Rule D)
+ * f32 only.  Nothing is allocated, nothing read back: the calls may run inside a stream capture.  N == 0 returns NPI_OK without a
+ * launch; kl[0], if asked for, is then set to 0 by a hipMemsetAsync on `stream`.  Refused with NPI_ERR_ARG before any launch: N or
+ * n_total outside [0, 2^31 - 1), F outside [1, 2^31 - 1), more than 2^31 - 2 tiles, a leading dimension below F, n_total < N, or
+ * n_total < 1 with N > 0; unknown or empty flags; table outside {0, 1}; NPI_GAUSS_KL without kl / partials, or partials misaligned
+ * or shorter than npi_gauss_workspace_bytes(N, F); NPI_GAUSS_SAMPLE without z; a null table (or both of d_mu, d_logvar null) with
+ * N > 0.  npi_gauss_workspace_bytes returns -1 for a bad size.
+ *
+ * Out of scope: bf16 tables, any distribution other than N(0, 1), antithetic or quasi-random draws, multi-GPU.
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_GAUSS_SAMPLE 1
+#define NPI_GAUSS_KL 2
+#define NPI_GAUSS_TILE 4096
+int64_t npi_gauss_workspace_bytes(int64_t N, int64_t F);   /* -1: bad size */
+int npi_gauss_sample_kl(const float* mu, int64_t ld_mu, const float* logvar, int64_t ld_lv, int64_t N, int64_t F, int64_t n_total,
+                        float max_logvar, int64_t key, const int64_t* tick /* device word, or NULL */, int table, int flags, float* z,
+                        int64_t ld_z, float* kl /* [1] */, void* partials, int64_t partials_bytes, void* stream);
+int npi_gauss_sample_kl_bwd(const float* mu, int64_t ld_mu, const float* logvar, int64_t ld_lv, int64_t N, int64_t F,
+                            int64_t n_total, float max_logvar, int64_t key, const int64_t* tick, int table, int flags,
+                            const float* g_z, int64_t ld_gz, const float* g_kl /* device f32[1], or NULL */, float* d_mu,
+                            int64_t ld_dmu, float* d_logvar, int64_t ld_dlv, void* stream);
+int npi_gauss_noise(int64_t N, int64_t F, int64_t key, const int64_t* tick, int table, float* eps, int64_t ld, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Ranking metrics: the evaluation half of link prediction.  Replaces what PyG 1.4.2 `GAE.test` and the reference's ROC / PR
  * figures (src/compare_withKmer_noKmer.py:20-54) do on the host through sklearn: `roc_auc_score`, `average_precision_score`,
  * `roc_curve` and `precision_recall_curve` of M scores -- all four are functions of `_binary_clf_curve`, which this entry point

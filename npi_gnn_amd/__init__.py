@@ -8,14 +8,14 @@ be imported.
 """
 from ._lib import LIB_PATH, NpiError, load  # noqa: F401
 from .graph import BipartiteGraph, CSRGraph, GraphBatch, as_graph, set_debug  # noqa: F401
-from .functional import (GCNNorm, gat_conv, gat_conv_bipartite, gcn_conv, link_loss, pair_scores, sage_conv,  # noqa: F401
-                         sage_conv_bipartite, segsum)
+from .functional import (GCNNorm, GaussianNoise, gat_conv, gat_conv_bipartite, gaussian_noise, gcn_conv, link_loss,  # noqa: F401
+                         pair_scores, reparametrize_kl, sage_conv, sage_conv_bipartite, segsum)
 from .nn import GATConv, GCNConv, SAGEConv  # noqa: F401
 from .schedule import Schedule  # noqa: F401
 from .graphed import GraphedStack  # noqa: F401
 from .sampler import Block, DataFlow, NeighborSampler, SubgraphBatch  # noqa: F401
 from .negative import NegativeSampler, negative_sampling, structured_negative_sampling  # noqa: F401
-from .autoencoder import GAE, InnerProductDecoder  # noqa: F401
+from .autoencoder import ARGA, ARGVA, GAE, VGAE, InnerProductDecoder  # noqa: F401
 from .walk import Node2Vec, RandomWalker, random_walk  # noqa: F401
 from .rank import average_precision_score, precision_recall_curve, rank_metrics, roc_auc_score, roc_curve  # noqa: F401
 from .split import EdgeSplitter, to_undirected, train_test_split_edges  # noqa: F401
@@ -24,6 +24,6 @@ from .link_rank import LinkRanks, link_ranks, ranking_metrics  # noqa: F401
 
 __all__ = ["CSRGraph", "GraphBatch", "as_graph", "set_debug", "GCNNorm", "gat_conv", "gcn_conv", "sage_conv", "segsum",
            "GATConv", "GCNConv", "SAGEConv", "Schedule", "GraphedStack", "NeighborSampler", "DataFlow", "Block", "SubgraphBatch", "NegativeSampler", "negative_sampling",
-           "structured_negative_sampling", "InnerProductDecoder", "GAE", "RandomWalker", "random_walk", "Node2Vec", "pair_scores", "link_loss", "rank_metrics",
+           "structured_negative_sampling", "InnerProductDecoder", "GAE", "VGAE", "ARGA", "ARGVA", "GaussianNoise", "gaussian_noise", "reparametrize_kl", "RandomWalker", "random_walk", "Node2Vec", "pair_scores", "link_loss", "rank_metrics",
            "roc_auc_score", "average_precision_score", "roc_curve", "precision_recall_curve", "EdgeSplitter",
            "train_test_split_edges", "to_undirected", "KnownLinks", "topk_links", "LinkRanks", "link_ranks", "ranking_metrics", "NpiError", "load", "LIB_PATH"]

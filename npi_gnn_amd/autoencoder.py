@@ -8,12 +8,19 @@
     prob, ids = model.predict(z, k, pos_edge_index)            # [R, k] each: the k most likely NEW links of every source row
     m = model.test_ranking(z, test_edge_index, pos_edge_index)  # filtered MRR / mean rank / Hits@K of held-out links
 
+    model = npi.VGAE(encoder, seed=0)                          # the encoder returns (mu, logvar)
+    z = model.encode(x, edge_index)                            # training mode: mu + eps * exp(0.5 * logvar), eps seeded (Rule N)
+    loss = model.recon_loss(z, pos_edge_index) + model.kl_loss() / num_nodes
+
 ``InnerProductDecoder.forward`` is ``functional.pair_scores`` (one launch over the pair list, no sort), ``GAE.recon_loss`` is
 ``functional.link_loss`` (one forward launch, no logits written; the backward is the layers' own aggregation: no float atomics,
 bitwise reproducible), ``GAE.test`` is ``rank.rank_metrics`` (ROC-AUC and average precision of the decoder's outputs: one device
 sort, no copy to the host).  ``InnerProductDecoder.forward_all`` -- the dense ``[N, N]`` product -- is not provided:
 ``InnerProductDecoder.topk`` / ``GAE.predict`` (``topk.topk_links``) give each row's best ``k`` of it without the matrix, and
 ``InnerProductDecoder.ranks`` / ``GAE.test_ranking`` (``link_rank.link_ranks``) the rank of a held-out link within it.
+``VGAE.encode`` is ``functional.reparametrize_kl``: the sample and the KL term from one launch, the noise a pure function of ``(seed,
+draw, tick, table, row, column)`` that the backward recomputes, so a VGAE step is as reproducible as a GAE step.  ``ARGA`` / ``ARGVA``
+add PyG's adversarial regulariser as torch compositions over the user's discriminator.
 CPU tensors raise ``NpiError``: there is no CPU path.
 """
 from __future__ import annotations
@@ -132,3 +139,105 @@ class GAE(nn.Module):
         k, ...)`` shows the true partner within its ``k`` slots.  The inner product is scored whatever the decoder."""
         one = isinstance(z, torch.Tensor) or (isinstance(z, (tuple, list)) and len(z) == 2 and z[0] is z[1])
         return ranking_metrics(z, pos_edge_index, exclude=known_edge_index, ks=ks, ties=ties, allow_loops=not one)
+
+
+MAX_LOGVAR = 10
+EPS = 1e-15
+
+
+def _is_pair(t) -> bool:
+    return isinstance(t, (tuple, list)) and len(t) == 2
+
+
+class VGAE(GAE):
+    """PyG 1.4.2 ``VGAE(encoder, decoder=None)``; the encoder returns ``(mu, logvar)`` -- or, from bipartite layers,
+    ``((mu_src, logvar_src), (mu_dst, logvar_dst))``.  ``seed`` and the counter ``draw_noise`` (readable and settable; separate from
+    ``draw``, the negatives' counter) name the noise of a training-mode ``encode``: successive calls draw differently, and a run that
+    starts from the same ``seed`` and ``draw_noise`` repeats bit for bit.  ``tick``: the device word of ``functional.GaussianNoise``,
+    for fresh noise on every replay of a captured step.  Everything of ``GAE`` works on the result."""
+
+    def __init__(self, encoder, decoder=None, seed: int = 0, tick: Optional[torch.Tensor] = None):
+        super().__init__(encoder, decoder)
+        F_.GaussianNoise(seed, 0, tick)                        # the argument checks
+        self.seed, self.tick, self.draw_noise = seed, tick, 0
+        self.__mu__ = self.__logvar__ = self.__kl__ = None
+
+    def reparametrize(self, mu, logvar):
+        """``mu + eps * exp(0.5 * min(logvar, MAX_LOGVAR))`` in training mode -- under draw ``draw_noise``, which then counts up --
+        and ``mu`` in evaluation.  ``mu`` / ``logvar``: tensors, or pairs ``(mu_src, mu_dst)`` / ``(logvar_src, logvar_dst)`` (tables
+        0 and 1 of the rule).  The KL term of the same launch is kept for ``kl_loss()``."""
+        if not self.training:
+            self.__kl__ = None
+            return mu
+        rule = F_.GaussianNoise(self.seed, self.draw_noise, self.tick)
+        self.draw_noise += 1
+        if _is_pair(mu):
+            n_total = int(mu[0].size(0)) + int(mu[1].size(0))
+            z_src, kl_src = F_.reparametrize_kl(mu[0], logvar[0], rule, table=0, n_total=n_total, max_logvar=MAX_LOGVAR)
+            z_dst, kl_dst = F_.reparametrize_kl(mu[1], logvar[1], rule, table=1, n_total=n_total, max_logvar=MAX_LOGVAR)
+            self.__kl__ = kl_src + kl_dst
+            return z_src, z_dst
+        z, self.__kl__ = F_.reparametrize_kl(mu, logvar, rule, max_logvar=MAX_LOGVAR)
+        return z
+
+    def encode(self, *args, **kwargs):
+        """runs the encoder, keeps its ``__mu__`` and ``__logvar__`` (as the encoder returned them: the clamp at ``MAX_LOGVAR``
+        happens inside the kernels) and returns ``reparametrize`` of them"""
+        out = self.encoder(*args, **kwargs)
+        if not _is_pair(out):
+            raise TypeError("VGAE: the encoder returns (mu, logvar), or ((mu_src, logvar_src), (mu_dst, logvar_dst))")
+        if _is_pair(out[0]):
+            if not _is_pair(out[1]):
+                raise TypeError("VGAE: the encoder returns (mu, logvar), or ((mu_src, logvar_src), (mu_dst, logvar_dst))")
+            (mu_src, lv_src), (mu_dst, lv_dst) = out
+            self.__mu__, self.__logvar__ = (mu_src, mu_dst), (lv_src, lv_dst)
+        else:
+            self.__mu__, self.__logvar__ = out
+        return self.reparametrize(self.__mu__, self.__logvar__)
+
+    def kl_loss(self, mu=None, logvar=None) -> torch.Tensor:
+        """PyG's ``kl_loss``: ``-0.5 * mean(sum(1 + logvar - mu**2 - logvar.exp(), dim=1))`` with ``logvar`` clamped at
+        ``MAX_LOGVAR`` -- without arguments the term of the last ``encode`` (from its own launch in training mode), with arguments
+        a KL-only launch over them (tensors or pairs, the mean over all rows)."""
+        if mu is None and logvar is None and self.__kl__ is not None:
+            return self.__kl__
+        mu = self.__mu__ if mu is None else mu
+        logvar = self.__logvar__ if logvar is None else logvar
+        if mu is None or logvar is None:
+            raise ValueError("VGAE.kl_loss: no mu / logvar given and none kept by an encode()")
+        if _is_pair(mu):
+            n_total = int(mu[0].size(0)) + int(mu[1].size(0))
+            return sum(F_.reparametrize_kl(m, lv, table=t, n_total=n_total, max_logvar=MAX_LOGVAR, sample=False)[1]
+                       for t, (m, lv) in enumerate(zip(mu, logvar)))
+        return F_.reparametrize_kl(mu, logvar, max_logvar=MAX_LOGVAR, sample=False)[1]
+
+
+class ARGA(GAE):
+    """PyG 1.4.2 ``ARGA(encoder, discriminator, decoder=None)``: ``GAE`` plus the adversarial regulariser, torch compositions over
+    the user's ``discriminator`` (a module from ``z`` to one logit per row)."""
+
+    def __init__(self, encoder, discriminator, decoder=None, **kwargs):
+        super().__init__(encoder, decoder, **kwargs)
+        self.discriminator = discriminator
+        _reset(self.discriminator)
+
+    def reset_parameters(self) -> None:
+        super().reset_parameters()
+        _reset(self.discriminator)
+
+    def reg_loss(self, z: torch.Tensor) -> torch.Tensor:
+        real = torch.sigmoid(self.discriminator(z))
+        return -torch.log(real + EPS).mean()
+
+    def discriminator_loss(self, z: torch.Tensor) -> torch.Tensor:
+        real = torch.sigmoid(self.discriminator(torch.randn_like(z)))
+        fake = torch.sigmoid(self.discriminator(z.detach()))
+        return -torch.log(real + EPS).mean() - torch.log(1 - fake + EPS).mean()
+
+
+class ARGVA(ARGA, VGAE):
+    """PyG 1.4.2 ``ARGVA(encoder, discriminator, decoder=None)``: ``ARGA`` with ``VGAE``'s ``encode`` / ``reparametrize`` /
+    ``kl_loss`` (and its ``seed`` / ``tick``)."""
+
+    def __init__(self, encoder, discriminator, decoder=None, seed: int = 0, tick: Optional[torch.Tensor] = None):
+        super().__init__(encoder, discriminator, decoder, seed=seed, tick=tick)

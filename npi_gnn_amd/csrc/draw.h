@@ -21,6 +21,7 @@ enum DrawRule : uint64_t {
     DRAW_RULE_W_NEG = 4,                                   // Rule W's negatives of the pair list     (npi_walk_pairs)
     DRAW_RULE_S = 5,                                       // Rule S: the order of a split            (npi_split_permute)
     DRAW_RULE_D = 6,                                       // Rule D: the attention-dropout mask      (npi_gat_*_dropout)
+    DRAW_RULE_N = 7,                                       // Rule N: the standard normal, gauss.h      (npi_gauss_*)
 };
 
 __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {

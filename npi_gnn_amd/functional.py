@@ -17,7 +17,7 @@ import torch
 
 from ._draw import epoch_seed
 from ._lib import (NPI_BF16, NPI_F32, NPI_GEMM_A_ZERO_PADDED, NPI_GEMM_EXACT_F32, NPI_GEMM_RESERVE_CUS, NPI_GEMM_SPLIT_F16X2,
-                   NPI_GEMM_WORKSPACE_PREPARED, NPI_PAIR_LOGITS, NPI_PAIR_LOSS_BCE, NPI_PAIR_LOSS_GAE, NPI_PREPARE_F16X2, check, load, ptr,
+                   NPI_GEMM_WORKSPACE_PREPARED, NPI_GAUSS_KL, NPI_GAUSS_SAMPLE, NPI_PAIR_LOGITS, NPI_PAIR_LOSS_BCE, NPI_PAIR_LOSS_GAE, NPI_PREPARE_F16X2, check, load, ptr,
                    require_gpu, stream_ptr)
 from .graph import BipartiteGraph, CSRGraph, CSRSide, GraphBatch, HubPlan, as_graph, build_side, note_status, pair_list_side
 from .schedule import DEFAULT, Schedule
@@ -2552,3 +2552,161 @@ def link_loss(z, pos_edge_index, neg_edge_index=None, loss: str = "gae", num_pos
         pairs = _PairList(torch.cat([pos_edge_index, neg_edge_index], 1), n_src, n_dst, who)
     require_gpu(z_src, z_dst, pairs.src)
     return _LinkLossFn.apply(z_src, z_dst, pairs, n_pos, PAIR_LOSSES[loss])
+
+
+# ---- VGAE: the seeded reparametrisation and the KL term (``csrc/gauss.hip``) ---------------------------------------
+# PyG's ``mu + randn_like(logvar) * exp(0.5 * logvar)`` and ``-0.5 * mean(sum(1 + logvar - mu**2 - logvar.exp(), 1))`` in ONE launch
+# forward and ONE backward.  The noise is Rule N, a pure function of ``(seed, draw, tick, table, row, column)`` that the backward
+# recomputes -- as Rule D's mask is recomputed -- so no ``eps`` and no ``sigma`` tensor is saved; the KL term is a deterministic fp64
+# sum (``npi_pair_score``'s scheme), so a VGAE step is bitwise reproducible.
+@dataclass(frozen=True, eq=False)
+class GaussianNoise:
+    """The host side of Rule N (``include/npi_gnn.h``), the seeded standard normal: ``eps[row, column]`` of a table is a pure function
+    of ``(seed, draw, tick, table, row, column)``.  ``tick``: None, or a one-element int64 DEVICE tensor that the kernels read -- the
+    key travels by value, so a captured step replays the same draw; a caller that wants fresh noise on every replay of a HIP graph
+    counts the word up inside the graph (``tick.add_(1)``)."""
+    seed: int
+    draw: int = 0
+    tick: Optional[torch.Tensor] = None
+
+    def __post_init__(self):
+        for name in ("seed", "draw"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"GaussianNoise: {name} must be an int, got {v!r}")
+        if self.draw < 0:
+            raise ValueError(f"GaussianNoise: draw must be >= 0, got {self.draw!r}")
+        t = self.tick
+        if t is not None:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.numel() != 1:
+                raise ValueError("GaussianNoise: tick is None or a one-element int64 device tensor")
+            require_gpu(t)
+
+    @property
+    def key(self) -> int:
+        """the ``key`` of the C ABI: ``epoch_seed(seed, draw)``, as every other seeded rule"""
+        return epoch_seed(self.seed, self.draw)
+
+
+def _gauss_table(table) -> int:
+    if isinstance(table, bool) or table not in (0, 1):
+        raise ValueError(f"table is 0 (one id space, or z_src) or 1 (z_dst), got {table!r}")
+    return int(table)
+
+
+def _gauss_rule(rule, who: str) -> GaussianNoise:
+    if not isinstance(rule, GaussianNoise):
+        raise TypeError(f"{who}: rule must be a GaussianNoise(seed, draw, tick), got {type(rule).__name__}")
+    return rule
+
+
+def gaussian_noise(N: int, F: int, rule: GaussianNoise, table: int = 0, device=None) -> torch.Tensor:
+    """``eps [N, F]`` float32 of Rule N itself (``npi_gauss_noise``): what ``reparametrize_kl`` draws under the same ``rule`` and
+    ``table``, for tests and for variants composed from torch operations.  ``device``: where to write (default: the tick's, else
+    ``cuda``)."""
+    who = "gaussian_noise"
+    rule, table = _gauss_rule(rule, who), _gauss_table(table)
+    for v, name in ((N, "N"), (F, "F")):
+        if isinstance(v, bool) or not isinstance(v, int) or v < (1 if name == "F" else 0) or v >= _PAIR_LIMIT:
+            raise ValueError(f"{who}: {name} is an int in [{1 if name == 'F' else 0}, 2^31 - 1), got {v!r}")
+    dev = torch.device(device) if device is not None else (torch.device("cuda") if rule.tick is None else rule.tick.device)
+    eps = torch.empty((N, F), dtype=torch.float32, device=dev)
+    require_gpu(eps, rule.tick)
+    check(load().npi_gauss_noise(N, F, rule.key, ptr(rule.tick), table, ptr(eps), F, stream_ptr(eps.device)), "npi_gauss_noise")
+    return eps
+
+
+def _gauss_tables(mu, logvar, who: str):
+    for t, name in ((mu, "mu"), (logvar, "logvar")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name} must be a tensor [N, F]")
+        if t.dim() != 2 or t.size(1) < 1:
+            raise ValueError(f"{who}: {name} must be a [N, F] tensor with F >= 1 (got shape {tuple(t.shape)})")
+        if t.dtype == torch.bfloat16:
+            raise NotImplementedError(f"{who}: float32 tables only (bf16 storage is not implemented)")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{who}: {name} must be float32 (got {t.dtype})")
+    if mu.shape != logvar.shape:
+        raise ValueError(f"{who}: mu is {tuple(mu.shape)}, logvar {tuple(logvar.shape)}")
+    if max(mu.size(0), mu.size(1)) >= _PAIR_LIMIT:
+        raise ValueError(f"{who}: rows and width stay below 2^31 - 1")
+
+
+class _ReparamKlFn(torch.autograd.Function):
+    """``(z, kl)`` of one ``npi_gauss_sample_kl`` launch (``kl`` alone when ``sample`` is False).  The backward is one
+    ``npi_gauss_sample_kl_bwd`` launch that regenerates the noise; it keeps ``mu``, ``logvar`` and a copy of the tick word, and an
+    output nobody differentiates costs nothing in it."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, rule: Optional[GaussianNoise], table: int, n_total: int, max_logvar: float, sample: bool):
+        tick = rule.tick if sample else None
+        dev = require_gpu(mu, logvar, tick)
+        mu_, lv_ = _pitched(mu), _pitched(logvar)
+        N, F = int(mu.size(0)), int(mu.size(1))
+        lib = load()
+        z = torch.empty((N, F), dtype=torch.float32, device=dev) if sample else None
+        kl = torch.empty((), dtype=torch.float32, device=dev)
+        ws = torch.empty(int(lib.npi_gauss_workspace_bytes(N, F)), dtype=torch.uint8, device=dev)
+        key = rule.key if sample else 0
+        flags = NPI_GAUSS_KL | (NPI_GAUSS_SAMPLE if sample else 0)
+        check(lib.npi_gauss_sample_kl(ptr(mu_), mu_.stride(0), ptr(lv_), lv_.stride(0), N, F, n_total, max_logvar, key, ptr(tick), table,
+                                      flags, ptr(z), F, ptr(kl), ptr(ws), int(ws.numel()), stream_ptr(dev)), "npi_gauss_sample_kl")
+        # the backward redraws under the tick the forward saw, whatever the caller has counted since
+        keep_tick = tick is not None and any(ctx.needs_input_grad[:2])
+        ctx.call = (key, tick.clone() if keep_tick else None, table, n_total, max_logvar, sample)
+        ctx.save_for_backward(mu_, lv_)
+        ctx.set_materialize_grads(False)
+        return (z, kl) if sample else kl
+
+    @staticmethod
+    def backward(ctx, *grads):
+        key, tick, table, n_total, max_logvar, sample = ctx.call
+        g_z, g_kl = grads if sample else (None, grads[0])
+        want_mu, want_lv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if (g_z is None and g_kl is None) or not (want_mu or want_lv):
+            return (None,) * 7
+        mu, logvar = ctx.saved_tensors
+        N, F = int(mu.size(0)), int(mu.size(1))
+        g_z = None if g_z is None else _pitched(g_z)
+        g_kl = None if g_kl is None else g_kl.to(torch.float32).reshape(1)
+        dev = mu.device
+        # without a KL gradient d mu IS g_z: nothing to write
+        d_mu = torch.empty((N, F), dtype=torch.float32, device=dev) if (want_mu and g_kl is not None) else None
+        d_lv = torch.empty((N, F), dtype=torch.float32, device=dev) if want_lv else None
+        if N > 0 and (d_mu is not None or d_lv is not None):
+            flags = (NPI_GAUSS_SAMPLE if g_z is not None else 0) | (NPI_GAUSS_KL if g_kl is not None else 0)
+            check(load().npi_gauss_sample_kl_bwd(ptr(mu), mu.stride(0), ptr(logvar), logvar.stride(0), N, F, n_total, max_logvar, key,
+                                                 ptr(tick), table, flags, ptr(g_z), 0 if g_z is None else g_z.stride(0), ptr(g_kl),
+                                                 ptr(d_mu), F, ptr(d_lv), F, stream_ptr(dev)), "npi_gauss_sample_kl_bwd")
+        if want_mu and g_kl is None:
+            d_mu = g_z
+        return d_mu, d_lv, None, None, None, None, None
+
+
+def reparametrize_kl(mu: torch.Tensor, logvar: torch.Tensor, rule: Optional[GaussianNoise] = None, table: int = 0,
+                     n_total: Optional[int] = None, max_logvar: float = 10.0, sample: bool = True):
+    """PyG 1.4.2 ``VGAE.reparametrize`` and ``VGAE.kl_loss`` in one launch: ``(z, kl)`` with ``lv = min(logvar, max_logvar)``,
+
+    ``z = mu + eps * exp(0.5 * lv)`` -- ``eps`` Rule N under ``rule`` (a ``GaussianNoise``) and ``table`` (0: one id space or the source
+    table, 1: the target table of a pair) -- and ``kl = -0.5 / n_total * sum(1 + lv - mu**2 - exp(lv))``, a 0-d float32 tensor;
+    ``n_total``: the node count of the mean (default ``N``; ``n_src + n_dst`` when the call is one table of a pair).
+    ``sample=False`` (evaluation): ``z`` is ``mu`` itself, nothing is drawn (``rule`` may be None) and the launch computes ``kl`` only.
+
+    ``mu`` / ``logvar`` may be column blocks of one wider tensor (``h[:, :F]``, ``h[:, F:]`` of an encoder with ONE aggregation for
+    both heads): they are read in place.  Gradients: both inputs under any upstream ``(d z, d kl)``, one launch that regenerates
+    ``eps``; an output that is not differentiated costs nothing, and without a ``kl`` gradient ``d mu`` is ``d z`` itself.  A clamped
+    entry (``logvar > max_logvar``) gets ``d logvar = 0``, as ``clamp(max=)`` gives.  float32 only; CPU tensors raise ``NpiError``."""
+    who = "reparametrize_kl"
+    _gauss_tables(mu, logvar, who)
+    table = _gauss_table(table)
+    if sample:
+        rule = _gauss_rule(rule, who)
+    N = int(mu.size(0))
+    n_total = N if n_total is None else n_total
+    if isinstance(n_total, bool) or not isinstance(n_total, int) or n_total < N or n_total >= _PAIR_LIMIT:
+        raise ValueError(f"{who}: n_total is an int in [N, 2^31 - 1), got {n_total!r}")
+    if isinstance(max_logvar, bool) or not isinstance(max_logvar, (int, float)) or max_logvar != max_logvar:
+        raise ValueError(f"{who}: max_logvar must be a number, got {max_logvar!r}")
+    require_gpu(mu, logvar, rule.tick if sample else None)
+    out = _ReparamKlFn.apply(mu, logvar, rule, table, max(n_total, 1), float(max_logvar), bool(sample))
+    return out if sample else (mu, out)
