@@ -1016,6 +1016,75 @@ int npi_pair_score(const int64_t* src, const int64_t* dst, int64_t M, int64_t n_
                    float* loss, void* partials, int64_t partials_bytes, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ranking losses over corrupted targets: the listwise / pairwise sibling of npi_pair_score.  Where npi_pair_score pushes every pair
+ * towards 0 or 1 on its own, these compare a positive with the corrupted targets of the SAME source -- what filtered MRR / Hits@K
+ * (npi_link_ranks) and npi_topk_links measure.  The inputs are what NegativeSampler.corrupt (Rule T, npi_negative_targets),
+ * structured_negative_sampling and npi_topk_links' ids already give; no expanded pair list is written.
+ *
+ * Rule G (the groups):
+ *   src, dst  : int64 [P], the positives;  neg : int64 [P, K] with row pitch ld_neg >= K, 0 <= K <= 63 (may be NULL when K == 0)
+ *   z_src     : f32 [n_src, F], leading dimension ld_src;  z_dst : f32 [n_dst, F], ld_dst; unit column stride, any pitch >= F; they
+ *               may be the same pointer (one id space).  Lane widths as in npi_pair_score
+ *   Group p has C = 1 + K slots: slot 0 is (src_p, dst_p), slot c >= 1 is (src_p, neg[p, c-1]).  The logit of a slot is
+ *   x_{p,c} = <z_src[src_p], z_dst[target]>, in f32 exactly as npi_pair_score forms it: the value depends on the two rows only, not
+ *   on where the group sits in the list or in a wavefront.
+ *   Empty slots and bad ids:  neg[p, c-1] == -1 is an EMPTY slot (what corrupt and npi_topk_links write): no row is read, no status
+ *   raised, logit -inf, coefficient and loss term 0.  Any other negative id outside [0, n_dst) behaves the same and raises
+ *   NPI_STATUS_BAD_PAIR_ID.  A positive whose src or dst is out of range DROPS its whole group and raises the same status: all its
+ *   logits, coefficients and terms are 0.
+ *   With d_c = scale * (x_c - x_0) over the VALID negative slots V_p, terms and coefficients per slot in f32:
+ *     NPI_GROUP_LOSS_BPR     : term softplus(d_c) = max(d, 0) + log1p(exp(-|d|));  loss = sum / (P K);
+ *                              coef_c = scale sigmoid(d_c) / (P K)
+ *     NPI_GROUP_LOSS_MARGIN  : term max(0, margin + d_c);  loss = sum / (P K);  coef_c = scale [margin + d_c > 0] / (P K) -- strictly
+ *                              greater: 0 at the kink
+ *     NPI_GROUP_LOSS_SOFTMAX : (sampled softmax / InfoNCE) per group m + log(exp(-m) + sum_V exp(d_c - m)), m = max(0, max_V d_c);
+ *                              loss = sum_p / P;  coef_c = scale exp(d_c - m) / den / P
+ *   In every form coef_0 = -(sum over c >= 1 of coef_c), added in ascending slot order (never softmax_0 - 1: nothing cancels).
+ *   The divisors count SLOTS (P K, or P), not valid slots -- a deliberate deviation from masking followed by `.mean()`: it needs no
+ *   host read of a device count, so the call may sit in a stream capture.  K == 0, or a group without a valid negative, contributes
+ *   0; P == 0 gives loss 0.  The loss is a DETERMINISTIC sum, npi_pair_score's scheme: f32 terms, fp64 sums in a fixed order, one
+ *   partial per workgroup (4 wavefronts of 64 / C whole groups each), then the one-workgroup sum.  No float atomics.
+ * In numpy (fp64; the device computes logits, terms and coefficients in f32):
+ *     tgt = concatenate([dst[:, None], neg], 1);  keep = (0 <= src) & (src < n_src) & (0 <= dst) & (dst < n_dst)
+ *     valid = keep[:, None] & (0 <= tgt) & (tgt < n_dst);  V = valid.copy();  V[:, 0] = False
+ *     x = where(valid, einsum("pf,pcf->pc", z_src[clip(src, 0, n_src-1)], z_dst[clip(tgt, 0, n_dst-1)]), where(keep[:, None], -inf, 0))
+ *     d = where(V, scale * (x - x[:, :1]), -inf)
+ *     bpr:     loss = where(V, logaddexp(0, d), 0).sum() / (P*K);      coef = where(V, scale / (1 + exp(-d)), 0) / (P*K)
+ *     margin:  loss = where(V, maximum(0, margin + d), 0).sum() / (P*K);  coef = where(V & (margin + d > 0), scale, 0) / (P*K)
+ *     softmax: m = maximum(0, d.max(1, initial=0));  den = exp(-m) + exp(d - m[:, None]).sum(1)
+ *              loss = (m + log(den)).sum() / P;                        coef = scale * exp(d - m[:, None]) / den[:, None] / P
+ *     coef[:, 0] = -coef[:, 1:].sum(1)
+ *
+ *   mode       : NPI_GROUP_LOGITS (logits only) or one of the three loss modes; margin is read by NPI_GROUP_LOSS_MARGIN only
+ *   logits, coef : f32 [P, 1 + K] dense (either may be NULL);  coef = d loss / d logit       (coef: loss modes only)
+ *   loss [1]   : loss modes only; may be NULL; needs `partials`: npi_group_score_workspace_bytes(P, K) bytes, 16-byte aligned,
+ *                caller-owned, fully overwritten
+ *   status     : as npi_pair_score's
+ * Nothing is allocated, nothing read back.  Refused with NPI_ERR_ARG before any launch: an unknown mode; P, F, n_src or n_dst
+ * negative or >= 2^31 - 1 (F < 1); K outside [0, 63]; P (1 + K) >= 2^31 - 1; ld_neg < K; a leading dimension below F; a margin or
+ * scale that is not finite, scale <= 0; no output at all; coef or loss in NPI_GROUP_LOGITS mode; loss without partials, or partials
+ * misaligned or short; a null src / dst / z_src / z_dst (neg when K > 0) when P > 0.  P == 0 returns NPI_OK WITHOUT a kernel
+ * launch; loss[0], if given, is then set to 0 by a hipMemsetAsync on `stream`.  npi_group_score_workspace_bytes returns -1 on a bad
+ * size, else a multiple of 16 that is at least 8.
+ *
+ * The backward is npi_pair_score's: npi_segsum_ex over the sides of the EXPANDED list (src repeated C times; dst and neg
+ * interleaved, empty slots clamped to row 0) with g = coef times the upstream gradient as per-entry weights.  Empty, bad and
+ * dropped slots carry weight exactly 0.  The expanded list exists in the backward only.
+ *
+ * Out of scope: K > 63, bf16 tables, per-slot weights, corrupting the source side (swap the tables), a loss over npi_topk_links'
+ * scores without re-scoring.
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_GROUP_LOGITS 0
+#define NPI_GROUP_LOSS_BPR 1
+#define NPI_GROUP_LOSS_MARGIN 2
+#define NPI_GROUP_LOSS_SOFTMAX 3
+int64_t npi_group_score_workspace_bytes(int64_t P, int64_t K);   /* -1 on a bad size; 16-byte multiple, >= 8 */
+int npi_group_score(const int64_t* src, const int64_t* dst, int64_t P, const int64_t* neg, int64_t ld_neg, int64_t K,
+                    const float* z_src, int64_t ld_src, int64_t n_src, const float* z_dst, int64_t ld_dst, int64_t n_dst, int64_t F,
+                    int mode, float margin, float scale, float* logits /* [P, 1+K] dense */, float* coef /* [P, 1+K] dense */,
+                    float* loss, void* partials, int64_t partials_bytes, int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The variational half of PyG 1.4.2 `torch_geometric/nn/models/autoencoder.py` (VGAE / ARGVA):
  *     VGAE.reparametrize : mu + torch.randn_like(logvar) * torch.exp(0.5 * logvar)                     (training mode)
  *     VGAE.kl_loss       : -0.5 * torch.mean(torch.sum(1 + logvar - mu**2 - logvar.exp(), dim=1)),  logvar.clamp(max=MAX_LOGVAR)

@@ -3,7 +3,8 @@
 There is NO CPU fallback: every wrapper raises if the library is missing or if a tensor is not
 on an AMD GPU.  PyTorch only lends device memory and the current HIP stream.  The link-prediction entry points in the
 order of a run: ``npi_split_*`` (train / val / test parts and folds of the edge list), ``npi_sample_*`` (batches), ``npi_negative_*`` (negatives), ``npi_random_walk`` / ``npi_walk_pairs`` (node2vec
-walks and their skip-gram pair list), ``npi_pair_score`` (scores and loss), ``npi_gauss_*`` (the variational
+walks and their skip-gram pair list), ``npi_pair_score`` (scores and loss), ``npi_group_score`` (ranking losses of every
+positive against its own corrupted targets), ``npi_gauss_*`` (the variational
 sample and its KL term), ``npi_rank_metrics`` (ROC-AUC, average precision and
 the score curve of an evaluation), ``npi_topk_links`` (the k most likely new links of every query row), ``npi_link_ranks`` (the
 filtered rank of every held-out link among the targets its source has no known edge to).
@@ -41,6 +42,10 @@ NPI_STATUS_BAD_LABEL = 2048      # status bit of npi_rank_metrics: a label other
 NPI_PAIR_LOGITS = 0               # modes of npi_pair_score
 NPI_PAIR_LOSS_GAE = 1
 NPI_PAIR_LOSS_BCE = 2
+NPI_GROUP_LOGITS = 0              # modes of npi_group_score
+NPI_GROUP_LOSS_BPR = 1
+NPI_GROUP_LOSS_MARGIN = 2
+NPI_GROUP_LOSS_SOFTMAX = 3
 NPI_GAUSS_SAMPLE = 1              # flags of npi_gauss_sample_kl / _bwd: the reparametrised sample z ...
 NPI_GAUSS_KL = 2                  # ... and the KL term
 NPI_TOPK_MAX = 128               # largest k of npi_topk_links
@@ -186,6 +191,8 @@ PROTOTYPES = {
     "npi_walk_pairs": (c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "npi_pair_score_workspace_bytes": (_I, [_I]),
     "npi_pair_score": (c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, c_int, _P, _P, _P, _P, _I, _P, _P]),
+    "npi_group_score_workspace_bytes": (_I, [_I, _I]),
+    "npi_group_score": (c_int, [_P, _P, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, c_int, c_float, c_float, _P, _P, _P, _P, _I, _P, _P]),
     "npi_gauss_workspace_bytes": (_I, [_I, _I]),
     "npi_gauss_sample_kl": (c_int, [_P, _I, _P, _I, _I, _I, _I, c_float, _I, _P, c_int, c_int, _P, _I, _P, _P, _I, _P]),
     "npi_gauss_sample_kl_bwd": (c_int, [_P, _I, _P, _I, _I, _I, _I, c_float, _I, _P, c_int, c_int, _P, _I, _P, _P, _I, _P, _I, _P]),

@@ -4,6 +4,7 @@
     z = model.encode(x, edge_index)                            # a tensor [N, F], or a pair (z_src, z_dst) from bipartite layers
     loss = model.recon_loss(z, pos_edge_index)                 # negatives drawn on the device, as many as positives
     loss.backward()
+    loss = model.ranking_loss(z, pos_edge_index, num_neg=8, loss="softmax")   # each positive against 8 corrupted targets of its source
     auc, ap = model.test(z, pos_edge_index, neg_edge_index)    # 0-d float64 device tensors: float(auc) is PyG's number
     prob, ids = model.predict(z, k, pos_edge_index)            # [R, k] each: the k most likely NEW links of every source row
     m = model.test_ranking(z, test_edge_index, pos_edge_index)  # filtered MRR / mean rank / Hits@K of held-out links
@@ -15,7 +16,9 @@
 ``InnerProductDecoder.forward`` is ``functional.pair_scores`` (one launch over the pair list, no sort), ``GAE.recon_loss`` is
 ``functional.link_loss`` (one forward launch, no logits written; the backward is the layers' own aggregation: no float atomics,
 bitwise reproducible), ``GAE.test`` is ``rank.rank_metrics`` (ROC-AUC and average precision of the decoder's outputs: one device
-sort, no copy to the host).  ``InnerProductDecoder.forward_all`` -- the dense ``[N, N]`` product -- is not provided:
+sort, no copy to the host).  ``GAE.ranking_loss`` is ``functional.ranking_loss`` (BPR, a margin hinge or the sampled
+softmax of every positive against its own corrupted targets: one forward launch, the same backward).
+``InnerProductDecoder.forward_all`` -- the dense ``[N, N]`` product -- is not provided:
 ``InnerProductDecoder.topk`` / ``GAE.predict`` (``topk.topk_links``) give each row's best ``k`` of it without the matrix, and
 ``InnerProductDecoder.ranks`` / ``GAE.test_ranking`` (``link_rank.link_ranks``) the rank of a held-out link within it.
 ``VGAE.encode`` is ``functional.reparametrize_kl``: the sample and the KL term from one launch, the noise a pure function of ``(seed,
@@ -55,6 +58,12 @@ class InnerProductDecoder(nn.Module):
 
     def forward(self, z, edge_index, sigmoid: bool = True) -> torch.Tensor:
         value = F_.pair_scores(z, edge_index)
+        return torch.sigmoid(value) if sigmoid else value
+
+    def group_scores(self, z, pos_edge_index: torch.Tensor, neg_dst: torch.Tensor, sigmoid: bool = False) -> torch.Tensor:
+        """``functional.group_scores(z, pos_edge_index, neg_dst)``: ``[P, 1 + K]``, column 0 the positive's logit, column ``c`` that
+        of ``(pos_edge_index[0, p], neg_dst[p, c - 1])``; an empty (``-1``) slot holds ``-inf`` (``sigmoid=True``: probability 0)."""
+        value = F_.group_scores(z, pos_edge_index, neg_dst)
         return torch.sigmoid(value) if sigmoid else value
 
     def topk(self, z, k: int, exclude=None, rows: Optional[torch.Tensor] = None, sigmoid: bool = True):
@@ -111,6 +120,33 @@ class GAE(nn.Module):
             neg_edge_index = sampler.pairs(draw=self.draw)
             self.draw += 1
         return F_.link_loss(z, pos_edge_index, neg_edge_index, loss=loss)
+
+    def ranking_loss(self, z, pos_edge_index: torch.Tensor, num_neg: int = 1, loss: str = "bpr", margin: float = 1.0,
+                     scale: float = 1.0, known_edge_index: Optional[torch.Tensor] = None, neg_dst: Optional[torch.Tensor] = None,
+                     seed: int = 0) -> torch.Tensor:
+        """``functional.ranking_loss`` of every positive against ``num_neg`` corrupted targets of its own source (``loss``: ``"bpr"``,
+        ``"margin"`` or ``"softmax"``) -- the objective ``test_ranking`` and ``predict`` measure, where ``recon_loss`` is
+        pointwise.  ``neg_dst=None`` draws them: ``NegativeSampler(known_edge_index, size, seed).corrupt(...)`` (Rule T; targets the
+        source has no edge to in ``known_edge_index``, default ``pos_edge_index``; Rule T knows no loop exclusion) under draw
+        ``self.draw``, which then counts up as in ``recon_loss``.  ``neg_dst [P, K]``: the corrupted targets themselves, e.g. the
+        ids of ``predict`` as hard negatives (``num_neg`` is then not read; no draw is taken)."""
+        if neg_dst is None:
+            z_src, z_dst, n_src, n_dst = F_._pair_tables(z, None, "GAE.ranking_loss")
+            if loss not in F_.GROUP_LOSSES:
+                raise ValueError(f"GAE.ranking_loss: loss is 'bpr', 'margin' or 'softmax', got {loss!r}")
+            num_neg = int(num_neg)
+            if num_neg < 0 or num_neg > F_.GROUP_MAX_K:
+                raise ValueError(f"GAE.ranking_loss: num_neg must lie in [0, {F_.GROUP_MAX_K}], got {num_neg}")
+            if (not isinstance(pos_edge_index, torch.Tensor) or pos_edge_index.dtype != torch.int64 or pos_edge_index.dim() != 2
+                    or pos_edge_index.size(0) != 2):
+                raise ValueError("GAE.ranking_loss: pos_edge_index must be a LongTensor of shape [2, P]")
+            one = z_dst is None
+            known = pos_edge_index if known_edge_index is None else known_edge_index
+            sampler = NegativeSampler(known, n_src if one else (n_src, n_dst), seed=seed, allow_loops=not one)
+            P = int(pos_edge_index.size(1))
+            neg_dst = sampler.corrupt(pos_edge_index[0].repeat_interleave(num_neg), draw=self.draw).view(P, num_neg)
+            self.draw += 1
+        return F_.ranking_loss(z, pos_edge_index, neg_dst, loss=loss, margin=margin, scale=scale)
 
     def test(self, z, pos_edge_index: torch.Tensor, neg_edge_index: torch.Tensor):
         """PyG's ``test(z, pos_edge_index, neg_edge_index)``: ``(auc, ap)`` = ``roc_auc_score`` and ``average_precision_score`` of

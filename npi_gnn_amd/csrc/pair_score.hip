@@ -7,13 +7,13 @@
 // eight at a time -- sixteen gathered rows in flight per lane -- the eight partial dots reduce-scattered over the wave, the 64 logits
 // parked in LDS so that the loss terms, the coefficients d loss / d logit and the stores are lane-parallel again.
 // No float atomics: a wave sums its 64 loss terms in a fixed tree, a workgroup its four waves in order into ONE fp64 partial, and a
-// second, one-workgroup launch adds the partials in a fixed order.  Every output element has one writer.
+// second, one-workgroup launch (loss_sum.h) adds the partials in a fixed order.  Every output element has one writer.
 #include "dot_lanes.h"
+#include "loss_sum.h"
 
 namespace npi {
 
 constexpr int PS_WAVES = 4;                    // wavefronts (blocks of 64 pairs) per workgroup: one partial per 256 pairs
-constexpr int PS_SUM_THREADS = 256;            // the workgroup that adds the partials
 
 // Loss term and d term / d logit of one pair, before the 1 / count of its part.  s = sigmoid(x) in f32 throughout.
 //   GAE: PyG's expressions literally, EPS = 1e-15: a positive -log(s + EPS), a negative -log(1 - s + EPS), and what autograd
@@ -108,21 +108,6 @@ pair_score_kernel(const int64_t* __restrict__ src, const int64_t* __restrict__ d
         __syncthreads();
         if (threadIdx.x == 0) partials[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
     }
-}
-
-// loss[0] = sum of partials[0 .. n) in a fixed order: thread t adds t, t + 256, ... in fp64, then a fixed tree over the workgroup
-__global__ void __launch_bounds__(PS_SUM_THREADS)
-pair_loss_sum_kernel(const double* __restrict__ partials, int n, float* __restrict__ loss) {
-    __shared__ double acc[PS_SUM_THREADS];
-    double v = 0.0;
-    for (int i = threadIdx.x; i < n; i += PS_SUM_THREADS) v += partials[i];
-    acc[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = PS_SUM_THREADS / 2; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s) acc[threadIdx.x] += acc[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = (float)acc[0];
 }
 
 }  // namespace npi

@@ -17,7 +17,8 @@ import torch
 
 from ._draw import epoch_seed
 from ._lib import (NPI_BF16, NPI_F32, NPI_GEMM_A_ZERO_PADDED, NPI_GEMM_EXACT_F32, NPI_GEMM_RESERVE_CUS, NPI_GEMM_SPLIT_F16X2,
-                   NPI_GEMM_WORKSPACE_PREPARED, NPI_GAUSS_KL, NPI_GAUSS_SAMPLE, NPI_PAIR_LOGITS, NPI_PAIR_LOSS_BCE, NPI_PAIR_LOSS_GAE, NPI_PREPARE_F16X2, check, load, ptr,
+                   NPI_GEMM_WORKSPACE_PREPARED, NPI_GAUSS_KL, NPI_GAUSS_SAMPLE, NPI_GROUP_LOGITS, NPI_GROUP_LOSS_BPR, NPI_GROUP_LOSS_MARGIN,
+                   NPI_GROUP_LOSS_SOFTMAX, NPI_PAIR_LOGITS, NPI_PAIR_LOSS_BCE, NPI_PAIR_LOSS_GAE, NPI_PREPARE_F16X2, check, load, ptr,
                    require_gpu, stream_ptr)
 from .graph import BipartiteGraph, CSRGraph, CSRSide, GraphBatch, HubPlan, as_graph, build_side, note_status, pair_list_side
 from .schedule import DEFAULT, Schedule
@@ -2552,6 +2553,174 @@ def link_loss(z, pos_edge_index, neg_edge_index=None, loss: str = "gae", num_pos
         pairs = _PairList(torch.cat([pos_edge_index, neg_edge_index], 1), n_src, n_dst, who)
     require_gpu(z_src, z_dst, pairs.src)
     return _LinkLossFn.apply(z_src, z_dst, pairs, n_pos, PAIR_LOSSES[loss])
+
+
+# ---- ranking losses over corrupted targets (``csrc/group_score.hip``) ------------------------------------------------
+# Rule G (``include/npi_gnn.h``): every positive ``(i, j)`` with its own ``K`` corrupted targets -- ``NegativeSampler.corrupt``,
+# ``structured_negative_sampling`` or the ids of ``topk_links`` -- is one GROUP of ``1 + K`` slots that share the source row.  ONE
+# forward launch scores the groups from ``pos_edge_index`` and ``neg_dst`` as they are and reduces them to BPR, a margin hinge or the
+# sampled softmax; the expanded pair list exists only in the backward, which is ``_pair_grads`` over it.
+GROUP_LOSSES = {"bpr": NPI_GROUP_LOSS_BPR, "margin": NPI_GROUP_LOSS_MARGIN, "softmax": NPI_GROUP_LOSS_SOFTMAX}
+GROUP_MAX_K = 63
+
+
+class _GroupList:
+    """The ``P`` groups of one call: ``src``, ``dst`` contiguous ``[P]`` LongTensors, ``neg`` ``[P, K]`` with unit column stride and
+    row pitch ``ld_neg`` (a view of a wider buffer stays a view), and -- built only when a backward asks -- the expanded
+    ``_PairList`` of the ``P (1 + K)`` slots in slot order, empty and bad slots clamped into the tables (they carry weight 0)."""
+
+    def __init__(self, pos_edge_index, neg_dst, n_src: int, n_dst: int, who: str):
+        if not isinstance(pos_edge_index, torch.Tensor) or not isinstance(neg_dst, torch.Tensor):
+            raise TypeError(f"{who}: pos_edge_index is a LongTensor of shape [2, P], neg_dst one of shape [P, K] (or [P])")
+        if pos_edge_index.dtype != torch.int64 or pos_edge_index.dim() != 2 or pos_edge_index.size(0) != 2:
+            raise ValueError(f"{who}: pos_edge_index must be a LongTensor of shape [2, P] (got {pos_edge_index.dtype} "
+                             f"{tuple(pos_edge_index.shape)})")
+        P = int(pos_edge_index.size(1))
+        if neg_dst.dtype != torch.int64 or neg_dst.dim() not in (1, 2) or neg_dst.size(0) != P:
+            raise ValueError(f"{who}: neg_dst must be a LongTensor of shape [P, K] or [P] with P = {P} (got {neg_dst.dtype} "
+                             f"{tuple(neg_dst.shape)})")
+        if neg_dst.dim() == 1:
+            neg_dst = neg_dst[:, None]
+        K = int(neg_dst.size(1))
+        if K > GROUP_MAX_K:
+            raise ValueError(f"{who}: at most {GROUP_MAX_K} corrupted targets per positive (got K = {K})")
+        if P * (1 + K) >= _PAIR_LIMIT:
+            raise ValueError(f"{who}: more than 2^31 - 2 slots in one call")
+        if K == 0:
+            ld = 0
+        elif (K == 1 or neg_dst.stride(1) == 1) and (P <= 1 or neg_dst.stride(0) >= K):
+            ld = int(neg_dst.stride(0)) if P > 1 else K
+        else:
+            neg_dst, ld = neg_dst.contiguous(), K
+        self.src, self.dst, self.neg, self.ld_neg = pos_edge_index[0].contiguous(), pos_edge_index[1].contiguous(), neg_dst, ld
+        self.n_src, self.n_dst, self.P, self.K = n_src, n_dst, P, K
+        self._pairs = None
+
+    def targets(self) -> torch.Tensor:
+        """``[P, 1 + K]``: the positive's target, then the corrupted ones"""
+        return torch.cat([self.dst[:, None], self.neg], 1)
+
+    def valid(self) -> torch.Tensor:
+        """``[P, 1 + K]`` bool: the slots that read rows (Rule G: neither empty nor bad, in a group that is not dropped)"""
+        tgt = self.targets()
+        keep = (self.src >= 0) & (self.src < self.n_src) & (self.dst >= 0) & (self.dst < self.n_dst)
+        return keep[:, None] & (tgt >= 0) & (tgt < self.n_dst)
+
+    def pairs(self) -> _PairList:
+        if self._pairs is None:
+            C = 1 + self.K
+            src = self.src.repeat_interleave(C).clamp(min=0, max=max(self.n_src - 1, 0))
+            tgt = self.targets().clamp(min=0, max=max(self.n_dst - 1, 0)).flatten()
+            self._pairs = _PairList(torch.stack([src, tgt]), self.n_src, self.n_dst, "ranking_loss")
+        return self._pairs
+
+
+def _group_score_launch(z_src, z_dst, groups: _GroupList, mode: int, margin: float, scale: float, want_logits: bool, want_coef: bool,
+                        want_loss: bool):
+    """one ``npi_group_score`` launch (plus the one-workgroup sum of the partials when the loss is asked for): ``(logits, coef,
+    loss)``, the first two ``[P, 1 + K]``"""
+    dev = require_gpu(z_src, z_dst, groups.src, groups.dst, groups.neg)
+    z_src = _pitched(z_src)
+    z_dst = z_src if z_dst is None else _pitched(z_dst)
+    P, K, lib = groups.P, groups.K, load()
+    f32 = dict(dtype=torch.float32, device=dev)
+    logits = torch.empty((P, 1 + K), **f32) if want_logits else None
+    coef = torch.empty((P, 1 + K), **f32) if want_coef else None
+    loss = torch.empty((), **f32) if want_loss else None
+    ws = torch.empty(int(lib.npi_group_score_workspace_bytes(P, K)), dtype=torch.uint8, device=dev) if want_loss else None
+    if P == 0 and not want_loss:
+        return logits, coef, loss                              # empty outputs (null pointers to the library): nothing to launch
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib.npi_group_score(ptr(groups.src), ptr(groups.dst), P, ptr(groups.neg) if K else 0, groups.ld_neg, K, ptr(z_src),
+                              z_src.stride(0), groups.n_src, ptr(z_dst), z_dst.stride(0), groups.n_dst, z_src.size(1), mode,
+                              float(margin), float(scale), ptr(logits), ptr(coef), ptr(loss), ptr(ws),
+                              0 if ws is None else int(ws.numel()), ptr(status), stream_ptr(dev)), "npi_group_score")
+    note_status(status)
+    return logits, coef, loss
+
+
+class _GroupScoreFn(torch.autograd.Function):
+    """``logits[p, c]`` of Rule G under an arbitrary upstream ``d logits`` (ignored at empty, bad and dropped slots)"""
+
+    @staticmethod
+    def forward(ctx, z_src, z_dst, groups: _GroupList):
+        logits = _group_score_launch(z_src, z_dst, groups, NPI_GROUP_LOGITS, 0.0, 1.0, True, False, False)[0]
+        ctx.groups = groups
+        ctx.save_for_backward(z_src, z_dst)
+        return logits
+
+    @staticmethod
+    def backward(ctx, grad):
+        z_src, z_dst = ctx.saved_tensors
+        groups = ctx.groups
+        g = torch.where(groups.valid(), grad.to(torch.float32), torch.zeros((), dtype=torch.float32, device=grad.device)).flatten()
+        d_src, d_dst = _pair_grads(groups.pairs(), z_src, z_dst, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return d_src, d_dst, None
+
+
+class _RankingLossFn(torch.autograd.Function):
+    """the scalar loss of ``npi_group_score``; ``coef = d loss / d logit`` ``[P, 1 + K]`` comes out of the same launch and is all the
+    backward keeps of it (no logits are written).  Empty, bad and dropped slots hold coefficient exactly 0."""
+
+    @staticmethod
+    def forward(ctx, z_src, z_dst, groups: _GroupList, mode: int, margin: float, scale: float):
+        want_coef = any(ctx.needs_input_grad[:2])
+        _, coef, loss = _group_score_launch(z_src, z_dst, groups, mode, margin, scale, False, want_coef, True)
+        ctx.groups, ctx.coef = groups, coef
+        ctx.save_for_backward(z_src, z_dst)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        z_src, z_dst = ctx.saved_tensors
+        g = (ctx.coef * grad.to(torch.float32)).flatten()
+        d_src, d_dst = _pair_grads(ctx.groups.pairs(), z_src, z_dst, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return d_src, d_dst, None, None, None, None
+
+
+def group_scores(z, pos_edge_index, neg_dst) -> torch.Tensor:
+    """The logits of every positive and of its own corrupted targets, ``[P, 1 + K]`` float32 (Rule G, ``npi_group_score``): column 0
+    is ``<z_src[i], z_dst[j]>`` of the positive ``(i, j) = pos_edge_index[:, p]``, column ``c`` that of ``(i, neg_dst[p, c - 1])``.
+    ``z`` as in ``pair_scores``; ``neg_dst``: ``[P, K]`` int64, ``0 <= K <= 63`` (``[P]`` means ``K = 1``) -- what
+    ``NegativeSampler.corrupt``, ``structured_negative_sampling`` or ``topk_links`` return; a row-pitched view stays a view.  A slot
+    holding ``-1`` is empty: ``-inf``, nothing read, nothing reported.  Any other id outside the target table gives ``-inf`` too and
+    is reported (``graph.check_pending()`` raises ``IndexError``); a positive with an id out of range drops its group: all zeros,
+    reported.  ONE launch that reads each source row once per batch of eight slots, not once per slot.
+
+    Gradients: both tables, under any upstream gradient; the upstream value at an empty, bad or dropped slot is ignored.  The
+    backward is ``pair_scores``' (segmented sums over the expanded list, built there only): no float atomics, bitwise reproducible."""
+    who = "group_scores"
+    z_src, z_dst, n_src, n_dst = _pair_tables(z, None, who)
+    groups = _GroupList(pos_edge_index, neg_dst, n_src, n_dst, who)
+    require_gpu(z_src, z_dst, groups.src, groups.neg)
+    return _GroupScoreFn.apply(z_src, z_dst, groups)
+
+
+def ranking_loss(z, pos_edge_index, neg_dst, loss: str = "bpr", margin: float = 1.0, scale: float = 1.0) -> torch.Tensor:
+    """A ranking loss of the positives ``pos_edge_index [2, P]`` against their own corrupted targets ``neg_dst [P, K]`` as a 0-d
+    float32, in ONE forward launch that writes no logits.  With ``d_c = scale * (x_c - x_0)`` over the valid corrupted slots of a
+    group (``x`` as in ``group_scores``):
+
+    ``loss="bpr"``: ``softplus(d_c)`` -- ``-logsigmoid(scale * (x_pos - x_neg))`` --, summed and divided by ``P K``.
+    ``loss="margin"``: ``max(0, margin + d_c)``, divided by ``P K``; the derivative at the kink is 0.
+    ``loss="softmax"``: the sampled softmax / InfoNCE ``-log softmax(scale * x)[0]`` over the group's valid slots, divided by ``P``.
+
+    The divisors count slots, not valid slots (no device count is read back, so the forward may sit in a stream capture): an empty
+    (``-1``) slot adds 0 where masking followed by ``mean()`` would shrink the divisor.  ``K = 0``, a group without a valid
+    corrupted target, and ``P = 0`` give 0.  ``margin`` is read by ``"margin"`` only.  Gradients: both tables, ``d loss / d
+    logit`` from the forward launch times the upstream gradient as the per-entry weights of the layers' own aggregation over the
+    expanded list -- no float atomics, bitwise reproducible; only the side of a table that requires grad is built, and under
+    ``torch.no_grad()`` nothing is."""
+    who = "ranking_loss"
+    if loss not in GROUP_LOSSES:
+        raise ValueError(f"{who}: loss is 'bpr', 'margin' or 'softmax', got {loss!r}")
+    margin, scale = float(margin), float(scale)
+    if margin != margin or scale != scale or abs(margin) == float("inf") or abs(scale) == float("inf") or scale <= 0:
+        raise ValueError(f"{who}: margin and scale must be finite and scale > 0 (got margin={margin}, scale={scale})")
+    z_src, z_dst, n_src, n_dst = _pair_tables(z, None, who)
+    groups = _GroupList(pos_edge_index, neg_dst, n_src, n_dst, who)
+    require_gpu(z_src, z_dst, groups.src, groups.neg)
+    return _RankingLossFn.apply(z_src, z_dst, groups, GROUP_LOSSES[loss], margin, scale)
 
 
 # ---- VGAE: the seeded reparametrisation and the KL term (``csrc/gauss.hip``; DESIGN.md 3.19) ---------------------------------------
