@@ -1384,6 +1384,58 @@ int npi_link_ranks(const int64_t* src, const int64_t* dst, int64_t Q,
                    int64_t* counts /* [Q, 4] */, float* scores /* [Q] */, void* workspace, int64_t workspace_bytes,
                    int32_t* status, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Max aggregation: the third aggregator of PyG's `MessagePassing` (`add`, `mean`, `max`) -- the pooling aggregator of GraphSAGE.
+ * npi_segmax replaces `scatter_('max', x[col], row, dim_size=N)` inside `MessagePassing.propagate(aggr='max')`, npi_segmax_bwd the
+ * backward of that composition (`index_add_` on float atomics).  Neither writes the [nnz, F] gather, neither uses a float atomic.
+ *
+ * RULE X -- out, arg of a CSR side (rowptr, col, eid, rowidx; items of 64 or 256 entries) and an f32 table x [n_cols, F].
+ *   1. Value.   out[i, c] = the maximum of x[col[p], c] over the entries p of row i.  -0.0 equals +0.0 in this comparison and a
+ *               zero maximum is written as +0.0 (the key of Rule R 1).  A NaN beats every number; what is written is the quiet NaN
+ *               0x7fc00000.  +-inf are ordinary values.
+ *   2. Winner.  arg[i, c] (int32) = eid of the winning entry: the column of edge_index it came from, or -1 for the self loop the
+ *               CSR build appends (eid < 0).  Among equal values -- all NaNs count as equal -- the smallest uint32(eid) wins, so
+ *               the appended loop loses every tie.
+ *   3. Empty.   A row without entries: out = +0.0 (PyG's fill of scatter_('max')), arg = -2.
+ *   4. Padding. Entries at positions >= rowptr[N] (up to nnz_max) are never read.
+ * In numpy, per row i and column c (key() = the ascending-orderable uint32 of a float32 with NaN -> 0x7fc00000, -0.0 -> +0.0):
+ *     p    = np.arange(rowptr[i], rowptr[i + 1]);  e = np.where(eid[p] < 0, -1, eid[p])
+ *     word = (key(x[col[p], c]).astype(np.uint64) << 32) | (~e.astype(np.uint32)).astype(np.uint64)
+ *     w    = word.argmax();  out[i, c] = value_of_key(word[w] >> 32);  arg[i, c] = e[w]          # len(p) == 0: +0.0, -2
+ * Consequence: out and arg are a pure function of (x, the edge list, self_loops).  The maximum is exact and the tie rule does not
+ * look at the entry order, so both are bitwise the same for either item size, for NPI_CSR_SORT_COLUMNS on or off and for any
+ * order of merging partial rows.
+ *
+ * Backward (the by-SOURCE side of the same edge list; only eid links the two sides, no transpose map):
+ *     dX[j, c] = sum of dOut[col[q], c] over the entries q of row j whose eid[q] (a loop entry: -1) equals arg[col[q], c]
+ * a gather-form sum in a fixed order: ascending entry order inside an item; a row cut by item boundaries adds its parts as
+ * tail[i] + head[i + 1] + ... ascending when it has at most 4 heads, and a longer chain (a hub row) as
+ * tail[i] + s_0 + s_1 + ... + s_15 with s_w = head[i + 1 + w] + head[i + 1 + w + 16] + ... ascending.  Bitwise reproducible for a
+ * given side; it gathers a dOut row AND an arg row per entry: the price of having no atomics.
+ *
+ *   rowptr .. rowidx : one side as npi_csr_build_ex wrote it, item_edges the item size it was built with (64 or 256)
+ *   N, n_cols        : rows of the side (= rows of out / dX) and rows of the gathered table (x / dOut and arg)
+ *   x, out, arg, dout, dx : unit column stride, leading dimensions (elements) >= F.  16-byte lanes when F > 64, F % 4 == 0 and every
+ *                      base and pitch of the call is 16-byte aligned, one float per lane otherwise: any F >= 1, any pitch >= F
+ *   workspace        : npi_segmax_workspace_bytes(nnz_max, item_edges, F) bytes, 16-byte aligned, caller-owned: the head / tail
+ *                      partial rows of every item ((value, eid) pairs forward, sums backward) and the tails' rows.  Needs no clearing
+ * Nothing is allocated, nothing read back: both calls may run inside a stream capture.  Refused with NPI_ERR_ARG before any
+ * launch: N, n_cols or nnz_max outside [0, 2^31 - 1), F <= 0, a leading dimension below F, item_edges other than 64 / 256; with N > 0 a
+ * null rowptr, col, eid, rowidx, table or output, and with nnz_max > 0 as well a workspace that is null, misaligned or shorter
+ * than the query says.  N == 0 returns NPI_OK without a launch; nnz_max == 0 launches the empty-row fill alone.
+ * npi_segmax_workspace_bytes returns -1 for a bad size or item size.
+ *
+ * Out of scope: bf16 storage, weighted messages, 'add' / 'min' (npi_segsum_ex is 'add'), two-part tables, hub streaming.
+ * ------------------------------------------------------------------------------------------ */
+int64_t npi_segmax_workspace_bytes(int64_t nnz_max, int64_t item_edges, int64_t F);   /* -1: bad size */
+int npi_segmax(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const int32_t* rowidx, int64_t item_edges,
+               int64_t N, int64_t n_cols, int64_t nnz_max, const float* x, int64_t ldx, int64_t F,
+               float* out, int64_t ldo, int32_t* arg, int64_t lda, void* workspace, int64_t workspace_bytes, void* stream);
+int npi_segmax_bwd(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const int32_t* rowidx, int64_t item_edges,
+                   int64_t N /* sources: rows of dx */, int64_t n_cols /* targets: rows of dout and arg */, int64_t nnz_max,
+                   const float* dout, int64_t ldd, const int32_t* arg, int64_t lda, int64_t F,
+                   float* dx, int64_t ldx, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Evaluation loop(reference src/methods.py:87-105 compares one element per Python
  * iteration, one device sync each).  counts[4] += [TP, FN, TN, FP] for pred = first arg-max of scores[i, 0..C):
  * pred 1 & y 1 -> TP, pred 1 & y 0 -> FP, pred 0 & y 1 -> FN, anything else -> TN (the reference's else

@@ -9,7 +9,7 @@ be imported.
 from ._lib import LIB_PATH, NpiError, load  # noqa: F401
 from .graph import BipartiteGraph, CSRGraph, GraphBatch, as_graph, set_debug  # noqa: F401
 from .functional import (GCNNorm, GaussianNoise, gat_conv, gat_conv_bipartite, gaussian_noise, gcn_conv, group_scores,  # noqa: F401
-                         link_loss, pair_scores, ranking_loss, reparametrize_kl, sage_conv, sage_conv_bipartite, segsum)
+                         link_loss, pair_scores, ranking_loss, reparametrize_kl, sage_conv, sage_conv_bipartite, segmax, segsum)
 from .nn import GATConv, GCNConv, SAGEConv  # noqa: F401
 from .schedule import Schedule  # noqa: F401
 from .graphed import GraphedStack  # noqa: F401
@@ -22,7 +22,7 @@ from .split import EdgeSplitter, to_undirected, train_test_split_edges  # noqa: 
 from .topk import KnownLinks, topk_links  # noqa: F401
 from .link_rank import LinkRanks, link_ranks, ranking_metrics  # noqa: F401
 
-__all__ = ["CSRGraph", "GraphBatch", "as_graph", "set_debug", "GCNNorm", "gat_conv", "gcn_conv", "sage_conv", "segsum",
+__all__ = ["CSRGraph", "GraphBatch", "as_graph", "set_debug", "GCNNorm", "gat_conv", "gcn_conv", "sage_conv", "segmax", "segsum",
            "GATConv", "GCNConv", "SAGEConv", "Schedule", "GraphedStack", "NeighborSampler", "DataFlow", "Block", "SubgraphBatch", "NegativeSampler", "negative_sampling",
            "structured_negative_sampling", "InnerProductDecoder", "GAE", "VGAE", "ARGA", "ARGVA", "GaussianNoise", "gaussian_noise", "reparametrize_kl", "RandomWalker", "random_walk", "Node2Vec", "pair_scores", "link_loss", "group_scores", "ranking_loss", "rank_metrics",
            "roc_auc_score", "average_precision_score", "roc_curve", "precision_recall_curve", "EdgeSplitter",

@@ -208,6 +208,9 @@ PROTOTYPES = {
     "npi_topk_links": (c_int, [_P, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, c_int, _I, _P, _P, _P, _I, _P, _P]),
     "npi_link_ranks_workspace_bytes": (_I, [_I, _I, _I]),
     "npi_link_ranks": (c_int, [_P, _P, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, c_int, _I, _P, _P, _P, _I, _P, _P]),
+    "npi_segmax_workspace_bytes": (_I, [_I, _I, _I]),
+    "npi_segmax": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
+    "npi_segmax_bwd": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P]),
 }
 
 _lib = None

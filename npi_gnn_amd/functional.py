@@ -1079,7 +1079,8 @@ class _SageConcatFn(torch.autograd.Function):
 
 def sage_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
               normalize: bool = False, edge_weight: Optional[torch.Tensor] = None, relu: bool = False,
-              pad_base: Optional[torch.Tensor] = None, schedule: Schedule = DEFAULT, concat: bool = False) -> torch.Tensor:
+              pad_base: Optional[torch.Tensor] = None, schedule: Schedule = DEFAULT, concat: bool = False,
+              aggr: str = "mean") -> torch.Tensor:
     """PyG 1.4.2 ``SAGEConv(normalize=False, concat=False).forward`` on MI355X
     (call sites: reference ``src/classes.py:62,66,70``).  ``edge_weight [E]`` scales the messages.  ``pad_base``: the wider
     buffer ``x`` is the leading columns of, its other columns zero (``GraphBatch.pad_base``).
@@ -1093,7 +1094,13 @@ def sage_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, bias: Optional[
     (``_EdgeWeightGradFn``, ``npi_edge_dot``).  As under ``add_remaining_self_loops``, an existing self-loop edge ``(k, k)``
     receives the gradient of node k's loop entry -- if several such edges name the same node, EACH of them receives it (what
     the backward of autograd's ``index_put`` does) -- the loop entries of the other nodes carry the constant 1, and padding
-    columns ``(-1, -1)`` and dropped edges get 0.  The gradient has ``edge_weight``'s shape and dtype."""
+    columns ``(-1, -1)`` and dropped edges get 0.  The gradient has ``edge_weight``'s shape and dtype.
+
+    ``aggr="max"``: the maximum over the same entries instead of their mean (``segmax``, Rule X; float32, no ``edge_weight``;
+    ``schedule`` only names the GEMM flags) -- ``_SageMaxFn``."""
+    if aggr != "mean":
+        _check_aggr(aggr, "sage_conv")
+        return _sage_conv_max(x, edge_index, weight, bias, normalize, edge_weight, relu, schedule, concat)
     require_gpu(x, weight, bias)
     w_grad = _check_edge_weight_grad(edge_weight, x, weight)
     x_in = x
@@ -1135,6 +1142,231 @@ def sage_conv(x: torch.Tensor, edge_index, weight: torch.Tensor, bias: Optional[
     if normalize:
         out = l2_normalize(out)
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Max aggregation (include/npi_gnn.h: RULE X) and SAGEConv(aggr="max")
+# ---------------------------------------------------------------------------------------------
+def _check_aggr(aggr, who: str) -> None:
+    if aggr not in ("mean", "max"):
+        raise ValueError(f"{who}: aggr must be 'mean' or 'max' (got {aggr!r})")
+
+
+def _f32_rows(t: torch.Tensor, name: str, who: str) -> torch.Tensor:
+    """an f32 ``[rows, F]`` operand of the max kernels: unit column stride, any row pitch >= F (anything else is copied)"""
+    if t.dtype != torch.float32:
+        raise NotImplementedError(f"{who}: {name} is {t.dtype}; max aggregation runs on float32 tables (bf16 storage is not implemented)")
+    if t.dim() != 2 or t.size(1) < 1:
+        raise ValueError(f"{who}: {name} must be a [rows, F] tensor with F >= 1")
+    return t if t.stride(1) == 1 and t.stride(0) >= t.size(1) else t.contiguous()
+
+
+def _pitch(t: torch.Tensor) -> int:
+    return t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))     # (the stride of a single row means nothing)
+
+
+def _segmax_workspace(side: CSRSide, F: int, dev) -> torch.Tensor:
+    """the per-call scratch of ``npi_segmax`` / ``npi_segmax_bwd`` (head / tail partial rows of every item); needs no clearing"""
+    return torch.empty(int(load().npi_segmax_workspace_bytes(side.nnz_max, side.item, F)), dtype=torch.uint8, device=dev)
+
+
+def segmax_side(side: CSRSide, x: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """``(out, arg)`` of Rule X over ONE side (``npi_segmax``): ``out[i] = max_{p in row i} x[col[p]]``, ``arg`` the winners' ``eid``
+    (int32; -1 the appended loop, -2 a row without entries, whose ``out`` is 0).  ``out``: write the maxima into this ``[n_rows, F]``
+    tensor (a column block of a wider buffer is fine).  Not differentiable: ``segmax`` is."""
+    dev = require_gpu(x, out)
+    x = _f32_rows(x, "x", "segmax")
+    N, F = side.n_rows, x.size(1)
+    if x.size(0) < side.n_cols:
+        raise ValueError(f"segmax: the table has {x.size(0)} rows, the adjacency indexes {side.n_cols}")
+    if out is None:
+        out = torch.empty((N, F), dtype=torch.float32, device=dev)
+    else:
+        _check_out(out, N, F, x, "segmax")
+    arg = torch.empty((N, F), dtype=torch.int32, device=dev)
+    ws = _segmax_workspace(side, F, dev)
+    check(load().npi_segmax(ptr(side.rowptr), ptr(side.col), ptr(side.eid), ptr(side.rowidx), side.item, N, side.n_cols, side.nnz_max,
+                            ptr(x), _pitch(x), F, ptr(out), _pitch(out), ptr(arg), F, ptr(ws), ws.numel(), stream_ptr(dev)), "npi_segmax")
+    return out, arg
+
+
+def segmax_bwd_side(tside: CSRSide, dout: torch.Tensor, arg: torch.Tensor) -> torch.Tensor:
+    """``dX`` of Rule X over the by-SOURCE side (``npi_segmax_bwd``): row j sums ``dout[i, c]`` over its entries ``(j -> i)`` whose
+    ``eid`` is ``arg[i, c]`` -- a gather in a fixed order, no float atomics, bitwise reproducible."""
+    dev = require_gpu(dout, arg)
+    dout = _f32_rows(dout, "grad_out", "segmax")
+    F = dout.size(1)
+    if arg.dtype != torch.int32 or arg.shape != dout.shape or arg.stride(1) != 1 or arg.stride(0) < F:
+        raise ValueError("segmax: arg must be the int32 [rows, F] winners of the forward, the shape of grad_out")
+    if dout.size(0) < tside.n_cols:
+        raise ValueError(f"segmax: grad_out has {dout.size(0)} rows, the by-source side indexes {tside.n_cols}")
+    dx = torch.empty((tside.n_rows, F), dtype=torch.float32, device=dev)
+    ws = _segmax_workspace(tside, F, dev)
+    check(load().npi_segmax_bwd(ptr(tside.rowptr), ptr(tside.col), ptr(tside.eid), ptr(tside.rowidx), tside.item, tside.n_rows,
+                                tside.n_cols, tside.nnz_max, ptr(dout), _pitch(dout), ptr(arg), _pitch(arg), F, ptr(dx), F, ptr(ws),
+                                ws.numel(), stream_ptr(dev)), "npi_segmax_bwd")
+    return dx
+
+
+class _SegmaxFn(torch.autograd.Function):
+    """``segmax`` over a graph: ``by_dst`` forward, ``by_src`` (built on first use) backward; ``arg`` is kept and not differentiable"""
+
+    @staticmethod
+    def forward(ctx, x, graph):
+        out, arg = segmax_side(graph.by_dst, x)
+        ctx.graph = graph
+        ctx.save_for_backward(arg)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, dout, _darg):
+        (arg,) = ctx.saved_tensors
+        return segmax_bwd_side(ctx.graph.by_src, dout, arg), None
+
+
+def segmax(graph_or_side, x: torch.Tensor):
+    """``(out, arg)``: the max aggregation of PyG's ``MessagePassing(aggr='max')`` under Rule X (``include/npi_gnn.h``) --
+    ``out[i, c] = max_{j -> i} x[j, c]`` (a target without an entry: 0), ``arg[i, c]`` the column of ``edge_index`` that won (int32;
+    -1: the appended self loop, -2: no entry; ties: the smallest column, the loop last; NaN beats every number).  Both are a pure
+    function of ``(x, edge list, self_loops)``: bitwise the same for either item size and for ``sort_columns`` on or off.
+    ``graph_or_side``: a ``CSRGraph``, a ``BipartiteGraph`` (``x`` = the source table), a ``GraphBatch``, the ``[2, E]`` tensor
+    (sorted here, self loops appended, as the layers do) or one ``CSRSide`` (then nothing is differentiable: a side alone has no
+    transposed side).  Differentiable in ``x``: the gradient of ``out[i, c]`` goes to the winner's row, summed over the by-source side
+    in a fixed order (no float atomics; bitwise reproducible).  float32 only; ``x`` may keep a row pitch."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError("segmax: x must be a [rows, F] tensor")
+    if x.dtype != torch.float32:
+        raise NotImplementedError(f"segmax: x is {x.dtype}; max aggregation runs on float32 tables (bf16 storage is not implemented)")
+    require_gpu(x)
+    g = graph_or_side
+    if isinstance(g, CSRSide):
+        if x.requires_grad and torch.is_grad_enabled():
+            raise ValueError("segmax: a CSRSide alone has no by-source side for the backward; pass the CSRGraph / BipartiteGraph")
+        return segmax_side(g, x)
+    if isinstance(g, GraphBatch):
+        g = g.graph()
+    elif isinstance(g, torch.Tensor):
+        g = CSRGraph(g, x.size(0))
+    if not isinstance(g, (CSRGraph, BipartiteGraph)):
+        raise TypeError("segmax: the first argument is a CSRGraph, a BipartiteGraph, a GraphBatch, a CSRSide or the [2, E] edge_index")
+    if x.size(0) != g.by_dst.n_cols:
+        raise ValueError(f"segmax: the graph gathers from {g.by_dst.n_cols} rows, x has {x.size(0)}")
+    return _SegmaxFn.apply(x, g)
+
+
+def _root_only_side(graph: BipartiteGraph, res_n_id: torch.Tensor) -> CSRSide:
+    """the side that scatters ``N_dst`` root rows back through ``res_n_id`` as ONE deterministic segmented sum (row ``res_n_id[i]`` holds
+    entry i; duplicates accumulate in list order) -- the root term of ``SAGEConv(concat=True, aggr='max')``'s backward in the pair form;
+    kept for as long as ``res_n_id`` is the same tensor in the same state (``BipartiteGraph.root_side`` is the precedent)"""
+    key = (res_n_id.data_ptr(), res_n_id._version, tuple(res_n_id.shape))
+    kept = graph.__dict__.get("_root_only")
+    if kept is None or kept[0] != key:
+        nd = graph.num_dst
+        side = build_side(res_n_id.reshape(-1), torch.arange(nd, dtype=torch.int64, device=graph.device), graph.num_src, nd,
+                          self_loops=False, drop_equal=False, item=graph.by_dst.item)
+        kept = graph._root_only = (key, side, res_n_id)
+    return kept[1]
+
+
+class _SageMaxFn(torch.autograd.Function):
+    """``SAGEConv(aggr='max')``: ``out = act([root |] max_{j -> i} x_j) @ W + b``.  Forward: ``npi_segmax`` (written straight into the
+    right half of the GEMM's operand under ``concat``), then ``linear_fwd`` with the bias and the ``relu=`` epilogue.  Backward:
+    ``linear_bwd_weight``, ``linear_bwd_data``, ``npi_segmax_bwd`` over the by-source side.  ``res_n_id``: the pair form's root rows."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, graph, res_n_id, concat: bool, relu: bool, flags: int):
+        d = graph.by_dst
+        x = _f32_rows(x, "x", "sage_conv")
+        N, F = d.n_rows, x.size(1)
+        if concat:
+            a = torch.empty((N, 2 * F), dtype=torch.float32, device=x.device)
+            if res_n_id is None:
+                a[:, :F].copy_(x)
+            else:
+                rows_gather(x, res_n_id, a[:, :F], status=d.status)
+            _, arg = segmax_side(d, x, out=a[:, F:])
+        else:
+            a, arg = segmax_side(d, x)
+        out = linear_fwd(a, weight, bias, relu=relu, flags=flags)
+        ctx.graph, ctx.F, ctx.res_n_id, ctx.concat, ctx.relu, ctx.flags = graph, F, res_n_id, concat, relu, flags
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(a, weight, arg, out if relu else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        a, weight, arg, out = ctx.saved_tensors
+        graph, F = ctx.graph, ctx.F
+        g = _f32c(grad_out, "grad_out")
+        if ctx.relu:
+            g = relu_backward(g, out)
+        dx = dw = db = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            dw, db = linear_bwd_weight(a, g, want_bias=ctx.has_bias, flags=ctx.flags)
+        if ctx.needs_input_grad[0]:
+            da = linear_bwd_data(g, weight, flags=ctx.flags)                      # [N, F], or [N, 2F]: [d root | d max]
+            dx = segmax_bwd_side(graph.by_src, da[:, F:] if ctx.concat else da, arg)
+            if ctx.concat and ctx.res_n_id is None:
+                dx += da[:, :F]
+            elif ctx.concat:
+                dx += segsum(graph, _root_only_side(graph, ctx.res_n_id), da[:, :F], mean=False)
+        return dx, dw, db, None, None, None, None, None
+
+
+def _refuse_for_max(who: str, x, weight, bias, edge_weight) -> None:
+    """what ``aggr='max'`` does not take, said before any device work; then the usual device check"""
+    if edge_weight is not None:
+        raise NotImplementedError(f"{who}(aggr='max'): edge_weight is not implemented (weighted messages under max are out of scope)")
+    for t, name in ((x, "x"), (weight, "weight"), (bias, "bias")):
+        if t is not None and t.dtype != torch.float32:
+            raise NotImplementedError(f"{who}(aggr='max'): {name} is {t.dtype}; max aggregation runs on float32 features and weights "
+                                      "(bf16 storage is not implemented)")
+    require_gpu(x, weight, bias)
+
+
+def _sage_conv_max(x, edge_index, weight, bias, normalize: bool, edge_weight, relu: bool, schedule: Schedule, concat: bool):
+    who = "sage_conv"
+    _refuse_for_max(who, x, weight, bias, edge_weight)
+    if relu and normalize:
+        raise ValueError(f"{who}: relu=True applies to the projection's output; normalize=True comes after it in PyG")
+    N, F = x.shape
+    if weight.size(0) != (2 if concat else 1) * F:
+        raise ValueError(f"{who}(aggr='max'): weight must have {(2 if concat else 1) * F} rows (got {weight.size(0)})")
+    if not concat:
+        graph = as_graph(edge_index, N)
+    elif isinstance(edge_index, CSRGraph):                      # the edge list as it is, as for the mean
+        graph = edge_index
+        if graph.self_loops or not graph.keep_equal:
+            raise ValueError("sage_conv(concat=True) aggregates over the edge list as it is: build the graph with "
+                             "CSRGraph(edge_index, N, self_loops=False, keep_equal=True)")
+        if graph.num_nodes != N:
+            raise ValueError(f"CSRGraph was built for {graph.num_nodes} nodes, x has {N}")
+    else:
+        ei = edge_index.edge_index if hasattr(edge_index, "edge_index") else edge_index
+        graph = CSRGraph(ei, N, self_loops=False, keep_equal=True)
+    out = _SageMaxFn.apply(x, weight, bias, graph, None, concat, relu, _gflags(schedule))
+    return l2_normalize(out) if normalize else out
+
+
+def _sage_conv_bipartite_max(x, edge_index, weight, bias, size, res_n_id, normalize: bool, concat: bool, edge_weight, relu: bool,
+                             schedule: Schedule):
+    who = "sage_conv_bipartite"
+    x_src, _, n_src, n_dst = _pair_sizes(x, size, who, edge_index)
+    _refuse_for_max(who, x_src, weight, bias, edge_weight)
+    if relu and normalize:
+        raise ValueError(f"{who}: relu=True applies to the projection's output; normalize=True comes after it in PyG")
+    if weight.size(0) != (2 if concat else 1) * x_src.size(1):
+        raise ValueError(f"{who}(aggr='max'): weight must have {(2 if concat else 1) * x_src.size(1)} rows (got {weight.size(0)})")
+    if concat:
+        if res_n_id is None:
+            raise ValueError(f"{who}(concat=True): res_n_id [N_dst] is required -- the rows of x_src that are the targets' own features")
+        if res_n_id.dtype != torch.int64 or res_n_id.dim() != 1 or res_n_id.numel() != n_dst:
+            raise ValueError(f"{who}: res_n_id must be a LongTensor [{n_dst}] (one row of x_src per target)")
+        require_gpu(x_src, res_n_id)
+    graph = _as_bipartite(edge_index, n_src, n_dst, who)
+    out = _SageMaxFn.apply(x_src, weight, bias, graph, res_n_id.contiguous() if concat else None, concat, relu, _gflags(schedule))
+    return l2_normalize(out) if normalize else out
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2110,7 +2342,8 @@ class _SageBipartiteConcatFn(torch.autograd.Function):
 
 def sage_conv_bipartite(x, edge_index, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, size=None,
                         res_n_id: Optional[torch.Tensor] = None, normalize: bool = False, concat: bool = False,
-                        edge_weight: Optional[torch.Tensor] = None, relu: bool = False, schedule: Schedule = DEFAULT) -> torch.Tensor:
+                        edge_weight: Optional[torch.Tensor] = None, relu: bool = False, schedule: Schedule = DEFAULT,
+                        aggr: str = "mean") -> torch.Tensor:
     """PyG 1.4.2 ``SAGEConv.forward((x_src, x_dst), edge_index, edge_weight, size, res_n_id)``: ``edge_index[0]`` indexes
     ``x_src``, ``edge_index[1]`` the ``N_dst`` output rows (``N_dst``: ``x_dst``'s rows, else ``size[1]``, else ``N_src``).  No self
     loop is added or removed; a target without an in-edge gets ``bias`` (or 0).
@@ -2120,8 +2353,11 @@ def sage_conv_bipartite(x, edge_index, weight: torch.Tensor, bias: Optional[torc
     of ``x_src`` (an id out of range gives a zero root row and is reported like a dropped edge, ``graph.note_status``).
     ``edge_index``: the ``[2, E]`` tensor (sorted here, every call) or a ``BipartiteGraph``.  float32 only.  Gradients: ``x_src``,
     ``weight``, ``bias`` and ``edge_weight`` (``d edge_weight[e] = inv_count[i] <dAgg[i], x_src[j]>``, ``npi_edge_dot`` over the
-    by-target side)."""
+    by-target side).  ``aggr="max"``: the maximum over a target's in-edges instead of their mean (``segmax``, Rule X; no ``edge_weight``)."""
     who = "sage_conv_bipartite"
+    if aggr != "mean":
+        _check_aggr(aggr, who)
+        return _sage_conv_bipartite_max(x, edge_index, weight, bias, size, res_n_id, normalize, concat, edge_weight, relu, schedule)
     x_src, x_dst, n_src, n_dst = _pair_sizes(x, size, who, edge_index)
     if concat and res_n_id is None:
         raise ValueError(f"{who}(concat=True): res_n_id [N_dst] is required -- the rows of x_src that are the targets' own features")

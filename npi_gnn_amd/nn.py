@@ -49,16 +49,22 @@ def _only_batch(gb: GraphBatch, edge_index, who: str) -> GraphBatch:
 
 
 class SAGEConv(nn.Module):
-    """``SAGEConv(in_channels, out_channels, normalize=False, concat=False, bias=True)`` --
-    mean over in-neighbours and the node itself, then ``@ weight + bias``.  Both parameters are
+    """``SAGEConv(in_channels, out_channels, normalize=False, concat=False, bias=True, aggr="mean")`` --
+    mean over in-neighbours and the node itself, then ``@ weight + bias``.  ``aggr="max"``: the maximum instead of the mean
+    (GraphSAGE's pooling aggregator; ``functional.segmax``, Rule X: exact, ties to the smallest edge column, float32, no
+    ``edge_weight``); the parameters, their shapes and initialisation are the same, ``aggr`` is not in the ``state_dict``, so a
+    checkpoint moves between the two.  Any other ``aggr`` is a ``ValueError``.  Both parameters are
     initialised U(+-1/sqrt(weight.size(0))) as in PyG 1.4.2.  ``concat=True``: no self loop is added, the mean over the
     in-neighbours is concatenated behind the node's own features and ``weight`` is ``[2 in, out]`` -- an option the reference
     never sets, served as a COMPOSED layer (the kernels of the default layer plus torch elementwise ops on the activations in
     its backward: three activation-sized passes more than a fused layer would make), not at the default layer's kernel quality."""
 
     def __init__(self, in_channels: int, out_channels: int, normalize: bool = False, concat: bool = False,
-                 bias: bool = True, schedule: Schedule = DEFAULT, **kwargs):
+                 bias: bool = True, schedule: Schedule = DEFAULT, aggr: str = "mean", **kwargs):
         super().__init__()
+        if aggr not in ("mean", "max"):
+            raise ValueError(f"SAGEConv: aggr must be 'mean' or 'max' (got {aggr!r})")
+        self.aggr = aggr
         self.schedule = schedule                  # how the launches are arranged (schedule.Schedule); never what they compute
         self.in_channels = in_channels
         self.out_channels = out_channels
@@ -92,7 +98,8 @@ class SAGEConv(nn.Module):
                 raise TypeError("SAGEConv: a GraphBatch is one id space; `size` belongs to the pair form x = (x_src, x_dst)")
         if isinstance(x, (tuple, list)):
             return F_.sage_conv_bipartite(x, edge_index, self.weight, self.bias, size=size, res_n_id=res_n_id, normalize=self.normalize,
-                                          concat=self.concat, edge_weight=edge_weight, relu=relu, schedule=self.schedule)
+                                          concat=self.concat, edge_weight=edge_weight, relu=relu, schedule=self.schedule,
+                                          aggr=self.aggr)
         if size is not None:
             if isinstance(edge_index, GraphBatch):
                 raise TypeError("SAGEConv: a GraphBatch is one id space; `size` belongs to the pair form x = (x_src, x_dst)")
@@ -102,14 +109,16 @@ class SAGEConv(nn.Module):
                                  "x = (x_src, x_dst) (PyG would scatter x.size(0) self loops into size[1] rows)")
         if isinstance(x, GraphBatch):
             gb = _only_batch(x, edge_index, "SAGEConv")
-            return gb.with_x(F_.sage_conv(gb.x, gb if self.concat else gb.graph(), self.weight, self.bias, normalize=self.normalize,
-                                          edge_weight=edge_weight, relu=relu, pad_base=gb.pad_base, schedule=self.schedule,
-                                          concat=self.concat))
+            # (aggr="max" takes the batch itself: what it refuses, it refuses before the batch's CSR is built)
+            return gb.with_x(F_.sage_conv(gb.x, gb if self.concat or self.aggr != "mean" else gb.graph(), self.weight, self.bias,
+                                          normalize=self.normalize, edge_weight=edge_weight, relu=relu, pad_base=gb.pad_base,
+                                          schedule=self.schedule, concat=self.concat, aggr=self.aggr))
         return F_.sage_conv(x, edge_index, self.weight, self.bias, normalize=self.normalize, edge_weight=edge_weight,
-                            relu=relu, schedule=self.schedule, concat=self.concat)
+                            relu=relu, schedule=self.schedule, concat=self.concat, aggr=self.aggr)
 
     def __repr__(self):
-        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
+        extra = "" if self.aggr == "mean" else f", aggr={self.aggr!r}"
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}{extra})"
 
 
 class GATConv(nn.Module):
