@@ -1385,6 +1385,93 @@ int npi_link_ranks(const int64_t* src, const int64_t* dst, int64_t Q,
                    int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Listwise link loss: the training objective whose optimum the filtered MRR of npi_link_ranks measures -- for every positive
+ * (s, t) the negative log-probability of t under the softmax over EVERY candidate target of s (the "1-N" / full-softmax loss of
+ * the knowledge-graph-embedding and recommender literature), where npi_group_score's softmax mode sees K <= 63 sampled
+ * corruptions.  The three entry points replace `F.cross_entropy(scale * z_src[src] @ z_dst.t() + mask, t)` over
+ * `InnerProductDecoder.forward_all` and its autograd backward: the dense [Q, n_dst] product, a dense additive mask, the
+ * probability matrix kept for the backward, and `index_add_` on float atomics.  Here the scan is npi_topk_links' -- tiles of 64
+ * queries x 128 targets on the matrix cores, known edges masked on the chip -- and nothing of size Q * n_dst is ever written,
+ * forward or backward.
+ *
+ * RULE L -- lp_q, the loss and the gradients, from two f32 tables, Q query pairs (s_q, t_q), a set of excluded pairs, a no-loops
+ *           flag and a finite scale > 0.
+ *   1. Score.   x_qj = scale * score(s_q, j) with score the ascending f32 fmaf chain of Rule K 1 -- the bits npi_topk_links and
+ *              npi_link_ranks produce for the pair -- and the product with scale ONE f32 multiply.
+ *   2. Candidates of query q: j == t_q, OR ((s_q, j) not in the exclusion set AND (j != s_q unless NPI_SOFTMAX_LINK_NO_LOOPS is
+ *              clear)).  The true target is always a candidate, also when (s_q, t_q) is itself a known edge (Rule F 2: in
+ *              training the positives ARE the known edges); the other known partners of s_q are not in the denominator -- the
+ *              filtered softmax, which removes the false negatives.
+ *   3. Output.  lp_q = x_{q,t_q} - lse_q, lse_q = log(sum over the candidates j of exp(x_qj)) in the max-shifted form: finite
+ *              for any finite scores, and exactly 0 (with exactly zero gradients) when the target is the only candidate.
+ *   4. Bad pair. s_q outside [0, n_src) or t_q outside [0, n_dst): nothing is dereferenced, lp_q = 0 (lse_q = 0),
+ *              NPI_STATUS_BAD_PAIR_ID is raised, and the pair contributes nothing to any sum or gradient.
+ *   5. NaN.     A NaN score among the candidates makes lp_q NaN, as torch.logsumexp would, and raises NPI_STATUS_BAD_SCORE.
+ *              The gradients of such a query are unspecified.
+ *   6. Loss.    loss = -(sum over the good pairs of lp_q) / Q.  The divisor counts pairs, not good pairs (Rule G: nothing is read
+ *              back); Q == 0 gives 0.  The sum is the fp64 scheme of npi_pair_score: one partial per workgroup, one workgroup adds
+ *              them in a fixed order.
+ *   7. Gradient. With u_q = d L / d lp_q and p_qj = exp(x_qj - lse_q) over the candidates, d L / d x_qj = u_q ([j == t_q] - p_qj):
+ *                  dZ_src[i] = scale * sum over q with s_q == i and over the candidates j of u_q ([j == t_q] - p_qj) z_dst[j]
+ *                  dZ_dst[j] = scale * sum over q that j is a candidate of, of u_q ([j == t_q] - p_qj) z_src[s_q]
+ *              (one id space: both land in the one table).  The entry points compute the DENSE part, -u_q scale p_qj over the
+ *              candidates j != t_q; the target's own term u_q scale (1 - exp(lp_q)) per pair is a weighted pair-list sum, which
+ *              npi_segsum_ex over the pair list's sides already is (functional._pair_grads).
+ *                  npi_softmax_link_bwd_src : dq[q, :] = sum_j w_qj z_dst[j, :], w_qj = -u_q scale p_qj, j ascending; dZ_src is
+ *                                             then the segmented sum of dq's rows over the queries of each source
+ *                  npi_softmax_link_bwd_dst : dz_dst[j, :] = sum_q w_qj z_src[s_q, :], q ascending
+ *   8. Reproducibility, forward.  lp is a pure function of (tables, pair, exclusion set, flags, scale, splits): the same bits run
+ *              to run and for any order or repetition of the queries (which lane adds which column depends on the column alone).
+ *              Across different `splits` the float sum order changes: equal up to rounding, not bitwise.  Within one call all
+ *              queries of one source with the same candidate set share lse bit for bit, so lp orders them as their scores do.
+ *   9. Reproducibility, backward.  The same bits run to run for the same arguments: every element is one fmaf chain in ascending
+ *              partner order per split, the splits added in ascending order.  No float atomics anywhere.
+ *
+ *   src, dst  : int64 [Q] each: the query pairs, in any order, repeats allowed
+ *   z_src, z_dst, ld_src, ld_dst, n_src, n_dst, F, ex_rowptr, ex_col, status : as npi_link_ranks takes them
+ *   flags     : NPI_SOFTMAX_LINK_NO_LOOPS or 0;  scale : finite, > 0
+ *   splits    : 0 (chosen as npi_topk_links chooses) or the number of ranges scanned separately: column ranges of z_dst in
+ *               npi_softmax_link_fwd / _bwd_src, ranges of the QUERY list in _bwd_dst
+ *   lp, lse   : f32 [Q] each (fwd: written; bwd: lse read);  loss : f32 [1] or NULL;  u : f32 [Q], d L / d lp
+ *   dq        : f32 [Q, F], contiguous;  dz_dst : f32 [n_dst, F], contiguous.  Both are written, not accumulated into
+ *   workspace : npi_softmax_link_workspace_bytes(Q, n_src, n_dst, F, splits) bytes, 16-byte aligned, caller-owned; one size serves
+ *               the three calls: (m, s) per query and split, a key per query and the loss partials forward, the F-wide partial rows
+ *               of every split backward -- O(S (Q + n_dst) F), nowhere near a score matrix
+ * Nothing is allocated, nothing read back: every call may run inside a stream capture.  The only atomic is the status OR.
+ * Refused with NPI_ERR_ARG before any launch: Q, n_src or n_dst outside [0, 2^31 - 1), F outside [1, 2^31 - 1), a leading
+ * dimension below F, an unknown flag, NPI_SOFTMAX_LINK_NO_LOOPS with n_src != n_dst, only one of ex_rowptr / ex_col, negative
+ * splits, a scale that is not positive and finite; with Q > 0 a null list, table that has rows, lp / lse / u / dq / dz_dst or
+ * workspace, and a workspace misaligned or shorter than the query says.  Q == 0: NPI_OK without a kernel (loss[0], if given, and
+ * dz_dst are set to 0 by hipMemsetAsync).  npi_softmax_link_workspace_bytes returns -1 on a bad size, or when the byte count does not
+ * fit an int64 (the calls then refuse too).
+ *
+ * Out of scope: bf16 tables, grouping the queries by source to share score rows (the obvious next optimisation: the queries of
+ * one source share every x_qj), per-target weights or label smoothing, the by-target softmax (swap the tables and flip the
+ * lists), decoders other than the inner product, a top-k truncated softmax, gradients through scale.
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_SOFTMAX_LINK_NO_LOOPS 1
+int64_t npi_softmax_link_workspace_bytes(int64_t Q, int64_t n_src, int64_t n_dst, int64_t F, int64_t splits);   /* -1: bad size */
+int npi_softmax_link_fwd(const int64_t* src, const int64_t* dst, int64_t Q,
+                         const float* z_src, int64_t ld_src, int64_t n_src,
+                         const float* z_dst, int64_t ld_dst, int64_t n_dst, int64_t F,
+                         const int32_t* ex_rowptr, const int32_t* ex_col /* by-source CSR, columns ascending; both NULL: none */,
+                         int flags /* NPI_SOFTMAX_LINK_NO_LOOPS 1 */, float scale, int64_t splits,
+                         float* lp /* [Q] */, float* lse /* [Q] */, float* loss /* [1], may be NULL */,
+                         void* workspace, int64_t workspace_bytes, int32_t* status, void* stream);
+int npi_softmax_link_bwd_src(const int64_t* src, const int64_t* dst, int64_t Q,
+                             const float* z_src, int64_t ld_src, int64_t n_src,
+                             const float* z_dst, int64_t ld_dst, int64_t n_dst, int64_t F,
+                             const int32_t* ex_rowptr, const int32_t* ex_col, int flags, float scale, int64_t splits,
+                             const float* lse /* [Q] */, const float* u /* [Q] */, float* dq /* [Q, F] */,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+int npi_softmax_link_bwd_dst(const int64_t* src, const int64_t* dst, int64_t Q,
+                             const float* z_src, int64_t ld_src, int64_t n_src,
+                             const float* z_dst, int64_t ld_dst, int64_t n_dst, int64_t F,
+                             const int32_t* ex_rowptr, const int32_t* ex_col, int flags, float scale, int64_t splits,
+                             const float* lse /* [Q] */, const float* u /* [Q] */, float* dz_dst /* [n_dst, F] */,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Max aggregation: the third aggregator of PyG's `MessagePassing` (`add`, `mean`, `max`) -- the pooling aggregator of GraphSAGE.
  * npi_segmax replaces `scatter_('max', x[col], row, dim_size=N)` inside `MessagePassing.propagate(aggr='max')`, npi_segmax_bwd the
  * backward of that composition (`index_add_` on float atomics).  Neither writes the [nnz, F] gather, neither uses a float atomic.

@@ -7,7 +7,8 @@ walks and their skip-gram pair list), ``npi_pair_score`` (scores and loss), ``np
 positive against its own corrupted targets), ``npi_gauss_*`` (the variational
 sample and its KL term), ``npi_rank_metrics`` (ROC-AUC, average precision and
 the score curve of an evaluation), ``npi_topk_links`` (the k most likely new links of every query row), ``npi_link_ranks`` (the
-filtered rank of every held-out link among the targets its source has no known edge to).
+filtered rank of every held-out link among the targets its source has no known edge to), ``npi_softmax_link_*`` (the listwise
+loss over all those targets, forward and backward).
 """
 from __future__ import annotations
 
@@ -51,6 +52,7 @@ NPI_GAUSS_KL = 2                  # ... and the KL term
 NPI_TOPK_MAX = 128               # largest k of npi_topk_links
 NPI_TOPK_NO_LOOPS = 1            # flag of npi_topk_links: one id space, (v, v) is no candidate
 NPI_LINK_RANK_NO_LOOPS = 1       # flag of npi_link_ranks: one id space, (v, v) is no competitor
+NPI_SOFTMAX_LINK_NO_LOOPS = 1    # flag of npi_softmax_link_*: one id space, (v, v) is no candidate (unless it is the target)
 NPI_HUB_MAX = 128               # hubs per plan (npi_hub_plan; mask words of NPI_HUB_MAX / 32 per source row)
 
 
@@ -208,6 +210,10 @@ PROTOTYPES = {
     "npi_topk_links": (c_int, [_P, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, c_int, _I, _P, _P, _P, _I, _P, _P]),
     "npi_link_ranks_workspace_bytes": (_I, [_I, _I, _I]),
     "npi_link_ranks": (c_int, [_P, _P, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, c_int, _I, _P, _P, _P, _I, _P, _P]),
+    "npi_softmax_link_workspace_bytes": (_I, [_I, _I, _I, _I, _I]),
+    "npi_softmax_link_fwd": (c_int, [_P, _P, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, c_int, c_float, _I, _P, _P, _P, _P, _I, _P, _P]),
+    "npi_softmax_link_bwd_src": (c_int, [_P, _P, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, c_int, c_float, _I, _P, _P, _P, _P, _I, _P]),
+    "npi_softmax_link_bwd_dst": (c_int, [_P, _P, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, c_int, c_float, _I, _P, _P, _P, _P, _I, _P]),
     "npi_segmax_workspace_bytes": (_I, [_I, _I, _I]),
     "npi_segmax": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
     "npi_segmax_bwd": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P]),

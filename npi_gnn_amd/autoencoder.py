@@ -37,6 +37,7 @@ from . import functional as F_
 from .negative import NegativeSampler
 from .rank import rank_metrics
 from .link_rank import link_ranks, ranking_metrics
+from .softmax_link import listwise_loss
 from .topk import topk_links
 
 
@@ -147,6 +148,16 @@ class GAE(nn.Module):
             neg_dst = sampler.corrupt(pos_edge_index[0].repeat_interleave(num_neg), draw=self.draw).view(P, num_neg)
             self.draw += 1
         return F_.ranking_loss(z, pos_edge_index, neg_dst, loss=loss, margin=margin, scale=scale)
+
+    def listwise_loss(self, z, pos_edge_index: torch.Tensor, known_edge_index=None, scale: float = 1.0) -> torch.Tensor:
+        """``softmax_link.listwise_loss``: every positive against ALL targets its source has no edge to in ``known_edge_index`` (the
+        ``[2, E]`` LongTensor, or a ``KnownLinks`` of it built once; default: ``pos_edge_index`` itself) -- the full-softmax
+        objective whose optimum ``test_ranking`` measures, where ``ranking_loss`` samples ``num_neg`` corruptions.  The target is
+        always in its own denominator; ``(v, v)`` is no candidate when ``z`` is one id space, as in ``predict`` and
+        ``test_ranking``.  The inner product is scored whatever the decoder."""
+        one = isinstance(z, torch.Tensor) or (isinstance(z, (tuple, list)) and len(z) == 2 and z[0] is z[1])
+        known = pos_edge_index if known_edge_index is None else known_edge_index
+        return listwise_loss(z, pos_edge_index, exclude=known, scale=scale, allow_loops=not one)
 
     def test(self, z, pos_edge_index: torch.Tensor, neg_edge_index: torch.Tensor):
         """PyG's ``test(z, pos_edge_index, neg_edge_index)``: ``(auc, ap)`` = ``roc_auc_score`` and ``average_precision_score`` of

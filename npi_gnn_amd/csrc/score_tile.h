@@ -1,10 +1,11 @@
-// The tile producer of the all-targets scans (include/npi_gnn.h: RULE K 1 - 3), shared by the top-k selection (topk.hip) and the
-// filtered link ranks (link_rank.hip).  A workgroup of 256 threads owns 64 query rows and walks its split's z_dst rows in tiles
-// of 128, ascending.  Per tile: the 64 x 128 scores on v_mfma_f32_32x32x2_f32 (both operands K-contiguous, the A . B^T form of
+// The tile producer of the all-targets scans (include/npi_gnn.h: RULE K 1 - 3), shared by the top-k selection (topk.hip), the
+// filtered link ranks (link_rank.hip) and the listwise link loss (softmax_link.hip).  A workgroup of 256 threads owns 64 query
+// rows and walks its split's z_dst rows in tiles of 128, ascending.
+// Per tile: the 64 x 128 scores on v_mfma_f32_32x32x2_f32 (both operands K-contiguous, the A . B^T form of
 // gemm_f32.hip's edge kernel: [row][BK + 4] LDS images, double-buffered k-steps of 32, the next tile's first k-step already in
 // flight), the accumulators go to LDS as KEYS (rank_key.h), and every wavefront takes 16 rows: it marks the row's excluded columns
 // (a cursor into the row's sorted CSR segment, placed by one binary search at the split's first column, moving forward only) and
-// the loop column, then hands the row's 128 keys to the CONSUMER -- what the two files differ in.
+// the loop column, then hands the row's 128 keys to the CONSUMER -- what the files differ in.
 // The k order of the products: the LDS image of a k-step stores column 8 g + e of a row at position 8 g + 4 (e & 1) + (e >> 1),
 // so that the 16-byte fragment of lane half h holds columns 8 g + h, 8 g + 2 + h, 8 g + 4 + h, 8 g + 6 + h and MFMA s of a group
 // multiplies columns 8 g + 2 s (half 0) and 8 g + 2 s + 1 (half 1): an ascending fmaf chain per output element, whatever tile,
@@ -19,7 +20,14 @@
 //                                               rows 16 wave .. 16 wave + 15 into registers
 //   void row(rr, r, krow, c0, cn, lane)         row r = 16 wave + rr of the workgroup (a good id), its keys of the tile's columns
 //                                               c0 .. c0 + cn - 1 in krow[0 .. cn) (TK_KEY_OUT: no candidate; also past cn)
+// and may provide (softmax_link.hip; a consumer without the constant compiles to what it compiled to before)
+//   static constexpr bool TILE_HOOKS = true     void tile_begin(c0, cn, wave, lane) before the rows of a tile and
+//                                               void tile_end(sh, c0, cn, wave, lane) after them: a second stage over what row()
+//                                               left in the wavefront's own 16 rows of sh.keys
+//   static constexpr bool GATHER_B = true       the B row of column j is zd[brows[j]] (zeros for an id outside [0, n_b)), not
+//                                               zd[j]: the columns are a list, n_dst its length
 #pragma once
+#include <type_traits>
 #include "dot_lanes.h"
 #include "rank_key.h"
 
@@ -40,6 +48,12 @@ constexpr int TK_TARGET_WORKGROUPS = 512;                // two per CU of an MI3
 
 // keys no score has (both are bit patterns of negative NaNs under rank_key): not a candidate / a NaN score
 constexpr uint32_t TK_KEY_OUT = 0xffffffffu, TK_KEY_NAN = 0xfffffffeu, TK_KEY_LAST = 0xff800000u /* -inf */;
+
+// the optional constants of a consumer (file header)
+template <class C, class = void> struct tile_hooks : std::false_type {};
+template <class C> struct tile_hooks<C, std::void_t<decltype(C::TILE_HOOKS)>> : std::bool_constant<C::TILE_HOOKS> {};
+template <class C, class = void> struct gather_b : std::false_type {};
+template <class C> struct gather_b<C, std::void_t<decltype(C::GATHER_B)>> : std::bool_constant<C::GATHER_B> {};
 
 // four columns k .. k + 3 of a table row (zeros past F); VEC: one 16-byte load (F % 4 == 0, aligned rows)
 template <bool VEC>
@@ -71,6 +85,8 @@ struct ScoreTileArgs {
     const int32_t* __restrict__ ex_col;
     int no_loops, tiles_per_split;
     int32_t* __restrict__ status;
+    const int64_t* __restrict__ brows = nullptr;         // GATHER_B consumers only: the B row id of every column, ids in [0, n_b)
+    int n_b = 0;
 };
 
 // the producer's LDS: 2 x 27 KiB staging + 34 KiB keys + 1.25 KiB row state
@@ -156,6 +172,17 @@ __device__ __forceinline__ void score_tiles(const ScoreTileArgs& a, ScoreTileSha
             return;
         }
         const int64_t j0 = (int64_t)tile * TK_BN + srow;
+        if constexpr (gather_b<Consumer>::value) {
+            auto brow = [&](int64_t j) {
+                const int64_t id = j < n_dst ? a.brows[j] : -1;
+                return (uint64_t)id < (uint64_t)a.n_b ? load_k4<VEC>(zd + id * ldd, kk, F) : z;
+            };
+            rb0 = brow(j0);
+            rb1 = brow(j0 + 32);
+            rb2 = brow(j0 + 64);
+            rb3 = brow(j0 + 96);
+            return;
+        }
         rb0 = j0 + 0 < n_dst ? load_k4<VEC>(zd + (j0 + 0) * ldd, kk, F) : z;
         rb1 = j0 + 32 < n_dst ? load_k4<VEC>(zd + (j0 + 32) * ldd, kk, F) : z;
         rb2 = j0 + 64 < n_dst ? load_k4<VEC>(zd + (j0 + 64) * ldd, kk, F) : z;
@@ -241,6 +268,7 @@ __device__ __forceinline__ void score_tiles(const ScoreTileArgs& a, ScoreTileSha
         }
 
         // ---- every wavefront its 16 rows: exclusions and the loop column, then the consumer
+        if constexpr (tile_hooks<Consumer>::value) consumer.tile_begin(c0, cn, wave, lane);
         const int v_next = sh.ex_next[rl];                                        // (row r's is written in row r's turn only)
         auto one_row = [&](int rr) {
             const int r = wave * TK_ROWS_PER_WAVE + rr;
@@ -273,6 +301,7 @@ __device__ __forceinline__ void score_tiles(const ScoreTileArgs& a, ScoreTileSha
         } else {
             for (int rr = 0; rr < TK_ROWS_PER_WAVE; ++rr) one_row(rr);
         }
+        if constexpr (tile_hooks<Consumer>::value) consumer.tile_end(sh, c0, cn, wave, lane);
         // (the next write of `keys` comes after the barriers of the next tile's k-steps: nk >= 1)
     }
 }

@@ -77,11 +77,14 @@ def raise_on_status(values) -> None:
         raise IndexError("pair_scores / link_loss: a pair holds an id outside its embedding table: its logit, coefficient and loss "
                          "term are 0 (npi_pair_score; torch's indexing raises here) -- or EdgeSplitter / to_undirected: a column "
                          "holds an id outside its range: it was dropped (npi_split_permute / npi_split_undirected) -- or link_ranks: "
-                         "a query pair holds an id outside its table: its counts are -1 (npi_link_ranks)")
+                         "a query pair holds an id outside its table: its counts are -1 (npi_link_ranks) -- or link_log_softmax / "
+                         "listwise_loss: such a pair has lp = 0 and adds to no sum or gradient (npi_softmax_link_fwd)")
     if any(int(v) & _lib.NPI_STATUS_BAD_SCORE for v in values):
         raise ValueError("Input contains NaN: rank_metrics / roc_auc_score and their kin were given a NaN score; the metrics and "
                          "the curve of that call are undefined (npi_rank_metrics; sklearn raises here) -- or topk_links / link_ranks "
-                         "met a NaN score: it was not returned or counted, a NaN target's counts are -1 (npi_topk_links / npi_link_ranks)")
+                         "met a NaN score: it was not returned or counted, a NaN target's counts are -1 (npi_topk_links / npi_link_ranks) "
+                         "-- or link_log_softmax / listwise_loss met one among the candidates of a query: its lp is NaN "
+                         "(npi_softmax_link_fwd)")
     if any(int(v) & _lib.NPI_STATUS_BAD_LABEL for v in values):
         raise ValueError("rank_metrics / roc_auc_score and their kin: a label other than 0 / 1; it counted as 0 "
                          "(npi_rank_metrics; sklearn's binary metrics raise here)")
