@@ -640,6 +640,62 @@ int npi_gat_dropout_keep(const int32_t* rowptr, const int32_t* col, const int32_
                          int64_t key, int64_t threshold, float scale, float* keep, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DropEdge (PyG 1.4.2 torch_geometric.utils.dropout_adj): seeded edge dropout as a SORT-FREE filter of both CSR sides.  A side is
+ * ordered by (row, list order) and dropping entries keeps that order, so the dropped graph's sides are a stream compaction of the
+ * parent's -- no radix sort, no renumbering of the columns, nothing read back, and a step is reproducible from (seed, draw, tick).
+ *
+ * Rule E (the generator of the other rules, npi_gnn_amd/csrc/draw.h; wrapping uint64 throughout):
+ *     key    = epoch_seed(seed, draw)                       as every other rule
+ *     root   = mix64(mix64(key) + 8 G)                      draw_root(key, DRAW_RULE_E)
+ *     root_t = mix64(root + G (tick + 1))                   tick: an optional DEVICE int64 word, 0 when none is given (as Rule N)
+ *     directed:    k = e, the column of edge_index (0 <= e < n_edges);     word = mix64(mix64(root_t ^ (k C)) + G)
+ *     undirected:  k = 2^32 min(u, v) + max(u, v), (u, v) the column's ends; word = mix64(mix64(root_t ^ (k C)) + 2 G)
+ *                  (min / max of the int64 ends, then wrapping uint64: (u, v), (v, u) and every parallel duplicate share a word)
+ *     T      = floor(p 2^64)          exact integers on the host, as Rule D: int(Fraction(p) * 2**64); 0 <= p < 1
+ *     column dropped  <=>  word < T
+ * The calls take key and T = `threshold` (the int64_t with the same 64 bits), never p.  T = 0 drops nothing.
+ * On a CSR side an entry is subject to the rule iff 0 <= eid < n_edges: directed, its slot is its eid; undirected, its slot comes
+ * from (rowidx[p], col[p]), the same pair on both sides.  Every other entry is kept: the self loop the build appends (eid < 0) and
+ * the root entries of a combined side (eid >= n_edges).  Kept entries keep their order AND the parent's column number in eid, so an
+ * [E]-long edge_weight still lines up, npi_segmax's arg still names parent columns and Rule D's mask of an edge is unchanged.
+ * In numpy (uint64 arrays wrap):
+ *     root_t = mix64(mix64(mix64(uint64(key)) + 8 * G) + G * (tick + 1))
+ *     k = arange(E) if directed else (minimum(u, v).astype(uint64) << 32) + maximum(u, v).astype(uint64)
+ *     keep = mix64(mix64(root_t ^ (k * C)) + G * (1 if directed else 2)) >= T
+ * Known answers (seed 0, draw 0): key = 0xe220a8397b1dcdaf, root = 0x3500c0e53fa8015b, root_t = 0x6ca685ee2acaed88 (tick 0),
+ * 0x7eeb741d67e7ca58 (tick 1); tick 0, directed, slots 0, 1: 0x7f2790ca6cae07ac, 0x4836408e21e38141; undirected, slots 0, 1 (the
+ * pairs (0, 0), (0, 1)): 0xa7db0d37986c2656, 0x37f4d516f27ca8a6.  T(0.5) = 2^63, T(0.3) = 5534023222112865280,
+ * T(1 - 2^-53) = 18446744073709549568.
+ *
+ *   npi_csr_drop_side : the side (rowptr [N + 1], col / eid / rowidx [nnz_max], nnz = rowptr[N] read on the device; entries at or
+ *       behind nnz are never touched or counted) with the dropped entries removed: rowptr_o [N + 1] (rowptr_o[N] = the number
+ *       kept), col_o / eid_o / rowidx_o [nnz_max_out] compacted, item_row_o cut for capacity nnz_max_out and item_edges (64 or
+ *       NPI_ITEM_EDGES).  nnz_max_out >= nnz_max is required and always enough, so nothing is read back.  Parallel over entries
+ *       (one wavefront per 256): a hub row costs what its entries cost.  The outputs must not be the inputs.
+ *   npi_drop_edge_list : the rule over the COLUMNS of an edge list (src, dst int64 [E]); every column takes part, (i, i) and
+ *       (-1, -1) columns included.  The kept columns compacted in input order into out_src / out_dst [E]; newpos [E] (or NULL):
+ *       the new position of column e, -1 if dropped; count: the number kept (int32 device word).  pad_tail != 0: the columns behind
+ *       the kept ones are (-1, -1), the padding npi_filter_adj writes and npi_csr_build_ex drops.  Not in place.
+ *   npi_drop_edge_keep : keep [E] uint8, 1 = kept: the decision itself, for tests and composed variants (src / dst may be NULL
+ *       in directed mode).
+ *   npi_drop_edges_workspace_elems(n) : int32 words of `workspace` for the two compactions over n entries / columns (-1: bad n).
+ * flags: NPI_DROP_UNDIRECTED.  NPI_ERR_ARG before anything is launched: a null pointer, a bad size or item size, an unknown flag,
+ * nnz_max_out < nnz_max, a workspace that is NULL, not aligned to 4 bytes or shorter than the query says.
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_DROP_UNDIRECTED 1
+int64_t npi_drop_edges_workspace_elems(int64_t n);
+int npi_csr_drop_side(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const int32_t* rowidx, int64_t N,
+                      int64_t nnz_max, int64_t n_edges, int64_t key, const int64_t* tick /* device word, or NULL */,
+                      int64_t threshold, int flags, int64_t nnz_max_out, int64_t item_edges, int32_t* rowptr_o, int32_t* col_o,
+                      int32_t* eid_o, int32_t* rowidx_o, int32_t* item_row_o, int32_t* workspace, int64_t workspace_elems,
+                      void* stream);
+int npi_drop_edge_list(const int64_t* src, const int64_t* dst, int64_t E, int64_t key, const int64_t* tick, int64_t threshold,
+                       int flags, int64_t* out_src, int64_t* out_dst, int32_t* newpos, int32_t* count, int pad_tail,
+                       int32_t* workspace, int64_t workspace_elems, void* stream);
+int npi_drop_edge_keep(const int64_t* src, const int64_t* dst, int64_t E, int64_t key, const int64_t* tick, int64_t threshold,
+                       int flags, uint8_t* keep, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Between-layer steps of Net_1 (reference src/classes.py:63-64,67-68,71-72),
  * forward only: PyG 1.4.2 TopKPooling(ratio) and the [global_max_pool || global_mean_pool] readout.
  * `batch` is the PyG Batch vector (int64, non-decreasing); graph_ptr[B+1] its segment starts.

@@ -53,7 +53,8 @@ NPI_TOPK_MAX = 128               # largest k of npi_topk_links
 NPI_TOPK_NO_LOOPS = 1            # flag of npi_topk_links: one id space, (v, v) is no candidate
 NPI_LINK_RANK_NO_LOOPS = 1       # flag of npi_link_ranks: one id space, (v, v) is no competitor
 NPI_SOFTMAX_LINK_NO_LOOPS = 1    # flag of npi_softmax_link_*: one id space, (v, v) is no candidate (unless it is the target)
-NPI_HUB_MAX = 128               # hubs per plan (npi_hub_plan; mask words of NPI_HUB_MAX / 32 per source row)
+NPI_DROP_UNDIRECTED = 1         # flag of npi_csr_drop_side / npi_drop_edge_*: Rule E keyed on the column's unordered pair of ends
+NPI_HUB_MAX = 128              # hubs per plan (npi_hub_plan; mask words of NPI_HUB_MAX / 32 per source row)
 
 
 def NPI_GEMM_RESERVE_CUS(n: int) -> int:
@@ -217,6 +218,11 @@ PROTOTYPES = {
     "npi_segmax_workspace_bytes": (_I, [_I, _I, _I]),
     "npi_segmax": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
     "npi_segmax_bwd": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P]),
+    # DropEdge under Rule E: key, tick (device word or NULL), threshold (the uint64's bits), flags
+    "npi_drop_edges_workspace_elems": (_I, [_I]),
+    "npi_csr_drop_side": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, c_int, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "npi_drop_edge_list": (c_int, [_P, _P, _I, _I, _P, _I, c_int, _P, _P, _P, _P, c_int, _P, _I, _P]),
+    "npi_drop_edge_keep": (c_int, [_P, _P, _I, _I, _P, _I, c_int, _P, _P]),
 }
 
 _lib = None

@@ -22,6 +22,7 @@ enum DrawRule : uint64_t {
     DRAW_RULE_S = 5,                                       // Rule S: the order of a split            (npi_split_permute)
     DRAW_RULE_D = 6,                                       // Rule D: the attention-dropout mask      (npi_gat_*_dropout)
     DRAW_RULE_N = 7,                                       // Rule N: the standard normal, gauss.h      (npi_gauss_*)
+    DRAW_RULE_E = 8,                                       // Rule E: DropEdge, per column / per pair (npi_csr_drop_side, npi_drop_edge_*)
 };
 
 __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
@@ -54,6 +55,18 @@ __host__ __device__ __forceinline__ int drop_keep_bits(uint64_t root, uint64_t t
 #pragma unroll
     for (int h = 0; h < NH; ++h) bits |= drop_kept(stream, h, threshold) ? (1 << h) : 0;
     return bits;
+}
+
+// Rule E, DropEdge: a pure function of (key, tick, column) -- or, undirected, of (key, tick, the column's unordered pair of ends).
+// root_t = draw_word(draw_root(key, DRAW_RULE_E), tick + 1), the tick word read as Rule N reads it.  Directed: slot e, word 1;
+// undirected: slot 2^32 min(u, v) + max(u, v) (wrapping uint64 of the int64 ends), word 2.  DROPPED iff word < threshold.
+__host__ __device__ __forceinline__ uint64_t edge_pair_slot(int64_t u, int64_t v) {
+    const int64_t lo = u < v ? u : v, hi = u < v ? v : u;
+    return ((uint64_t)lo << 32) + (uint64_t)hi;
+}
+__host__ __device__ __forceinline__ bool edge_dropped(uint64_t root_t, bool undirected, int64_t e, int64_t u, int64_t v, uint64_t threshold) {
+    const uint64_t k = undirected ? edge_pair_slot(u, v) : (uint64_t)e;
+    return draw_word(draw_stream(root_t, k), undirected ? 2 : 1) < threshold;
 }
 
 // is x a column of row `row`?  Rows ascend; empty rows, rows of one entry and rows with repeated columns all occur.

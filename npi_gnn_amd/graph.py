@@ -378,6 +378,7 @@ class CSRGraph:
             build_side(self._dst, self._src, self.num_nodes, self.num_nodes, self.self_loops, drop_equal=not self.keep_equal,
                        item=self._item, sort_columns=self.sort_columns)
         self._by_src: Optional[CSRSide] = None
+        self.dropped_from: Optional["CSRGraph"] = None      # the graph whose edges ``drop_edges`` dropped to make this one
 
     @property
     def by_src(self) -> CSRSide:
@@ -385,6 +386,24 @@ class CSRGraph:
             self._by_src = build_side(self._src, self._dst, self.num_nodes, self.num_nodes, self.self_loops,
                                       drop_equal=not self.keep_equal, item=self.by_dst.item, sort_columns=self.sort_columns)
         return self._by_src
+
+    def drop_edges(self, p: float, seed: int = 0, draw: int = 0, tick: Optional[torch.Tensor] = None, undirected: bool = False,
+                   training: bool = True, out: Optional["CSRGraph"] = None) -> "CSRGraph":
+        """DropEdge (PyG's ``dropout_adj`` in front of a conv) WITHOUT a sort: a new ``CSRGraph`` over the same ``edge_index`` whose two
+        sides are this graph's with the dropped entries removed (``npi_csr_drop_side``, Rule E of ``include/npi_gnn.h``: column e is
+        dropped iff a word that is a pure function of ``(seed, draw, tick, e)`` lies below ``floor(p 2^64)``).  The kept entries keep
+        their order and THIS graph's column numbers, so an ``[E]``-long ``edge_weight`` still lines up (the gradient w.r.t. a dropped
+        edge's weight is 0), ``segmax``'s ``arg`` names the same columns and a GATConv's Rule D mask of an edge is unchanged.  Nothing
+        is read back; both sides keep this graph's capacity and item size and never get a hub plan.
+
+        ``p`` in ``[0, 1)`` (PyG's ``p = 1`` is refused); ``p == 0`` or ``training=False``: this graph itself.  ``tick``: None, or a
+        one-element int64 DEVICE tensor the kernels read -- a captured step draws a new mask per replay by counting it up.
+        ``undirected``: the rule is keyed on the column's unordered pair of ends, so ``(u, v)``, ``(v, u)`` and parallel duplicates
+        go together; ``symmetric`` stays True only then.  ``out``: a graph an earlier ``drop_edges`` of this very graph returned --
+        its arrays are reused and what was derived from them is dropped.  Existing ``(i, i)`` columns have no entry on either side
+        (the build drops them), so they are not subject to DropEdge: their weight remains the node's loop weight."""
+        from .dropedge import drop_edges_csr
+        return drop_edges_csr(self, p, seed, draw, tick, undirected, training, out)
 
     def built_from(self, edge_index: torch.Tensor, num_nodes: Optional[int] = None) -> bool:
         """True while ``edge_index`` is still the tensor this CSR was built from: same storage, same shape and, above all,
@@ -441,6 +460,14 @@ class BipartiteGraph:
         self._by_src: Optional[CSRSide] = None
         self._root = None                       # (res_n_id storage, _version, shape) -> the combined by-source side (root_side)
         self._pair = None                       # the one-id-space side of the list read as pairs (pair_side)
+        self.dropped_from: Optional["BipartiteGraph"] = None     # the graph whose edges ``drop_edges`` dropped to make this one
+
+    def drop_edges(self, p: float, seed: int = 0, draw: int = 0, tick: Optional[torch.Tensor] = None, undirected: bool = False,
+                   training: bool = True, out: Optional["BipartiteGraph"] = None) -> "BipartiteGraph":
+        """``CSRGraph.drop_edges`` for two id spaces (directed mode only: ``undirected=True`` is a ``ValueError``).  ``root_side`` of
+        the result is the drop of this graph's ``root_side`` -- the root entries are never dropped --, its ``pair_side`` raises."""
+        from .dropedge import drop_edges_bipartite
+        return drop_edges_bipartite(self, p, seed, draw, tick, undirected, training, out)
 
     @property
     def by_src(self) -> CSRSide:

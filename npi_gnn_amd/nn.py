@@ -24,6 +24,7 @@ from torch.nn import Parameter
 
 from . import functional as F_
 from ._draw import next_draw
+from .dropedge import DropEdge  # noqa: F401  (the module lives beside the rule it applies; exported here with the layers)
 from .graph import BipartiteGraph, CSRGraph, GraphBatch, as_graph
 from .schedule import DEFAULT, Schedule
 
@@ -251,6 +252,9 @@ class GCNConv(nn.Module):
         if isinstance(x, GraphBatch):
             gb = _only_batch(x, edge_index, "GCNConv")
             return gb.with_x(self.forward(gb.x, gb.graph() if self.normalize else gb.edge_index, edge_weight))
+        if self.cached and getattr(edge_index, "dropped_from", None) is not None:
+            raise ValueError("GCNConv(cached=True) keeps the normalisation of ONE graph: a graph that drop_edges returned changes "
+                             "every step (and has its parent's num_edges, so the cache could not tell) -- use cached=False")
         if edge_weight is not None and edge_weight.requires_grad and torch.is_grad_enabled():
             # a differentiable weight: the normalisation is part of the graph of this very call, not a constant to keep
             if self.cached:
