@@ -1579,6 +1579,80 @@ int npi_segmax_bwd(const int32_t* rowptr, const int32_t* col, const int32_t* eid
                    const float* dout, int64_t ldd, const int32_t* arg, int64_t lda, int64_t F,
                    float* dx, int64_t ldx, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-graph readouts: the rest of PyG 1.4.2's `nn.glob` next to npi_readout_max_mean -- `global_add_pool`, `global_sort_pool`
+ * (DGCNN's SortPooling, the readout of SEAL) and the softmax + weighted sum of `GlobalAttention`, forward and backward.  None of them
+ * builds a [B, n_max, F] dense batch or an [N] alpha array, none uses a float atomic.
+ *
+ * graph_ptr [B + 1] (int32, non-decreasing) are the segment starts: graph g owns rows [graph_ptr[g], graph_ptr[g + 1]), n_g of them.
+ *
+ * RULE O -- out of an f32 table x [N, F] and graph_ptr.
+ *   O-add.   out[g, c] = sum of x[i, c] over the rows of g; an empty graph gives 0.
+ *            Backward: dx[i] = dout[g(i)]; rows outside [graph_ptr[0], graph_ptr[B]) are written as zeros (no fill launch).
+ *   O-sort.  key_i = x[i, F - 1], every NaN written as 0x7fc00000 (npi_sort_pool_keys).  The rows of a graph are ordered by key
+ *            descending in the bit order of npi_topk_select: NaN above +inf, +0.0 above -0.0, equal bits by ascending row index --
+ *            TopKPooling's order, taken with ratio = 1.0 (ceil(1.0f n) = n exactly below 2^24 rows per graph).
+ *            out[g, r F : (r + 1) F] = x[row of rank r in g] for r < min(k, n_g), zeros for n_g <= r < k; out is [B, k F] and rows
+ *            are copied bit for bit.  DEVIATION from PyG: PyG fills the dense batch with x.min() - 1 and afterwards zeroes EVERY
+ *            cell that equals that value; here only the padding is zero.
+ *            Backward: dx[i] = dout[g, r F : (r + 1) F] if row i has rank r < k, else zeros; every row of dx is written, each from
+ *            at most one slot.  No gradient flows through the order.
+ *   O-att.   gate [N] f32.  PyG's softmax(gate, batch): m_g = max gate_i, e_i = exp(gate_i - m_g), s_g = sum e_i,
+ *            alpha_i = e_i / (s_g + 1e-16);  out[g] = sum alpha_i x_i; an empty graph gives zeros (m_g = s_g = 0).
+ *            Backward, with c_g = <dout_g, out_g> from the SAVED out:  dx_i = alpha_i dout_g,  dgate_i = alpha_i (<dout_g, x_i> - c_g).
+ *            The forward keeps m [B], s [B] and out [B, F] per graph; alpha is recomputed from them, never stored.
+ *   Order.   The sums of O-add and O-att are taken in an order that is a function of n_g alone.  With C = NPI_READOUT_CHUNK, chunk q of
+ *            a graph is its rows [q C, min(n_g, (q + 1) C)) (counted from the graph's first row); inside a chunk, lane l of 16 adds
+ *            the rows l, l + 16, ... ascending from 0.0f; the chunk's partial is lane 0 + lane 1 + ... + lane 15 ascending; the
+ *            graph's sum is partial 0 + partial 1 + ... ascending.  O-att computes a chunk relative to the chunk's own maximum m_q
+ *            (terms fma(exp(gate_i - m_q), x[i, c], .), s_q the same sum of the exps) and merges with the online-softmax rescale:
+ *            m = max m_q, s = sum s_q exp(m_q - m), acc = sum acc_q exp(m_q - m) ascending (fma), out = acc / (s + 1e-16); a graph
+ *            of one chunk is acc_0 / (s_0 + 1e-16).
+ * In numpy, per graph with rows r = x[b:e] (float32 arithmetic throughout; g8 = gate[b:e]):
+ *     lanes = lambda v: reduce(add, [reduce(add, v[l::16], float32(0)) for l in range(16)])   # v: the chunk's terms, [n, F] or [n]
+ *     add   = reduce(add, [lanes(r[q:q + C]) for q in range(0, e - b, C)])                     # e == b: zeros
+ *     order = sorted(range(b, e), key=lambda i: (-bits(key_i), i))                             # bits(): ascending-orderable uint32
+ *     m_q, e_q = g8[q:q + C].max(), exp(g8[q:q + C] - m_q);  s_q, acc_q = lanes(e_q), lanes(e_q[:, None] * r[q:q + C])
+ *     m = max(m_q);  out = sum_q(acc_q * exp(m_q - m)) / (sum_q(s_q * exp(m_q - m)) + 1e-16)
+ * Consequences: the bits of out[g] depend only on the rows of graph g -- not on B, on where the graph sits in the batch, on the
+ * pitch or alignment of x (columns always travel in groups of 4 columns per thread; only the load width changes), or on the launch
+ * geometry.  The backward of O-att sums its two dot products with lane l owning columns 4 l .. 4 l + 3 (+ 256 j) and the 64 lanes
+ * added by an xor butterfly: a function of F alone.  No float atomics anywhere.
+ *
+ *   x, out, dout, dx : unit column stride, a pitch (elements) >= F each (out / dout of the sort pool: >= k F).  Rows are read and
+ *                      written 16 / 8 / 4 bytes per lane: the widest that F, every pitch and every base pointer of the call allow
+ *   workspace        : npi_readout_{add,attention}_workspace_bytes(N, B, F) bytes, 16-byte aligned, caller-owned; needs no clearing.
+ *                      It holds the chunk scan and the partials of the N / C + B workgroups (a bound known on the host)
+ *   order, remap     : perm and remap of npi_topk_select / npi_topk_select_sorted run on the keys with ratio 1.0 (out_ptr is then
+ *                      graph_ptr, which must start at 0): order[graph_ptr[g] + r] = the row of rank r, remap[i] = graph_ptr[g] + rank
+ * Nothing is allocated, nothing read back: every call may run inside a stream capture.  Refused with NPI_ERR_ARG before any launch,
+ * the text of npi_last_error() starting with the entry point's name: N or B outside [0, 2^31 - 1), F <= 0, k <= 0, a pitch below
+ * F (k F), a negative workspace length; with N > 0 and B > 0 also a null pointer and a workspace that is misaligned or shorter than
+ * the query says.  N == 0 or B == 0 returns NPI_OK without a launch (the caller zero-fills what it wants to read).  The workspace
+ * queries return -1 for a bad size.
+ *
+ * Out of scope: Set2Set, bf16 storage, SortPooling's 1-D conv head, `min_score` / SAGPooling, gradients through the sort.
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_READOUT_CHUNK 1024
+int64_t npi_readout_add_workspace_bytes(int64_t N, int64_t B, int64_t F);         /* -1: bad size */
+int npi_readout_add(const float* x, int64_t ldx, const int32_t* graph_ptr, int64_t N, int64_t B, int64_t F,
+                    float* out /* [B, F] */, int64_t ldo, void* workspace, int64_t workspace_bytes, void* stream);
+int npi_readout_add_bwd(const float* dout, int64_t ldd, const int32_t* graph_ptr, int64_t N, int64_t B, int64_t F,
+                        float* dx /* [N, F] */, int64_t lddx, void* stream);
+int64_t npi_readout_attention_workspace_bytes(int64_t N, int64_t B, int64_t F);   /* -1: bad size */
+int npi_readout_attention(const float* gate, const float* x, int64_t ldx, const int32_t* graph_ptr, int64_t N, int64_t B, int64_t F,
+                          float* out /* [B, F] */, int64_t ldo, float* m /* [B] */, float* s /* [B] */,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+int npi_readout_attention_bwd(const float* gate, const float* x, int64_t ldx, const int32_t* graph_ptr, int64_t N, int64_t B,
+                              int64_t F, const float* out, int64_t ldo, const float* m, const float* s,
+                              const float* dout, int64_t ldd, float* dx /* [N, F] */, int64_t lddx, float* dgate /* [N] */,
+                              void* stream);
+int npi_sort_pool_keys(const float* x, int64_t ldx, int64_t N, int64_t F, float* keys /* [N] */, void* stream);
+int npi_sort_pool_gather(const float* x, int64_t ldx, const int32_t* order, const int32_t* graph_ptr, int64_t N, int64_t B,
+                         int64_t F, int64_t k, float* out /* [B, k F] */, int64_t ldo, void* stream);
+int npi_sort_pool_bwd(const float* dout, int64_t ldd, const int32_t* remap, const int32_t* graph_ptr, int64_t N, int64_t B,
+                      int64_t F, int64_t k, float* dx /* [N, F] */, int64_t lddx, void* stream);
+
 /* Evaluation loop(reference src/methods.py:87-105 compares one element per Python
  * iteration, one device sync each).  counts[4] += [TP, FN, TN, FP] for pred = first arg-max of scores[i, 0..C):
  * pred 1 & y 1 -> TP, pred 1 & y 0 -> FP, pred 0 & y 1 -> FN, anything else -> TN (the reference's else

@@ -218,6 +218,16 @@ PROTOTYPES = {
     "npi_segmax_workspace_bytes": (_I, [_I, _I, _I]),
     "npi_segmax": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
     "npi_segmax_bwd": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P]),
+    # readouts under Rule O: x, ldx, graph_ptr, N, B, F, out, ldo, workspace, bytes | ... m, s ... | order / remap, k
+    "npi_readout_add_workspace_bytes": (_I, [_I, _I, _I]),
+    "npi_readout_add": (c_int, [_P, _I, _P, _I, _I, _I, _P, _I, _P, _I, _P]),
+    "npi_readout_add_bwd": (c_int, [_P, _I, _P, _I, _I, _I, _P, _I, _P]),
+    "npi_readout_attention_workspace_bytes": (_I, [_I, _I, _I]),
+    "npi_readout_attention": (c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
+    "npi_readout_attention_bwd": (c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
+    "npi_sort_pool_keys": (c_int, [_P, _I, _I, _I, _P, _P]),
+    "npi_sort_pool_gather": (c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
+    "npi_sort_pool_bwd": (c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     # DropEdge under Rule E: key, tick (device word or NULL), threshold (the uint64's bits), flags
     "npi_drop_edges_workspace_elems": (_I, [_I]),
     "npi_csr_drop_side": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, c_int, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),

@@ -314,16 +314,6 @@ __device__ __forceinline__ void store_vec(float* __restrict__ p, const float (&v
     *reinterpret_cast<typename VecLoad<VEC>::T*>(p) = t;
 }
 
-// widest VEC in {4, 2, 1} that divides F and every leading dimension and keeps every base pointer aligned
-static int pool_vec(int64_t F, std::initializer_list<int64_t> lds, std::initializer_list<const void*> ptrs) {
-    for (int v = 4; v > 1; v >>= 1) {
-        bool ok = F % v == 0;
-        for (int64_t l : lds) ok = ok && l % v == 0;
-        for (const void* p : ptrs) ok = ok && ((uintptr_t)p % (v * sizeof(float))) == 0;
-        if (ok) return v;
-    }
-    return 1;
-}
 static int pool_groups_per_block(int64_t F, int vec) { return (int)std::min<int64_t>(ceil_div(F, vec), POOL_THREADS); }
 
 // readout[g] = [max over the graph's rows || mean over the graph's rows]; an empty graph gives zeros

@@ -4,13 +4,27 @@
 //   PairSort             stable LSD radix sort of n (uint32 key, int32 val) pairs inside a caller's workspace
 //   exclusive_scan_i32   exclusive scan of an int32 array of any length, in place (three launches)
 //   block_exclusive_scan exclusive scan over the threads of ONE workgroup (a device helper for a client's own kernels)
+//   pool_vec             the load width of the row kernels that walk graphs by segment starts (pool.hip, readout.hip)
 #pragma once
+#include <initializer_list>
 #include "npi_common.h"
 
 namespace npi {
 
 // bits that hold every id in [0, n); at least 1
 int key_bits(int64_t n);
+
+// floats per load of the row kernels of pool.hip and readout.hip: the widest of {4, 2, 1} that divides F and every leading dimension
+// and keeps every base pointer aligned
+inline int pool_vec(int64_t F, std::initializer_list<int64_t> lds, std::initializer_list<const void*> ptrs) {
+    for (int v = 4; v > 1; v >>= 1) {
+        bool ok = F % v == 0;
+        for (int64_t l : lds) ok = ok && l % v == 0;
+        for (const void* p : ptrs) ok = ok && ((uintptr_t)p % (v * sizeof(float))) == 0;
+        if (ok) return v;
+    }
+    return 1;
+}
 
 // Every client: carve (a short workspace is the CALLER's error: it words the text and picks the status), write keys_a / vals_a with a
 // kernel of its own, sort; then -- for a second key -- rewrite keys_a from vals_a and sort again.

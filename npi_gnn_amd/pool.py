@@ -287,6 +287,262 @@ def global_mean_pool(x, batch, size=None):
     return global_max_mean_pool(x, batch, size)[:, x.size(1):]
 
 
+# ---- Rule O (include/npi_gnn.h): global_add_pool, global_sort_pool, GlobalAttention ---------------------------------------------
+READOUT_CHUNK = 1024             # NPI_READOUT_CHUNK: rows per workgroup; the order of every sum is a function of n_g and this alone
+
+
+def _rule_o_f32(who: str, **tensors) -> None:
+    for name, t in tensors.items():
+        if t.dtype != torch.float32:
+            raise NotImplementedError(f"{who}: {name} is {t.dtype}; the readouts run on float32 tables (bf16 storage is not implemented)")
+
+
+def _rows(t: torch.Tensor) -> torch.Tensor:
+    """a ``[n, F]`` table the kernels can walk with a pitch: unit column stride, rows at least ``F`` apart (a column block of a
+    wider tensor stays a view; anything else is copied)"""
+    if t.dim() != 2:
+        raise ValueError(f"expected a [rows, features] matrix, got {tuple(t.shape)}")
+    n, F = t.shape
+    if n > 1 and (F == 1 or t.stride(1) == 1) and t.stride(0) >= F:
+        return t
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _pitch(t: torch.Tensor) -> int:
+    return t.stride(0) if t.size(0) > 1 else t.size(1)
+
+
+def _segments(who: str, x, batch, num_graphs, **more):
+    """``(table, graph_ptr, GraphBatch or None, batch vector or None)`` of the two call forms; float32 is checked first"""
+    _rule_o_f32(who, x=x.x if isinstance(x, GraphBatch) else x, **more)
+    if isinstance(x, GraphBatch):
+        return x.x, x.segment_ptr(), x, x.batch
+    if batch is None:
+        raise TypeError("a readout needs the batch vector (or a GraphBatch)")
+    if batch.dtype == torch.int32:                            # segment starts [B + 1] instead of a batch vector
+        return x, batch.contiguous(), None, None
+    return x, graph_ptr(batch, num_graphs), None, batch
+
+
+def _add_fwd(x: torch.Tensor, gp: torch.Tensor) -> torch.Tensor:
+    dev = require_gpu(x, gp)
+    x = _rows(x.detach())
+    (N, F), B = x.shape, gp.numel() - 1
+    if N == 0 or B == 0:
+        return torch.zeros((B, F), dtype=torch.float32, device=dev)
+    lib = load()
+    out = torch.empty((B, F), dtype=torch.float32, device=dev)
+    n_ws = int(lib.npi_readout_add_workspace_bytes(N, B, F))
+    ws = torch.empty(max(n_ws, 16), dtype=torch.uint8, device=dev)
+    check(lib.npi_readout_add(ptr(x), _pitch(x), ptr(gp), N, B, F, ptr(out), F, ptr(ws), n_ws, stream_ptr(dev)), "npi_readout_add")
+    return out
+
+
+class _AddPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gp):
+        ctx.save_for_backward(gp)
+        ctx.rows = x.size(0)
+        return _add_fwd(x, gp)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (gp,) = ctx.saved_tensors
+        dev = dout.device
+        dout = _rows(dout)
+        (B, F), N = dout.shape, ctx.rows
+        if N == 0 or B == 0:
+            return torch.zeros((N, F), dtype=torch.float32, device=dev), None
+        dx = torch.empty((N, F), dtype=torch.float32, device=dev)     # rows outside every graph: zeroed by the kernel
+        check(load().npi_readout_add_bwd(ptr(dout), _pitch(dout), ptr(gp), N, B, F, ptr(dx), F, stream_ptr(dev)), "npi_readout_add_bwd")
+        return dx, None
+
+
+def global_add_pool(x, batch: Optional[torch.Tensor] = None, size: Optional[int] = None) -> torch.Tensor:
+    """PyG's ``global_add_pool(x, batch, size)`` -> ``[B, F]`` under Rule O-add: a fixed order of summation (bitwise reproducible,
+    independent of the batch around a graph), one workgroup per 1,024 rows of a graph; differentiable in ``x``.  ``x`` may be a
+    ``GraphBatch``.  ``size=None`` with a batch vector: one device read, as in PyG."""
+    x, gp, _, _ = _segments("global_add_pool", x, batch, size)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _AddPoolFn.apply(x, gp)
+    return _add_fwd(x, gp)
+
+
+def _sort_order(x: torch.Tensor, gp: torch.Tensor, batch: Optional[torch.Tensor], sizes: Optional[torch.Tensor],
+                selection: Optional[str] = None):
+    """``(perm, remap)`` of Rule O-sort: every graph's rows by last column descending, through TopKPooling's selection with ratio
+    1.0.  Graphs known to fit the LDS sort take ``npi_topk_select``; larger ones -- or unknown sizes with more than 16,384 rows in
+    all -- the radix selection, so nothing is ever read back.  ``selection`` ('lds' / 'radix') forces a path (tests)."""
+    lib = load()
+    dev = x.device
+    (N, F), B = x.shape, gp.numel() - 1
+    st = stream_ptr(dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    keys = torch.empty(N, dtype=torch.float32, device=dev)
+    check(lib.npi_sort_pool_keys(ptr(x), _pitch(x), N, F, ptr(keys), st), "npi_sort_pool_keys")
+    out_ptr, perm, remap = torch.empty(B + 1, **i32), torch.empty(N, **i32), torch.empty(N, **i32)
+    max_nodes = int(sizes.max()) if sizes is not None and sizes.numel() == B and B > 0 else 0
+    if selection is None:
+        selection = "radix" if (max_nodes > LDS_SORT_MAX_NODES or (max_nodes == 0 and N > LDS_SORT_MAX_NODES)) else "lds"
+    if selection == "radix":
+        if batch is None:                                    # only segment starts were given: the batch vector they stand for
+            batch = torch.repeat_interleave(torch.arange(B, device=dev), (gp[1:] - gp[:-1]).long(), output_size=N)
+        n_ws = int(lib.npi_topk_sorted_workspace_bytes(N))
+        ws = torch.empty(n_ws, dtype=torch.uint8, device=dev)
+        check(lib.npi_topk_select_sorted(ptr(keys), ptr(batch.contiguous()), ptr(gp), N, B, 1.0, ptr(out_ptr), ptr(perm), ptr(remap),
+                                         ptr(ws), n_ws, st), "npi_topk_select_sorted")
+    else:
+        status = torch.empty(1, **i32)
+        check(lib.npi_topk_select(ptr(keys), ptr(gp), N, B, 1.0, ptr(out_ptr), ptr(perm), ptr(remap), ptr(status), max_nodes, st),
+              "npi_topk_select")
+    return perm, remap
+
+
+def _sort_gather(x: torch.Tensor, gp: torch.Tensor, perm: torch.Tensor, k: int) -> torch.Tensor:
+    dev = x.device
+    (N, F), B = x.shape, gp.numel() - 1
+    out = torch.empty((B, k * F), dtype=torch.float32, device=dev)
+    check(load().npi_sort_pool_gather(ptr(x), _pitch(x), ptr(perm), ptr(gp), N, B, F, k, ptr(out), k * F, stream_ptr(dev)),
+          "npi_sort_pool_gather")
+    return out
+
+
+class _SortPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gp, perm, remap, k):
+        ctx.save_for_backward(gp, remap)
+        ctx.k, ctx.shape = k, tuple(x.shape)
+        return _sort_gather(_rows(x.detach()), gp, perm, k)
+
+    @staticmethod
+    def backward(ctx, dout):
+        gp, remap = ctx.saved_tensors
+        dev = dout.device
+        (N, F), B = ctx.shape, gp.numel() - 1
+        dout = _rows(dout)
+        dx = torch.empty((N, F), dtype=torch.float32, device=dev)     # every row is written: its slot, or zeros
+        check(load().npi_sort_pool_bwd(ptr(dout), _pitch(dout), ptr(remap), ptr(gp), N, B, F, ctx.k, ptr(dx), F, stream_ptr(dev)),
+              "npi_sort_pool_bwd")
+        return dx, None, None, None, None
+
+
+def global_sort_pool(x, batch: Optional[torch.Tensor] = None, k: int = 1, num_graphs: Optional[int] = None) -> torch.Tensor:
+    """PyG's ``global_sort_pool(x, batch, k)`` (DGCNN's SortPooling) -> ``[B, k * F]`` under Rule O-sort: each graph's rows by
+    their last feature, descending, in TopKPooling's order (ties by row index), the first ``k`` side by side, zero padded.  No
+    ``[B, n_max, F]`` dense batch is built.  Unlike PyG only the padding is zero (PyG also zeroes every cell equal to
+    ``x.min() - 1``).  Differentiable in ``x`` (not through the order).  ``x`` may be a ``GraphBatch``; with it or ``num_graphs``
+    nothing is read back."""
+    k = int(k)
+    if k <= 0:
+        raise ValueError(f"global_sort_pool: k must be positive, got {k}")
+    x, gp, gb, batch = _segments("global_sort_pool", x, batch, num_graphs)
+    dev = require_gpu(x, gp)
+    (N, F), B = x.shape, gp.numel() - 1
+    if N == 0 or B == 0:
+        return torch.zeros((B, k * F), dtype=torch.float32, device=dev)
+    xd = _rows(x.detach())
+    perm, remap = _sort_order(xd, gp, batch, gb.sizes if gb is not None else None)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _SortPoolFn.apply(x, gp, perm, remap, k)
+    return _sort_gather(xd, gp, perm, k)
+
+
+def _att_fwd(gate: torch.Tensor, x: torch.Tensor, gp: torch.Tensor):
+    dev = require_gpu(gate, x, gp)
+    x = _rows(x.detach())
+    gate = gate.detach().reshape(-1).contiguous()
+    (N, F), B = x.shape, gp.numel() - 1
+    if gate.numel() != N:
+        raise ValueError(f"attention_readout: {gate.numel()} gates for {N} rows")
+    f32 = dict(dtype=torch.float32, device=dev)
+    if N == 0 or B == 0:
+        return torch.zeros((B, F), **f32), torch.zeros(B, **f32), torch.zeros(B, **f32), x, gate
+    lib = load()
+    out, m, s = torch.empty((B, F), **f32), torch.empty(B, **f32), torch.empty(B, **f32)
+    n_ws = int(lib.npi_readout_attention_workspace_bytes(N, B, F))
+    ws = torch.empty(max(n_ws, 16), dtype=torch.uint8, device=dev)
+    check(lib.npi_readout_attention(ptr(gate), ptr(x), _pitch(x), ptr(gp), N, B, F, ptr(out), F, ptr(m), ptr(s), ptr(ws), n_ws,
+                                    stream_ptr(dev)), "npi_readout_attention")
+    return out, m, s, x, gate
+
+
+class _AttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gate, x, gp):
+        out, m, s, xc, gc = _att_fwd(gate, x, gp)
+        ctx.save_for_backward(gc, xc, gp, out, m, s)         # per graph: m, s and out -- no [N] alpha
+        ctx.gate_shape = tuple(gate.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        gate, x, gp, out, m, s = ctx.saved_tensors
+        dev = x.device
+        (N, F), B = x.shape, gp.numel() - 1
+        if N == 0 or B == 0:
+            return torch.zeros(ctx.gate_shape, dtype=torch.float32, device=dev), torch.zeros_like(x), None
+        dout = _rows(dout)
+        dx = torch.empty((N, F), dtype=torch.float32, device=dev)
+        dgate = torch.empty(N, dtype=torch.float32, device=dev)
+        check(load().npi_readout_attention_bwd(ptr(gate), ptr(x), _pitch(x), ptr(gp), N, B, F, ptr(out), F, ptr(m), ptr(s), ptr(dout),
+                                               _pitch(dout), ptr(dx), F, ptr(dgate), stream_ptr(dev)), "npi_readout_attention_bwd")
+        return dgate.view(ctx.gate_shape), dx, None
+
+
+def attention_readout(gate: torch.Tensor, x, batch_or_graph_ptr: Optional[torch.Tensor] = None,
+                      num_graphs: Optional[int] = None) -> torch.Tensor:
+    """``scatter_add(softmax(gate, batch) * x, batch)`` -> ``[B, F]`` under Rule O-att, the functional form of ``GlobalAttention``
+    (and the step Set2Set repeats): PyG's softmax ``exp(gate - max) / (sum + 1e-16)`` and the weighted sum in one pass, chunked
+    with the online-softmax rescale; differentiable in ``gate`` (``[N]`` or ``[N, 1]``) and ``x``.  The third argument is a batch
+    vector (int64) or segment starts (int32 ``[B + 1]``); ``x`` may be a ``GraphBatch``."""
+    x, gp, _, _ = _segments("attention_readout", x, batch_or_graph_ptr, num_graphs, gate=gate)
+    if torch.is_grad_enabled() and (x.requires_grad or gate.requires_grad):
+        return _AttentionFn.apply(gate, x, gp)
+    return _att_fwd(gate, x, gp)[0]
+
+
+def _reset(module) -> None:
+    """PyG 1.4.2's ``inits.reset``"""
+    if module is None:
+        return
+    children = list(module.children()) if hasattr(module, "children") else []
+    if children:
+        for child in children:
+            _reset(child)
+    elif hasattr(module, "reset_parameters"):
+        module.reset_parameters()
+
+
+class GlobalAttention(torch.nn.Module):
+    """PyG 1.4.2's ``GlobalAttention(gate_nn, nn=None)``: ``out_g = sum_i softmax(gate_nn(x))_i * nn(x)_i``.  ``gate_nn`` (to one
+    channel) and ``nn`` are ordinary torch modules; the softmax and the weighted sum are ``attention_readout``.  Same constructor,
+    ``forward(x, batch, size=None)``, ``reset_parameters`` and ``state_dict`` keys (``gate_nn.*``, ``nn.*``) as PyG's."""
+
+    def __init__(self, gate_nn, nn=None):
+        super().__init__()
+        self.gate_nn = gate_nn
+        self.nn = nn
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        _reset(self.gate_nn)
+        _reset(self.nn)
+
+    def forward(self, x, batch=None, size=None):
+        gb = x if isinstance(x, GraphBatch) else None
+        x = gb.x if gb is not None else x
+        x = x.unsqueeze(-1) if x.dim() == 1 else x
+        gate = self.gate_nn(x).view(-1, 1)
+        x = self.nn(x) if self.nn is not None else x
+        assert gate.dim() == x.dim() and gate.size(0) == x.size(0)
+        if gb is not None:
+            return attention_readout(gate, x, gb.segment_ptr())
+        return attention_readout(gate, x, batch, size)
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(gate_nn={self.gate_nn}, nn={self.nn})"
+
+
 class TopKPooling(nn.Module):
     """``TopKPooling(in_channels, ratio=0.5)``: parameter ``weight [1, in_channels]`` (PyG 1.4.2 layout,
     so ``pool1.weight`` of the reference checkpoints loads unchanged)."""
