@@ -807,6 +807,82 @@ int npi_subgraph_features(const float* feat, int64_t ldf, int64_t Ff, const int3
                           const int32_t* node_off, int64_t B, int64_t n, float* x, int64_t ldx, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Enclosing subgraphs: h-hop induced extraction with DRNL labels -- SEAL's data construction (Zhang & Chen, NeurIPS 2018; PyG's
+ * `seal_link_pred` example) over any undirected graph in one id space, where the entry points above restate the reference's
+ * one-hop star.  It follows the rule below, NOT the reference's own h-hop class, which is dead code.
+ *
+ * Rule H.  Inputs: edge_index [2, E] over N nodes holding every edge in both directions; an optional mask [E] (0: the column does
+ * not exist), equal on the two directions of an edge; keys [B, 2], one (u, v) per sample, u != v and both in [0, N); h >= 1 hops.
+ * Integer work throughout; the output is a pure function of these inputs.
+ *   1. Walkable. Column e = (j -> i) is walkable for sample g iff j != i, the mask allows e, and {i, j} != {u_g, v_g}: the target
+ *               link -- in either direction, every parallel copy -- is never walked and never emitted (no label leakage).
+ *   2. Nodes.   S_g = { w : min(d(u, w), d(v, w)) <= h }, d the BFS distance over walkable entries.
+ *   3. Order.   Local node 0 is u, local node 1 is v, the rest of S_g follows in ascending global id.
+ *   4. Edges.   For local a = 0 .. n_g - 1 in order: the walkable entries whose target is node_id[a] and whose source lies in S_g,
+ *               in ascending (source id, column number) order -- the order of a by-target CSR built with NPI_CSR_SORT_COLUMNS --,
+ *               each as (local(source) + off_g, a + off_g) with e_id = its column number; parallel duplicates as often as they
+ *               occur.  edge_dst comes out non-decreasing.  With NPI_ENCLOSE_ADD_TARGET_EDGE one (1 -> 0) column is put in front
+ *               of row 0's entries and one (0 -> 1) column in front of row 1's, both with e_id = -1, whether or not the graph had
+ *               the link (the reference's convention: positives and negatives both carry their target edge).
+ *   5. Labels.  Inside the sample, over its emitted entries with e_id >= 0: dist[w, 0] = the BFS distance from local 0 with local 1
+ *               removed (the source itself 0; node 1 and anything unreachable -1), dist[w, 1] = from local 1 with local 0 removed.
+ *               z = 1 for the two targets, 0 where either distance is -1, otherwise with d = du + dv
+ *                   z = 1 + min(du, dv) + (d / 2) * (d / 2 + d % 2 - 1)           (integer division; SEAL's DRNL), int64.
+ * A bad key (u == v, or an id outside [0, N)) gives an EMPTY sample -- 0 nodes, 0 edges -- and raises NPI_STATUS_BAD_ENCLOSE_KEY.
+ *
+ * The parent graph is passed as its by-target CSR: rowptr [N + 1], col, eid of npi_csr_build_ex(dst, src, ...) WITHOUT self loops,
+ * with NPI_CSR_DROP_EQUAL | NPI_CSR_SORT_COLUMNS ((i, i) columns dropped, a row's entries by source id); mask (uint8 [E], may be NULL) is looked up
+ * through eid.  One workgroup per sample; no synchronisation between workgroups, no spin-waits; every loop is bounded by its input.
+ *   workspace : npi_enclose_workspace_bytes(N, B) bytes (-1: bad size), 4-byte aligned, needs no clearing: per sample four bitmaps'
+ *               worth of ceil(N / 32) words -- visited, current, next and the exclusive popcount prefix of visited, from which
+ *               local(w) = 2 + rank(w) - [u < w] - [v < w].  npi_enclose_fill reads what npi_enclose_sizes left there: the two
+ *               calls of a batch share keys, flags, mask and workspace.
+ *   npi_enclose_sizes   : BFS marking, then counts[g] = n_g, counts[B + g] = e_g (the added target columns included) and their
+ *                         exclusive prefix sums node_off[B + 1] / edge_off[B + 1]; both totals are -1 when one passes 2^31 - 2.
+ *   npi_enclose_fill    : node_id [n] (int32), batch [n], edge_src / edge_dst / e_id [e] (int64, batch-global row ids), and the
+ *                         by-target CSR of the emitted entries over the batch's rows: local_rowptr [n + 1], local_col [e] (int32) --
+ *                         the entries are grouped by target already, so this is a counter, not a sort.  graph_ptr / edge_ptr
+ *                         [B + 1] (int32): node_off / edge_off as the consumers of the batch get them.  n_nodes / n_edges: the
+ *                         totals the CALLER sized the arrays with; when they are not node_off[B] / edge_off[B] nothing is
+ *                         written through the offsets: node 0 / graph 0 for every row, (-1, -1) with e_id -1 for every column,
+ *                         empty local rows, graph_ptr / edge_ptr = [0, n_nodes, n_nodes, ...] / [0, n_edges, ...] (one graph of the
+ *                         caller's size, the rest empty), and NPI_STATUS_BAD_ENCLOSE_TOTALS.
+ *   npi_drnl_label      : Rule H 5 over ANY batch of graphs given as a by-target CSR over the batch's n rows (nnz: the length of
+ *                         col): graph g = rows [graph_ptr[g], graph_ptr[g + 1]), targets src[g] / dst[g] (int32 row ids; both NULL:
+ *                         the graph's first two rows).  An entry whose source is its own row (a loop) or lies outside the graph is
+ *                         skipped; every index is clamped to the arrays.  z [n] int64, dist [n, 2] int32; rows outside every graph
+ *                         are not written.  A graph whose targets are equal or outside it gets z = 0, dist = -1.
+ *   npi_enclose_features: x[row] = [label | feat[node_id[row]][0 .. Ff)], pad columns up to ldx zero; label = float(z[row])
+ *                         (NPI_ENCLOSE_LABEL_DRNL), 0 for a sample's two targets and 1 elsewhere (NPI_ENCLOSE_LABEL_TARGETS, the
+ *                         reference's), or no column (NPI_ENCLOSE_LABEL_NONE; then Ff > 0).  Zero rows unless node_off[B] == n and
+ *                         edge_off[B] == e: the test of npi_enclose_fill.
+ * status (int32 device word, may be NULL) is OR-ed into, never cleared.  Refused with NPI_ERR_ARG before any launch: N outside
+ * [1, 2^31 - 1), B or a total outside its range, hops < 1, an unknown flag or label, a negative, short or misaligned workspace, a
+ * pitch below its width, a null pointer for anything that would be read or written.
+ * Out of scope: max_nodes_per_hop sampling, directed graphs, bf16 features.
+ * ------------------------------------------------------------------------------------------ */
+#define NPI_ENCLOSE_ADD_TARGET_EDGE 1
+#define NPI_ENCLOSE_LABEL_NONE 0
+#define NPI_ENCLOSE_LABEL_DRNL 1
+#define NPI_ENCLOSE_LABEL_TARGETS 2
+#define NPI_STATUS_BAD_ENCLOSE_KEY 4096
+#define NPI_STATUS_BAD_ENCLOSE_TOTALS 8192
+int64_t npi_enclose_workspace_bytes(int64_t N, int64_t B);
+int npi_enclose_sizes(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const uint8_t* mask, int64_t N,
+                      const int32_t* keys, int64_t B, int64_t hops, int flags, int32_t* counts /* [2 B] */, int32_t* node_off,
+                      int32_t* edge_off, void* workspace, int64_t workspace_bytes, int32_t* status, void* stream);
+int npi_enclose_fill(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const uint8_t* mask, int64_t N,
+                     const int32_t* keys, int64_t B, int flags, const int32_t* node_off, const int32_t* edge_off,
+                     void* workspace, int64_t workspace_bytes, int32_t* node_id, int64_t* batch, int64_t* edge_src,
+                     int64_t* edge_dst, int64_t* e_id, int32_t* local_rowptr, int32_t* local_col, int32_t* graph_ptr,
+                     int32_t* edge_ptr, int64_t n_nodes, int64_t n_edges, int32_t* status, void* stream);
+int npi_drnl_label(const int32_t* rowptr, const int32_t* col, int64_t n, int64_t nnz, const int32_t* src, const int32_t* dst,
+                   const int32_t* graph_ptr, int64_t B, int64_t* z /* [n] */, int32_t* dist /* [n, 2] */, void* stream);
+int npi_enclose_features(const float* feat, int64_t ldf, int64_t Ff, const int32_t* node_id, const int64_t* z,
+                         const int64_t* batch, const int32_t* node_off, const int32_t* edge_off, int64_t B, int64_t n,
+                         int64_t e, int label, float* x, int64_t ldx, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Neighbour sampling: the producer of the (x_src, None) / size= / res_n_id arguments of the bipartite layers.  Replaces, one hop
  * per sequence of calls, PyG 1.4.2 `torch_geometric.data.NeighborSampler.__produce_bipartite_data_flow__`:
  * `torch_cluster.neighbor_sampler(n_id, cumdeg, size)`, `torch.unique` over the sampled sources and the `tmp[n_id] = arange`

@@ -23,9 +23,11 @@ from .topk import KnownLinks, topk_links  # noqa: F401
 from .link_rank import LinkRanks, link_ranks, ranking_metrics  # noqa: F401
 from .softmax_link import link_log_softmax, listwise_loss  # noqa: F401
 from .dropedge import DropEdge, drop_edge_mask, dropout_adj  # noqa: F401
+from .enclose import EnclosingBatch, EnclosingSubgraphs, drnl_node_labeling  # noqa: F401
 
 __all__ = ["CSRGraph", "GraphBatch", "as_graph", "set_debug", "GCNNorm", "gat_conv", "gcn_conv", "sage_conv", "segmax", "segsum",
            "GATConv", "GCNConv", "SAGEConv", "Schedule", "GraphedStack", "NeighborSampler", "DataFlow", "Block", "SubgraphBatch", "NegativeSampler", "negative_sampling",
            "structured_negative_sampling", "InnerProductDecoder", "GAE", "VGAE", "ARGA", "ARGVA", "GaussianNoise", "gaussian_noise", "reparametrize_kl", "RandomWalker", "random_walk", "Node2Vec", "pair_scores", "link_loss", "group_scores", "ranking_loss", "rank_metrics",
            "roc_auc_score", "average_precision_score", "roc_curve", "precision_recall_curve", "EdgeSplitter",
-           "train_test_split_edges", "to_undirected", "KnownLinks", "topk_links", "LinkRanks", "link_ranks", "ranking_metrics", "link_log_softmax", "listwise_loss", "DropEdge", "drop_edge_mask", "dropout_adj", "NpiError", "load", "LIB_PATH"]
+           "train_test_split_edges", "to_undirected", "KnownLinks", "topk_links", "LinkRanks", "link_ranks", "ranking_metrics", "link_log_softmax", "listwise_loss", "DropEdge", "drop_edge_mask", "dropout_adj", "EnclosingSubgraphs", "EnclosingBatch", "drnl_node_labeling",
+           "NpiError", "load", "LIB_PATH"]

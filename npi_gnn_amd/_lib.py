@@ -40,6 +40,12 @@ NPI_SPLIT_UPPER = 1               # flag of npi_split_permute: keep src < dst on
 NPI_STATUS_WALK_TRIES = 512       # status bit of npi_random_walk: a step whose tries were all rejected (it took the last candidate)
 NPI_STATUS_BAD_SCORE = 1024      # status bit of npi_rank_metrics: a NaN score (the metrics are undefined)
 NPI_STATUS_BAD_LABEL = 2048      # status bit of npi_rank_metrics: a label other than 0 / 1 (it counted as 0)
+NPI_STATUS_BAD_ENCLOSE_KEY = 4096     # status bit of npi_enclose_sizes: a key with u == v or an id out of range (its sample is empty)
+NPI_STATUS_BAD_ENCLOSE_TOTALS = 8192  # status bit of npi_enclose_fill: totals of other keys (the batch holds placeholders only)
+NPI_ENCLOSE_ADD_TARGET_EDGE = 1   # flag of npi_enclose_sizes / _fill: both target columns in front of rows 0 and 1, e_id -1
+NPI_ENCLOSE_LABEL_NONE = 0        # label column of npi_enclose_features
+NPI_ENCLOSE_LABEL_DRNL = 1
+NPI_ENCLOSE_LABEL_TARGETS = 2
 NPI_PAIR_LOGITS = 0               # modes of npi_pair_score
 NPI_PAIR_LOSS_GAE = 1
 NPI_PAIR_LOSS_BCE = 2
@@ -178,6 +184,12 @@ PROTOTYPES = {
     "npi_subgraph_sizes": (c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "npi_subgraph_fill": (c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "npi_subgraph_features": (c_int, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _P]),
+    # enclosing subgraphs under Rule H: the parent's by-target CSR (rowptr, col, eid), mask, N, keys, B | ... | the label kernel alone
+    "npi_enclose_workspace_bytes": (_I, [_I, _I]),
+    "npi_enclose_sizes": (c_int, [_P, _P, _P, _P, _I, _P, _I, _I, c_int, _P, _P, _P, _P, _I, _P, _P]),
+    "npi_enclose_fill": (c_int, [_P, _P, _P, _P, _I, _P, _I, c_int, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "npi_drnl_label": (c_int, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "npi_enclose_features": (c_int, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, c_int, _P, _I, _P]),
     "npi_sample_counts": (c_int, [_P, _I, _P, _I, _I, c_float, _P, _P, _P]),
     "npi_sample_select": (c_int, [_P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P]),
     "npi_sample_workspace_elems": (_I, [_I]),

@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnpi_gnn.so")
-SOURCES = ["abi.hip", "sort.hip", "csr_build.hip", "segsum.hip", "segsum_hub.hip", "gemm_f32.hip", "graph_ops.hip", "rows.hip", "edge_dot.hip", "gat.hip", "segscan.hip", "pool.hip", "subgraph.hip",
+SOURCES = ["abi.hip", "sort.hip", "csr_build.hip", "segsum.hip", "segsum_hub.hip", "gemm_f32.hip", "graph_ops.hip", "rows.hip", "edge_dot.hip", "gat.hip", "segscan.hip", "pool.hip", "subgraph.hip", "enclose.hip",
            "sample.hip", "negative.hip", "walk.hip", "pair_score.hip", "group_score.hip", "gauss.hip", "rank.hip", "split.hip", "topk.hip", "link_rank.hip", "softmax_link.hip", "segmax.hip", "dropedge.hip", "readout.hip", "head.hip", "layer.hip"]
 HOST_ONLY = {"abi.hip", "layer.hip"}      # translation units without a kernel of their own (the error slot; sequences of the other entry points)
 ARCH = "gfx950"

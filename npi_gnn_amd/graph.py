@@ -88,6 +88,13 @@ def raise_on_status(values) -> None:
     if any(int(v) & _lib.NPI_STATUS_BAD_LABEL for v in values):
         raise ValueError("rank_metrics / roc_auc_score and their kin: a label other than 0 / 1; it counted as 0 "
                          "(npi_rank_metrics; sklearn's binary metrics raise here)")
+    if any(int(v) & _lib.NPI_STATUS_BAD_ENCLOSE_KEY for v in values):
+        raise ValueError("EnclosingSubgraphs: a key with u == v or an id outside [0, num_nodes): its sample is empty -- 0 nodes, 0 edges "
+                         "(npi_enclose_sizes)")
+    if any(int(v) & _lib.NPI_STATUS_BAD_ENCLOSE_TOTALS for v in values):
+        raise ValueError("EnclosingSubgraphs.batch: the n_nodes / n_edges it was given do not belong to its keys (the device counted "
+                         "other totals); that batch holds placeholders only (node 0 / graph 0 rows, (-1, -1) edges, zero features).  "
+                         "Totals must come from sizes() of the same keys")
     if any(int(v) & 4 for v in values):
         raise ValueError("InteractionGraph.batch: the n_nodes / n_pairs it was given do not belong to its keys (the device counted "
                          "other totals); that batch holds placeholders only (node 0 / graph 0 rows, padding edges, zero features).  "

@@ -18,6 +18,7 @@ from . import metrics as NM
 from . import pool as NP
 from .graph import GraphBatch
 from .nn import SAGEConv
+from .enclose import EnclosingSubgraphs
 from .subgraph import InteractionGraph
 
 
@@ -89,7 +90,8 @@ class Batch(GraphBatch):
 
 class KeyLoader:
     """``DataLoader(dataset, batch_size=B)`` over a list of target pairs: every batch of enclosing subgraphs is
-    built on the device when it is asked for (``InteractionGraph.batch``) instead of being read from the files
+    built on the device when it is asked for (``InteractionGraph.batch``: the reference's one-hop star; or
+    ``EnclosingSubgraphs.batch``: SEAL's h-hop induced subgraph with DRNL labels) instead of being read from the files
     the reference writes at dataset-build time.  ``shuffle()`` is ``dataset.shuffle()`` of
     ``src/train_with_twoDataset.PY:78-79``: ONE random permutation of the samples; the loader itself never
     shuffles (``:142`` passes no ``shuffle=``), so every epoch sees the same batches in the same order."""
@@ -113,7 +115,11 @@ class KeyLoader:
         for i in range(0, len(self.dataset), self.batch_size):
             k = self.keys[i:i + self.batch_size]
             nodes = self._nodes[i:i + self.batch_size]
-            gb = self.ig.batch(k, n_nodes=int(nodes.sum()), n_pairs=int(self._pairs[i:i + self.batch_size].sum()))
+            links = int(self._pairs[i:i + self.batch_size].sum())        # pairs of the star, or directed edges of the enclosing subgraph
+            if isinstance(self.ig, EnclosingSubgraphs):
+                gb = self.ig.batch(k, n_nodes=int(nodes.sum()), n_edges=links).graph_batch
+            else:
+                gb = self.ig.batch(k, n_nodes=int(nodes.sum()), n_pairs=links)
             # sizes=: the graph sizes known on the host -- TopKPooling then needs no device read
             yield Batch(gb, self.y[i:i + self.batch_size], sizes=nodes)
 
