@@ -9,8 +9,7 @@
 // permuted between the two.  This file holds the per-node dot products, the by-target SDDMM (npi_gat_edge_grad, shapes the
 // fused backward does not cover), the attention-gradient reductions and the entry points of the weighted aggregations, which
 // are segsum.hip's kernel in its W_GAT_* modes; the per-row statistics and row sums live in segscan.hip.
-#include "segsum.h"
-#include "draw.h"
+#include "seg_call.h"
 
 namespace npi {
 
@@ -593,14 +592,6 @@ gat_dropout_keep_kernel(const int32_t* __restrict__ rowptr, const int32_t* __res
     for (int h = 0; h < H; ++h) keep[p * H + h] = (live && drop_kept(stream, h, threshold)) ? scale : 0.f;
 }
 
-// the arguments of Rule D as the C ABI takes them (null: no dropout)
-struct DropArgs {
-    const int32_t* eid;
-    int64_t key;
-    uint64_t threshold;
-    float scale;
-};
-
 }  // namespace npi
 
 using namespace npi;
@@ -622,73 +613,43 @@ extern "C" int npi_gat_pack_targets(const float* a_dst, const float* m, const fl
     return check_launch("npi_gat_pack_targets");
 }
 
-// Rule D into the parameter block of a fused launch; false (error set): a null eid
-static bool set_drop(SegParams& P, const DropArgs* drop, const char* who) {
-    if (drop == nullptr) return true;
-    if (drop->eid == nullptr) {
-        set_error("%s: null eid (attention dropout is keyed on the entries' edge ids)", who);
-        return false;
-    }
-    P.eid = drop->eid;
-    P.drop_root = draw_root(drop->key, DRAW_RULE_D);
-    P.drop_threshold = drop->threshold;
-    P.drop_scale = drop->scale;
-    return true;
-}
-
-// the body of npi_gat_backward_fused_heads and npi_gat_backward_fused_heads_dropout (drop: null = the plain layer)
-static int gat_backward_fused_heads_run(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
-                                        const int32_t* item_row, int64_t item_edges, int64_t N, int64_t nnz_max,
-                                        const float* dout, int64_t ldd, const float* dout2, int64_t split, const float* hfeat,
-                                        int64_t ldh, float* out, int64_t ldo, int64_t H, int64_t C, const float* tpack,
-                                        const float* a_src, float slope, float* dz, float* carry, float* row_scales_out,
-                                        float* g_src_out, float* workspace, int64_t workspace_elems, const DropArgs* drop,
-                                        void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+// the body of npi_gat_backward_fused_heads and npi_gat_backward_fused_heads_dropout (c.x: the gathered dOut rows)
+static int gat_backward_fused(const SegCall& c, const float* hfeat, int64_t ldh, int64_t H, int64_t C, const float* tpack,
+                              const float* a_src, float slope, float* dz, float* g_src_out, float* workspace, int64_t workspace_elems) {
     const int64_t F = H * C;
-    NPI_REQUIRE(row_scales_out == nullptr || (F == 256 && ldd % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)dout % 16) == 0 &&
-                                              ((uintptr_t)out % 16) == 0 && (dout2 == nullptr || ((uintptr_t)dout2 % 16) == 0)),
-                "npi_gat_backward_fused_heads: row_scales_out needs heads * out_channels == 256 and 16-byte aligned rows");
-    NPI_REQUIRE(N >= 0 && nnz_max > 0 && C > 0 && C % 4 == 0 && F <= 256, "npi_gat_backward_fused_heads: needs heads * out_channels <= 256, out_channels % 4 == 0");
-    NPI_REQUIRE(H == 1 || ((H == 2 || H == 4 || H == 8) && C >= 32 && (C & (C - 1)) == 0),
-                "npi_gat_backward_fused_heads: several heads need 2 / 4 / 8 heads of 32 / 64 / 128 channels");
-    NPI_REQUIRE(dout2 == nullptr || (split >= 0 && split < 0x7fffffff), "npi_gat_backward_fused_heads: bad split");
-    NPI_REQUIRE(item_edges_ok(item_edges), "npi_gat_backward_fused_heads: item_edges must be 64 or NPI_ITEM_EDGES (the value the CSR was built with)");
-    if (N == 0) return NPI_OK;
-    NPI_REQUIRE(rowptr && col && rowidx && item_row && dout && hfeat && out && tpack && a_src && dz && carry,
-                "npi_gat_backward_fused_heads: null pointer");
-    NPI_REQUIRE(ldd >= F && ldh >= F && ldo >= F && ldh % 4 == 0 && ((uintptr_t)hfeat % 16) == 0 && ((uintptr_t)tpack % 16) == 0,
-                "npi_gat_backward_fused_heads: leading dimension / alignment");
-    SegParams P{};
-    P.rowptr = rowptr; P.col = col; P.item_row = item_row;
-    P.N = (int)N; P.item = (int)item_edges;
-    P.x = dout; P.ldx = ldd; P.out = out; P.ldo = ldo; P.F = (int)F;
-    P.x2 = dout2; P.split = (int)split;              // rows gathered from a two-part table (the sharded layers), as npi_segsum_ex
-    P.carry = carry; P.bias = nullptr;
+    NPI_SEG_REQUIRE(c, C > 0 && C % 4 == 0 && F <= 256, "needs heads * out_channels <= 256, out_channels %% 4 == 0");
+    NPI_SEG_REQUIRE(c, H == 1 || ((H == 2 || H == 4 || H == 8) && C >= 32 && (C & (C - 1)) == 0),
+                    "several heads need 2 / 4 / 8 heads of 32 / 64 / 128 channels");
+    SegNeeds needs{F};
+    needs.rowidx = true;
+    needs.scales_F = 256;
+    if (const int rc = seg_check(c, needs); rc != SEG_PROCEED) return rc;
+    NPI_SEG_REQUIRE(c, hfeat && tpack && a_src && dz, "null pointer");
+    NPI_SEG_REQUIRE(c, ldh >= F && ldh % 4 == 0 && ((uintptr_t)hfeat % 16) == 0 && ((uintptr_t)tpack % 16) == 0,
+                    "leading dimension / alignment");
+    SegParams P = seg_params(c, F);                  // (no bias: the caller passes none)
     P.H = (int)H; P.C = (int)C; P.a_src = a_src; P.slope = slope;
     P.a_dst = a_src; P.m = a_src; P.s = a_src;                                 // unused in this mode
     P.tpack = reinterpret_cast<const float4*>(tpack);                          // [n_cols, H, 4], indexed by the COLUMN id over both parts
-    P.hrow = hfeat; P.ldh = ldh; P.rowidx = rowidx; P.dz_out = dz;            // dz: [nnz_max, H]
-    P.scale_out = row_scales_out;
-    if (!set_drop(P, drop, "npi_gat_backward_fused_heads")) return NPI_ERR_ARG;
+    P.hrow = hfeat; P.ldh = ldh; P.dz_out = dz;                                // dz: [nnz_max, H]
     const int mode = (H == 1 ? W_GAT_SRC_FUSED : H == 2 ? W_GAT_SRC_FUSED_H2 : H == 4 ? W_GAT_SRC_FUSED_H4 : W_GAT_SRC_FUSED_H8) |
-                     (drop ? W_DROP : 0);
+                     (c.drop ? W_DROP : 0);
     // g_src_out [N] (one head): the row sums of dz from the same launch -- the lanes that compute dz scan it by row; rows cut by an
     // item boundary are added up by the chain kernel of segscan.hip behind it (workspace: npi_seg_scan_workspace_elems(nnz_max, 1))
-    const int64_t n_items = num_items_of(nnz_max, (int)item_edges);
+    const int64_t n_items = num_items_of(c.nnz_max, c.item_edges);
     if (g_src_out != nullptr) {
-        NPI_REQUIRE(H == 1, "npi_gat_backward_fused_heads: g_src_out serves one head");
+        NPI_SEG_REQUIRE(c, H == 1, "g_src_out serves one head");
         if (workspace == nullptr || workspace_elems < 3 * n_items) {
-            set_error("npi_gat_backward_fused_heads: workspace too small");
+            set_error("%s: workspace too small", c.who);
             return NPI_ERR_WORKSPACE;
         }
-        (void)hipMemsetAsync(g_src_out, 0, sizeof(float) * N, stream);                 // rows without an entry
+        (void)hipMemsetAsync(g_src_out, 0, sizeof(float) * c.N, c.stream);             // rows without an entry
         P.rowsum_out = g_src_out; P.rs_head = workspace; P.rs_tail = workspace + n_items;
         P.rs_tail_row = reinterpret_cast<int32_t*>(workspace + 2 * n_items);
     }
-    const int rc = segsum_run(P, mode, 0, nnz_max, NPI_F32, stream);
+    const int rc = segsum_run(P, mode, 0, c.nnz_max, NPI_F32, c.stream);
     if (rc != NPI_OK || g_src_out == nullptr) return rc;
-    return seg_chain_sum(rowptr, P.rs_head, P.rs_tail, P.rs_tail_row, g_src_out, N, n_items, (int)item_edges, stream);
+    return seg_chain_sum(c.rowptr, P.rs_head, P.rs_tail, P.rs_tail_row, g_src_out, c.N, n_items, (int)c.item_edges, c.stream);
 }
 
 extern "C" int npi_gat_backward_fused_heads(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
@@ -697,9 +658,9 @@ extern "C" int npi_gat_backward_fused_heads(const int32_t* rowptr, const int32_t
                                                 int64_t ldh, float* out, int64_t ldo, int64_t H, int64_t C, const float* tpack,
                                                 const float* a_src, float slope, float* dz, float* carry, float* row_scales_out,
                                                 float* g_src_out, float* workspace, int64_t workspace_elems, void* stream_) {
-    return gat_backward_fused_heads_run(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, dout, ldd, dout2, split, hfeat, ldh, out,
-                                        ldo, H, C, tpack, a_src, slope, dz, carry, row_scales_out, g_src_out, workspace,
-                                        workspace_elems, nullptr, stream_);
+    const SegCall c = SegCall("npi_gat_backward_fused_heads", stream_).side(rowptr, col, rowidx, item_row, item_edges, N, nnz_max)
+                          .table(dout, ldd, dout2, split).rows(out, ldo, carry, row_scales_out, nullptr);
+    return gat_backward_fused(c, hfeat, ldh, H, C, tpack, a_src, slope, dz, g_src_out, workspace, workspace_elems);
 }
 
 // The same launch with attention dropout under Rule D (draw.h; include/npi_gnn.h): `eid` [nnz_max] of this by-source side; the rows
@@ -712,9 +673,10 @@ extern "C" int npi_gat_backward_fused_heads_dropout(const int32_t* rowptr, const
                                                     float* row_scales_out, float* g_src_out, float* workspace, int64_t workspace_elems,
                                                     void* stream_, const int32_t* eid, int64_t key, int64_t threshold, float scale) {
     const DropArgs drop{eid, key, (uint64_t)threshold, scale};
-    return gat_backward_fused_heads_run(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, dout, ldd, dout2, split, hfeat, ldh, out,
-                                        ldo, H, C, tpack, a_src, slope, dz, carry, row_scales_out, g_src_out, workspace,
-                                        workspace_elems, &drop, stream_);
+    SegCall c = SegCall("npi_gat_backward_fused_heads_dropout", stream_).side(rowptr, col, rowidx, item_row, item_edges, N, nnz_max)
+                    .table(dout, ldd, dout2, split).rows(out, ldo, carry, row_scales_out, nullptr);
+    c.drop = &drop;
+    return gat_backward_fused(c, hfeat, ldh, H, C, tpack, a_src, slope, dz, g_src_out, workspace, workspace_elems);
 }
 
 extern "C" int npi_gat_rank1_add(float* dh, int64_t ld, const float* g_dst, const float* g_src, const float* att,
@@ -801,84 +763,66 @@ extern "C" int npi_gat_aggregate_ex(const int32_t* rowptr, const int32_t* col, c
                                     const float* g_dst, const float* g_src, const float* att,
                                     const float* alpha, const int32_t* alpha_map,
                                     float* carry, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(x2 == nullptr || (split >= 0 && split < 0x7fffffff), "npi_gat_aggregate_ex: bad split");
-    NPI_REQUIRE(item_edges_ok(item_edges), "npi_gat_aggregate: item_edges must be 64 or NPI_ITEM_EDGES (the value the CSR was built with)");
-    NPI_REQUIRE(N >= 0 && nnz_max > 0 && H > 0 && C > 0, "npi_gat_aggregate: bad size");
-    if (N == 0) return NPI_OK;
-    NPI_REQUIRE(rowptr && col && item_row && x && out && a_dst && a_src && m && s && carry, "npi_gat_aggregate: null pointer");
-    NPI_REQUIRE(ldx >= H * C && ldo >= H * C, "npi_gat_aggregate: leading dimension too small");
-    SegParams P{};
-    P.rowptr = rowptr; P.col = col; P.item_row = item_row;
-    P.N = (int)N; P.item = (int)item_edges;
-    P.x = x; P.ldx = ldx; P.out = out; P.ldo = ldo; P.F = (int)(H * C);
-    P.x2 = x2; P.split = (int)split;
-    P.carry = carry; P.w = nullptr; P.bias = bias;
+    const SegCall c = SegCall("npi_gat_aggregate_ex", stream_).side(rowptr, col, nullptr, item_row, item_edges, N, nnz_max)
+                          .table(x, ldx, x2, split).rows(out, ldo, carry, nullptr, bias);
+    NPI_SEG_REQUIRE(c, H > 0 && C > 0, "bad size");
+    if (const int rc = seg_check(c, SegNeeds{H * C}); rc != SEG_PROCEED) return rc;
+    NPI_SEG_REQUIRE(c, a_dst && a_src && m && s, "null pointer");
+    SegParams P = seg_params(c, H * C);
     P.H = (int)H; P.C = (int)C; P.a_dst = a_dst; P.a_src = a_src; P.m = m; P.s = s; P.slope = slope;
     P.g_dst = g_dst; P.g_src = g_src; P.att = att;
+    int mode = by_source ? W_GAT_SRC : W_GAT_DST;
     if (alpha != nullptr && !by_source) {     // forward, one head: also WRITE alpha of every entry (by-target order) for the backward
-        NPI_REQUIRE(H == 1 && alpha_map == nullptr, "npi_gat_aggregate: storing alpha needs one head (and no alpha_map)");
+        NPI_SEG_REQUIRE(c, H == 1 && alpha_map == nullptr, "storing alpha needs one head (and no alpha_map)");
         P.alpha_out = const_cast<float*>(alpha);
-        return segsum_run(P, W_GAT_DST, 0, nnz_max, NPI_F32, stream);
-    }
-    if (alpha != nullptr) {       // the weights of the forward / of npi_gat_edge_grad, read back through the transpose map (one head, by source)
-        NPI_REQUIRE(by_source && H == 1 && alpha_map != nullptr, "npi_gat_aggregate: alpha needs by_source, one head and alpha_map");
+    } else if (alpha != nullptr) {  // the weights of the forward / of npi_gat_edge_grad, read back through the transpose map (one head, by source)
+        NPI_SEG_REQUIRE(c, H == 1 && alpha_map != nullptr, "alpha needs by_source, one head and alpha_map");
         P.w = alpha; P.wmap = alpha_map;
-        return segsum_run(P, W_GAT_SRC_PRE, 0, nnz_max, NPI_F32, stream);
+        mode = W_GAT_SRC_PRE;
     }
-    return segsum_run(P, by_source ? W_GAT_SRC : W_GAT_DST, 0, nnz_max, NPI_F32, stream);
+    return segsum_run(P, mode, 0, nnz_max, NPI_F32, c.stream);
 }
 
 extern "C" int npi_gat_aggregate_scores(const int32_t* rowptr, const int32_t* col, const int32_t* item_row, int64_t item_edges,
                                         int64_t N, int64_t nnz_max, const float* x, int64_t ldx, const float* x2, int64_t split,
                                         float* out, int64_t ldo, int64_t C, const float* scores, const float* m, const float* s,
                                         const float* bias, int relu, float* carry, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(x2 == nullptr || (split >= 0 && split < 0x7fffffff), "npi_gat_aggregate_scores: bad split");
-    NPI_REQUIRE(item_edges_ok(item_edges), "npi_gat_aggregate_scores: item_edges must be 64 or NPI_ITEM_EDGES (the value the CSR was built with)");
-    NPI_REQUIRE(N >= 0 && nnz_max > 0 && C > 0, "npi_gat_aggregate_scores: bad size");
-    if (N == 0) return NPI_OK;
-    NPI_REQUIRE(rowptr && col && item_row && x && out && scores && m && s && carry, "npi_gat_aggregate_scores: null pointer");
-    NPI_REQUIRE(ldx >= C && ldo >= C, "npi_gat_aggregate_scores: leading dimension too small");
-    SegParams P{};
-    P.rowptr = rowptr; P.col = col; P.item_row = item_row;
-    P.N = (int)N; P.item = (int)item_edges;
-    P.x = x; P.ldx = ldx; P.out = out; P.ldo = ldo; P.F = (int)C;
-    P.x2 = x2; P.split = (int)split;
-    P.carry = carry; P.w = scores; P.bias = bias;
+    const SegCall c = SegCall("npi_gat_aggregate_scores", stream_).side(rowptr, col, nullptr, item_row, item_edges, N, nnz_max)
+                          .table(x, ldx, x2, split).rows(out, ldo, carry, nullptr, bias);
+    NPI_SEG_REQUIRE(c, C > 0, "bad size");
+    if (const int rc = seg_check(c, SegNeeds{C}); rc != SEG_PROCEED) return rc;
+    NPI_SEG_REQUIRE(c, scores && m && s, "null pointer");
+    SegParams P = seg_params(c, C);
+    P.w = scores;
     P.H = 1; P.C = (int)C; P.m = m; P.s = s; P.relu = relu ? 1 : 0;
-    return segsum_run(P, W_GAT_DST_PRE, 0, nnz_max, NPI_F32, stream);
+    return segsum_run(P, W_GAT_DST_PRE, 0, nnz_max, NPI_F32, c.stream);
 }
 
-// One head, C <= 256: the forward aggregation WITH the softmax statistics (W_GAT_DST_FUSED): out, m, s in one launch; no
-// statistics pass, no per-entry score array, no gather of the sources' scores (npi_gat_softmax_stats_ex +
-// npi_gat_aggregate_scores do the same in two): the source half of every score is recomputed from the gathered row
-static int gat_aggregate_fused_run(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* item_row,
-                                   int64_t item_edges, int64_t N, int64_t nnz_max, const float* x, int64_t ldx,
-                                   const float* x2, int64_t split, float* out, int64_t ldo, int64_t C, const float* a_dst,
-                                   const float* att, float slope, const float* bias, int relu, float* m, float* s,
-                                   float* carry, float* row_scales_out, const DropArgs* drop, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(row_scales_out == nullptr || (C == 256 && ldx % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)x % 16) == 0 &&
-                                              ((uintptr_t)out % 16) == 0 && (x2 == nullptr || ((uintptr_t)x2 % 16) == 0)),
-                "npi_gat_aggregate_fused: row_scales_out needs 256 channels and 16-byte aligned rows");
-    NPI_REQUIRE(x2 == nullptr || (split >= 0 && split < 0x7fffffff), "npi_gat_aggregate_fused: bad split");
-    NPI_REQUIRE(item_edges_ok(item_edges), "npi_gat_aggregate_fused: item_edges must be 64 or NPI_ITEM_EDGES (the value the CSR was built with)");
-    NPI_REQUIRE(N >= 0 && nnz_max > 0 && C > 0 && C <= 256 && C % 4 == 0, "npi_gat_aggregate_fused: bad size (one head of at most 256 channels, a multiple of 4)");
-    if (N == 0) return NPI_OK;
-    NPI_REQUIRE(rowptr && col && item_row && x && out && a_dst && att && m && s && carry, "npi_gat_aggregate_fused: null pointer");
-    NPI_REQUIRE((uintptr_t)att % 16 == 0, "npi_gat_aggregate_fused: att must be 16-byte aligned");
-    NPI_REQUIRE(ldx >= C && ldo >= C, "npi_gat_aggregate_fused: leading dimension too small");
-    SegParams P{};
-    P.rowptr = rowptr; P.col = col; P.item_row = item_row; P.rowidx = rowidx;
-    P.N = (int)N; P.item = (int)item_edges;
-    P.x = x; P.ldx = ldx; P.out = out; P.ldo = ldo; P.F = (int)C;
-    P.x2 = x2; P.split = (int)split;
-    P.carry = carry; P.bias = bias;
-    P.H = 1; P.C = (int)C; P.a_dst = a_dst; P.att = att; P.slope = slope; P.m_out = m; P.s_out = s; P.relu = relu ? 1 : 0;
-    P.scale_out = row_scales_out;                // the scales of the rows as they are stored: bias and ReLU applied
-    if (!set_drop(P, drop, "npi_gat_aggregate_fused")) return NPI_ERR_ARG;
-    return segsum_run(P, W_GAT_DST_FUSED | (drop ? W_DROP : 0), 0, nnz_max, NPI_F32, stream);
+// The forward aggregation WITH the softmax statistics (W_GAT_DST_FUSED*): out, m, s in one launch; no statistics pass, no per-entry
+// score array, no gather of the sources' scores (npi_gat_softmax_stats_ex + npi_gat_aggregate_scores do the same in two): the
+// source half of every score is recomputed from the gathered row.  The body of npi_gat_aggregate_fused, npi_gat_aggregate_fused_heads
+// and npi_gat_aggregate_fused_heads_dropout: one head of C <= 256 channels, or 2 / 4 / 8 heads (the shapes of the fused backward:
+// 32 / 64 / 128 channels per head, H C <= 256) with a_dst, m, s [N, H] and att [H, 2C]; no other shape has a kernel
+static int gat_aggregate_fused(const SegCall& c, int64_t H, int64_t C, const float* a_dst, const float* att, float slope, int relu,
+                               float* m, float* s) {
+    SegNeeds needs{H * C};
+    if (H == 1) {
+        NPI_SEG_REQUIRE(c, C > 0 && C <= 256 && C % 4 == 0, "bad size (one head of at most 256 channels, a multiple of 4)");
+        needs.scales_F = 256;                        // the scales of the rows as they are stored: bias and ReLU applied
+    } else {
+        NPI_SEG_REQUIRE(c, H == 2 || H == 4 || H == 8, "heads must be 1, 2, 4 or 8");
+        NPI_SEG_REQUIRE(c, (C == 32 || C == 64 || C == 128) && H * C <= 256,
+                        "several heads need 32 / 64 / 128 channels per head and heads * out_channels <= 256");
+        NPI_SEG_REQUIRE(c, (uintptr_t)att % 16 == 0, "att must be 16-byte aligned");
+        needs.rows16 = true;
+    }
+    if (const int rc = seg_check(c, needs); rc != SEG_PROCEED) return rc;
+    NPI_SEG_REQUIRE(c, a_dst && att && m && s, "null pointer");
+    NPI_SEG_REQUIRE(c, (uintptr_t)att % 16 == 0, "att must be 16-byte aligned");
+    SegParams P = seg_params(c, H * C);
+    P.H = (int)H; P.C = (int)C; P.a_dst = a_dst; P.att = att; P.slope = slope; P.m_out = m; P.s_out = s; P.relu = relu ? 1 : 0;
+    const int mode = H == 1 ? W_GAT_DST_FUSED : H == 2 ? W_GAT_DST_FUSED_H2 : H == 4 ? W_GAT_DST_FUSED_H4 : W_GAT_DST_FUSED_H8;
+    return segsum_run(P, mode | (c.drop ? W_DROP : 0), 0, c.nnz_max, NPI_F32, c.stream);
 }
 
 extern "C" int npi_gat_aggregate_fused(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* item_row,
@@ -886,45 +830,9 @@ extern "C" int npi_gat_aggregate_fused(const int32_t* rowptr, const int32_t* col
                                            const float* x2, int64_t split, float* out, int64_t ldo, int64_t C, const float* a_dst,
                                            const float* att, float slope, const float* bias, int relu, float* m, float* s,
                                            float* carry, float* row_scales_out, void* stream_) {
-    return gat_aggregate_fused_run(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, x, ldx, x2, split, out, ldo, C, a_dst, att,
-                                   slope, bias, relu, m, s, carry, row_scales_out, nullptr, stream_);
-}
-
-// The same launch for 2 / 4 / 8 heads (W_GAT_DST_FUSED_H2/4/8; the shapes of the fused backward: 32 / 64 / 128 channels per head,
-// H C <= 256): a_dst, m, s are [N, H], att [H, 2C].  One head forwards to the mode above; no other shape has a kernel
-static int gat_aggregate_fused_heads_run(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* item_row,
-                                         int64_t item_edges, int64_t N, int64_t nnz_max, const float* x, int64_t ldx,
-                                         const float* x2, int64_t split, float* out, int64_t ldo, int64_t H, int64_t C,
-                                         const float* a_dst, const float* att, float slope, const float* bias, int relu,
-                                         float* m, float* s, float* carry, float* row_scales_out, const DropArgs* drop, void* stream_) {
-    if (H == 1)
-        return gat_aggregate_fused_run(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, x, ldx, x2, split, out, ldo, C, a_dst, att,
-                                       slope, bias, relu, m, s, carry, row_scales_out, drop, stream_);
-    hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(H == 2 || H == 4 || H == 8, "npi_gat_aggregate_fused_heads: heads must be 1, 2, 4 or 8");
-    NPI_REQUIRE((C == 32 || C == 64 || C == 128) && H * C <= 256,
-                "npi_gat_aggregate_fused_heads: several heads need 32 / 64 / 128 channels per head and heads * out_channels <= 256");
-    NPI_REQUIRE(row_scales_out == nullptr, "npi_gat_aggregate_fused_heads: row_scales_out serves one head");
-    NPI_REQUIRE(x2 == nullptr || (split >= 0 && split < 0x7fffffff), "npi_gat_aggregate_fused_heads: bad split");
-    NPI_REQUIRE(item_edges_ok(item_edges), "npi_gat_aggregate_fused_heads: item_edges must be 64 or NPI_ITEM_EDGES (the value the CSR was built with)");
-    NPI_REQUIRE(N >= 0 && nnz_max > 0, "npi_gat_aggregate_fused_heads: bad size");
-    NPI_REQUIRE(att == nullptr || (uintptr_t)att % 16 == 0, "npi_gat_aggregate_fused_heads: att must be 16-byte aligned");
-    if (N == 0) return NPI_OK;
-    NPI_REQUIRE(rowptr && col && item_row && x && out && a_dst && att && m && s && carry, "npi_gat_aggregate_fused_heads: null pointer");
-    const int64_t F = H * C;
-    NPI_REQUIRE(ldx >= F && ldo >= F && ldx % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 &&
-                (x2 == nullptr || ((uintptr_t)x2 % 16) == 0) && ((uintptr_t)carry % 16) == 0,
-                "npi_gat_aggregate_fused_heads: leading dimension / 16-byte alignment of the rows");
-    SegParams P{};
-    P.rowptr = rowptr; P.col = col; P.item_row = item_row; P.rowidx = rowidx;
-    P.N = (int)N; P.item = (int)item_edges;
-    P.x = x; P.ldx = ldx; P.out = out; P.ldo = ldo; P.F = (int)F;
-    P.x2 = x2; P.split = (int)split;
-    P.carry = carry; P.bias = bias;
-    P.H = (int)H; P.C = (int)C; P.a_dst = a_dst; P.att = att; P.slope = slope; P.m_out = m; P.s_out = s; P.relu = relu ? 1 : 0;
-    if (!set_drop(P, drop, "npi_gat_aggregate_fused_heads")) return NPI_ERR_ARG;
-    return segsum_run(P, (H == 2 ? W_GAT_DST_FUSED_H2 : H == 4 ? W_GAT_DST_FUSED_H4 : W_GAT_DST_FUSED_H8) | (drop ? W_DROP : 0), 0, nnz_max,
-                      NPI_F32, stream);
+    const SegCall c = SegCall("npi_gat_aggregate_fused", stream_).side(rowptr, col, rowidx, item_row, item_edges, N, nnz_max)
+                          .table(x, ldx, x2, split).rows(out, ldo, carry, row_scales_out, bias);
+    return gat_aggregate_fused(c, 1, C, a_dst, att, slope, relu, m, s);
 }
 
 extern "C" int npi_gat_aggregate_fused_heads(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx, const int32_t* item_row,
@@ -932,8 +840,9 @@ extern "C" int npi_gat_aggregate_fused_heads(const int32_t* rowptr, const int32_
                                              const float* x2, int64_t split, float* out, int64_t ldo, int64_t H, int64_t C,
                                              const float* a_dst, const float* att, float slope, const float* bias, int relu,
                                              float* m, float* s, float* carry, float* row_scales_out, void* stream_) {
-    return gat_aggregate_fused_heads_run(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, x, ldx, x2, split, out, ldo, H, C, a_dst,
-                                         att, slope, bias, relu, m, s, carry, row_scales_out, nullptr, stream_);
+    const SegCall c = SegCall("npi_gat_aggregate_fused_heads", stream_).side(rowptr, col, rowidx, item_row, item_edges, N, nnz_max)
+                          .table(x, ldx, x2, split).rows(out, ldo, carry, row_scales_out, bias);
+    return gat_aggregate_fused(c, H, C, a_dst, att, slope, relu, m, s);
 }
 
 // The same launch with attention dropout under Rule D (draw.h; include/npi_gnn.h): `eid` [nnz_max] of this by-target side; an entry
@@ -946,40 +855,40 @@ extern "C" int npi_gat_aggregate_fused_heads_dropout(const int32_t* rowptr, cons
                                                      float* row_scales_out, void* stream_, const int32_t* eid, int64_t key,
                                                      int64_t threshold, float scale) {
     const DropArgs drop{eid, key, (uint64_t)threshold, scale};
-    return gat_aggregate_fused_heads_run(rowptr, col, rowidx, item_row, item_edges, N, nnz_max, x, ldx, x2, split, out, ldo, H, C, a_dst,
-                                         att, slope, bias, relu, m, s, carry, row_scales_out, &drop, stream_);
+    SegCall c = SegCall("npi_gat_aggregate_fused_heads_dropout", stream_).side(rowptr, col, rowidx, item_row, item_edges, N, nnz_max)
+                    .table(x, ldx, x2, split).rows(out, ldo, carry, row_scales_out, bias);
+    c.drop = &drop;
+    return gat_aggregate_fused(c, H, C, a_dst, att, slope, relu, m, s);
 }
 
-static int gat_edge_grad_run(const int32_t* rowptr, const int32_t* col, const int32_t* rowidx,
-                             int64_t N, int64_t nnz_max, const float* hfeat, int64_t ldh,
-                             const float* hfeat2, int64_t split,
-                             const float* dout, int64_t ldd, int64_t H, int64_t C,
-                             const float* a_dst, const float* a_src, const float* m, const float* s,
-                             const float* D, float slope, int swap, float* dz, float* alpha_out, const DropArgs* drop, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(hfeat2 == nullptr || (split >= 0 && split < 0x7fffffff), "npi_gat_edge_grad_ex: bad split");
-    if (hfeat2 == nullptr) { hfeat2 = hfeat; split = 0x7fffffff; }
-    NPI_REQUIRE((uintptr_t)hfeat2 % 16 == 0, "npi_gat_edge_grad_ex: hfeat2 must be 16-B aligned");
-    NPI_REQUIRE(N >= 0 && nnz_max >= 0 && H > 0 && C > 0, "npi_gat_edge_grad: bad size");
-    if (N == 0 || nnz_max == 0) return NPI_OK;
-    NPI_REQUIRE(rowptr && col && rowidx && hfeat && dout && a_dst && a_src && m && s && D && dz, "npi_gat_edge_grad: null pointer");
+// the body of npi_gat_edge_grad_ex and npi_gat_edge_grad_dropout (c.x: the gathered table; no item_row, no out, no carry: its own
+// kernel, which keeps no item state between calls)
+static int gat_edge_grad(const SegCall& c, const float* dout, int64_t ldd, int64_t H, int64_t C, const float* a_dst, const float* a_src,
+                         const float* m, const float* s, const float* D, float slope, int swap, float* dz, float* alpha_out) {
+    const float* hfeat2 = c.x2 ? c.x2 : c.x;
+    const int split = c.x2 ? (int)c.split : 0x7fffffff;
+    NPI_SEG_REQUIRE(c, (uintptr_t)hfeat2 % 16 == 0, "hfeat2 must be 16-B aligned");
+    NPI_SEG_REQUIRE(c, H > 0 && C > 0, "bad size");
+    if (const int rc = seg_check_sizes(c, true); rc != NPI_OK) return rc;
+    if (c.N == 0 || c.nnz_max == 0) return NPI_OK;
+    NPI_SEG_REQUIRE(c, seg_side_present(c, true) && dout && a_dst && a_src && m && s && D && dz, "null pointer");
     const int64_t F = H * C;
-    NPI_REQUIRE(F % 4 == 0 && C % 4 == 0 && ldh % 4 == 0 && ldd % 4 == 0 && F <= 1024 &&
-                ((uintptr_t)hfeat % 16 == 0) && ((uintptr_t)dout % 16 == 0),
-                "npi_gat_edge_grad: needs 16-B aligned rows, out_channels % 4 == 0, heads*out_channels <= 1024");
-    // this kernel keeps no item state between calls (no item_row, no carry): its own chunking of the entry stream, per call
-    const int chunk = item_edges_for(nnz_max);
-    const int n_items = (int)num_items_of(nnz_max, chunk);
+    NPI_SEG_REQUIRE(c, F % 4 == 0 && C % 4 == 0 && c.ldx % 4 == 0 && ldd % 4 == 0 && F <= 1024 &&
+                    ((uintptr_t)c.x % 16 == 0) && ((uintptr_t)dout % 16 == 0),
+                    "needs 16-B aligned rows, out_channels %% 4 == 0, heads*out_channels <= 1024");
+    NPI_SEG_REQUIRE(c, c.drop == nullptr || c.drop->eid != nullptr, "null eid (attention dropout is keyed on the entries' edge ids)");
+    // its own chunking of the entry stream, per call
+    const int chunk = item_edges_for(c.nnz_max);
+    const int n_items = (int)num_items_of(c.nnz_max, chunk);
     const unsigned grid = (unsigned)ceil_div(n_items, 4);
-    const int nch = (int)ceil_div(F, 256);
-#define NPI_EG(NC) gat_edge_grad_kernel<NC><<<grid, 256, 0, stream>>>(rowptr, col, rowidx, (int)N, n_items, chunk, hfeat, ldh, dout, ldd, (int)H, (int)C, a_dst, a_src, m, s, D, slope, dz, alpha_out, hfeat2, (int)split, swap)
-#define NPI_EG_DROP(NC) gat_edge_grad_kernel<NC, true><<<grid, 256, 0, stream>>>(rowptr, col, rowidx, (int)N, n_items, chunk, hfeat, ldh, dout, ldd, (int)H, (int)C, a_dst, a_src, m, s, D, slope, dz, alpha_out, hfeat2, (int)split, swap, drop->eid, draw_root(drop->key, DRAW_RULE_D), drop->threshold, drop->scale)
-    if (drop != nullptr) {
-        NPI_REQUIRE(drop->eid != nullptr, "npi_gat_edge_grad_dropout: null eid (attention dropout is keyed on the entries' edge ids)");
-        if (nch == 1) NPI_EG_DROP(1); else if (nch == 2) NPI_EG_DROP(2); else if (nch == 3) NPI_EG_DROP(3); else NPI_EG_DROP(4);
-    } else if (nch == 1) NPI_EG(1); else if (nch == 2) NPI_EG(2); else if (nch == 3) NPI_EG(3); else NPI_EG(4);
-#undef NPI_EG
-#undef NPI_EG_DROP
+    const DropArgs drop = c.drop ? *c.drop : DropArgs{nullptr, 0, 0, 1.f};
+    const uint64_t root = c.drop ? draw_root(drop.key, DRAW_RULE_D) : 0;
+    static constexpr decltype(&gat_edge_grad_kernel<1>) kernels[2][4] = {       // [no dropout][256-column chunks - 1]
+        {gat_edge_grad_kernel<1, true>, gat_edge_grad_kernel<2, true>, gat_edge_grad_kernel<3, true>, gat_edge_grad_kernel<4, true>},
+        {gat_edge_grad_kernel<1>, gat_edge_grad_kernel<2>, gat_edge_grad_kernel<3>, gat_edge_grad_kernel<4>}};
+    kernels[c.drop ? 0 : 1][ceil_div(F, 256) - 1]<<<grid, 256, 0, c.stream>>>(
+        c.rowptr, c.col, c.rowidx, (int)c.N, n_items, chunk, c.x, c.ldx, dout, ldd, (int)H, (int)C, a_dst, a_src, m, s, D, slope, dz,
+        alpha_out, hfeat2, split, swap, drop.eid, root, drop.threshold, drop.scale);
     return check_launch("npi_gat_edge_grad");
 }
 
@@ -989,8 +898,8 @@ extern "C" int npi_gat_edge_grad_ex(const int32_t* rowptr, const int32_t* col, c
                                     const float* dout, int64_t ldd, int64_t H, int64_t C,
                                     const float* a_dst, const float* a_src, const float* m, const float* s,
                                     const float* D, float slope, int swap, float* dz, float* alpha_out, void* stream_) {
-    return gat_edge_grad_run(rowptr, col, rowidx, N, nnz_max, hfeat, ldh, hfeat2, split, dout, ldd, H, C, a_dst, a_src, m, s, D, slope,
-                             swap, dz, alpha_out, nullptr, stream_);
+    const SegCall c = SegCall("npi_gat_edge_grad_ex", stream_).side(rowptr, col, rowidx, nullptr, 0, N, nnz_max).table(hfeat, ldh, hfeat2, split);
+    return gat_edge_grad(c, dout, ldd, H, C, a_dst, a_src, m, s, D, slope, swap, dz, alpha_out);
 }
 
 // npi_gat_edge_grad_ex with attention dropout under Rule D: dz = alpha (kappa <dOut_i, h_j> - D_i) leaky_relu'(z); `eid` [nnz_max] of
@@ -1003,8 +912,9 @@ extern "C" int npi_gat_edge_grad_dropout(const int32_t* rowptr, const int32_t* c
                                          const float* D, float slope, int swap, float* dz, float* alpha_out, void* stream_,
                                          const int32_t* eid, int64_t key, int64_t threshold, float scale) {
     const DropArgs drop{eid, key, (uint64_t)threshold, scale};
-    return gat_edge_grad_run(rowptr, col, rowidx, N, nnz_max, hfeat, ldh, hfeat2, split, dout, ldd, H, C, a_dst, a_src, m, s, D, slope,
-                             swap, dz, alpha_out, &drop, stream_);
+    SegCall c = SegCall("npi_gat_edge_grad_dropout", stream_).side(rowptr, col, rowidx, nullptr, 0, N, nnz_max).table(hfeat, ldh, hfeat2, split);
+    c.drop = &drop;
+    return gat_edge_grad(c, dout, ldd, H, C, a_dst, a_src, m, s, D, slope, swap, dz, alpha_out);
 }
 
 // keep [nnz_max, H] f32: kappa (0 or `scale`) of every entry and head of one side under Rule D, in the side's entry order (0 behind the

@@ -36,8 +36,7 @@
 //   ... | W_DROP  the eight fused modes with attention dropout under Rule D (draw.h): the lane that owns an entry's weight computes
 //              kappa = 0 or 1 / (1 - p) per head from the entry's eid; kappa scales what the entry ADDS (and the dot inside dz),
 //              never the softmax statistics -- so every partial row, however it is cut and merged, carries it already
-#include "segsum.h"
-#include "draw.h"
+#include "seg_call.h"
 
 #include <stdlib.h>
 
@@ -1533,17 +1532,10 @@ static int dispatch_nch(const SegParams& P, int wmode, hipStream_t stream) {
     return NPI_ERR_ARG;
 }
 
-// shared by npi_segsum and npi_gat_aggregate (gat.hip)
+// shared by npi_segsum and npi_gat_aggregate (gat.hip); P comes from seg_params behind seg_check (seg_call.h), which has refused an
+// unknown item size and a dropout mode without eid
 int segsum_run(SegParams P, int wmode, int mean, int64_t nnz_max, int dtype, hipStream_t stream) {
     const int64_t F = P.F;
-    if (!item_edges_ok(P.item)) {                             // the CSR's own item size, handed over by the caller next to item_row
-        set_error("npi_segsum: item_edges must be 64 or %d (the value the CSR was built with)", NPI_ITEM_EDGES);
-        return NPI_ERR_ARG;
-    }
-    if (drop_mode(wmode) && P.eid == nullptr) {
-        set_error("npi_segsum: the dropout modes need the entries' eid");
-        return NPI_ERR_ARG;
-    }
     P.n_items = (int)num_items_of(nnz_max, P.item);
     P.mean = mean ? 1 : 0;
     P.nt_out = ((int64_t)P.N * F * ((dtype == NPI_BF16) ? 2 : 4) >= ((int64_t)64 << 20)) ? 1 : 0;
@@ -1608,34 +1600,22 @@ extern "C" int npi_segsum_ex(const int32_t* rowptr, const int32_t* col, const in
                               const float* w, int64_t N, int64_t nnz_max, const void* x_, int64_t ldx,
                               const void* x2_, int64_t split, void* out_, int64_t ldo, int64_t F, int dtype, int mean,
                               const float* bias, float* carry, float* row_scales_out, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    NPI_REQUIRE(row_scales_out == nullptr || (npi_segsum_scales_supported(F, dtype) && nnz_max > 0 && ldx % 4 == 0 && ldo % 4 == 0 &&
-                                              ((uintptr_t)x_ % 16) == 0 && ((uintptr_t)out_ % 16) == 0 &&
-                                              (x2_ == nullptr || ((uintptr_t)x2_ % 16) == 0)),
-                "npi_segsum_ex: row_scales_out needs f32 rows of 256 columns, 16-byte aligned (npi_segsum_scales_supported), and a "
-                "graph with entries");
-    NPI_REQUIRE(x2_ == nullptr || (split >= 0 && split < 0x7fffffff), "npi_segsum_ex: bad split");
-    NPI_REQUIRE(N >= 0 && nnz_max >= 0 && F > 0, "npi_segsum: bad size");
-    NPI_REQUIRE(dtype == NPI_F32 || dtype == NPI_BF16, "npi_segsum: dtype must be NPI_F32 or NPI_BF16");
-    NPI_REQUIRE(ldx >= F && ldo >= F, "npi_segsum: leading dimension < F");
-    if (N == 0) return NPI_OK;
-    NPI_REQUIRE(rowptr && item_row && x_ && out_ && carry, "npi_segsum: null pointer");
-    NPI_REQUIRE(item_edges_ok(item_edges), "npi_segsum: item_edges must be 64 or NPI_ITEM_EDGES (the value the CSR was built with)");
-    const int64_t n_items = num_items_of(nnz_max, item_edges);
-    if (n_items == 0) {     // no entries at all: every row is empty
-        NPI_REQUIRE(bias == nullptr, "npi_segsum: bias with an entry-free graph is not supported");
+    const SegCall c = SegCall("npi_segsum_ex", stream_).side(rowptr, col, nullptr, item_row, item_edges, N, nnz_max)
+                          .table(x_, ldx, x2_, split).rows(out_, ldo, carry, row_scales_out, bias);
+    NPI_SEG_REQUIRE(c, F > 0, "bad size");
+    NPI_SEG_REQUIRE(c, dtype == NPI_F32 || dtype == NPI_BF16, "dtype must be NPI_F32 or NPI_BF16");
+    SegNeeds needs{F};
+    needs.empty_ok = true;
+    needs.scales_F = (npi_segsum_scales_supported(F, dtype) && nnz_max > 0) ? F : 0;
+    if (const int rc = seg_check(c, needs); rc != SEG_PROCEED) return rc;
+    if (nnz_max == 0) {     // no entries at all: every row is empty
+        NPI_SEG_REQUIRE(c, bias == nullptr, "bias with an entry-free graph is not supported");
         const size_t es = (dtype == NPI_BF16) ? 2 : 4;
-        (void)hipMemset2DAsync(out_, ldo * es, 0, F * es, N, stream);
+        (void)hipMemset2DAsync(out_, ldo * es, 0, F * es, N, c.stream);
         return check_launch("npi_segsum(memset)");
     }
-    NPI_REQUIRE(col != nullptr, "npi_segsum: null col");
-    SegParams P{};
-    P.rowptr = rowptr; P.col = col; P.item_row = item_row;
-    P.N = (int)N; P.item = (int)item_edges;
-    P.x = (const float*)x_; P.ldx = ldx; P.out = (float*)out_; P.ldo = ldo; P.F = (int)F;
-    P.x2 = (const float*)x2_; P.split = (int)split;
-    P.carry = carry; P.w = w; P.bias = bias;
+    SegParams P = seg_params(c, F);
+    P.w = w;
     P.H = 1; P.C = (int)F;
-    P.scale_out = row_scales_out;
-    return segsum_run(P, w ? W_ARRAY : W_NONE, mean, nnz_max, dtype, stream);
+    return segsum_run(P, w ? W_ARRAY : W_NONE, mean, nnz_max, dtype, c.stream);
 }

@@ -129,6 +129,24 @@ def _check_out(out: torch.Tensor, rows: int, cols: int, like: torch.Tensor, what
                          f"(got {tuple(out.shape)} {out.dtype}, strides {tuple(out.stride())}, {out.device})")
 
 
+def _out_or_new(out: Optional[torch.Tensor], rows: int, cols: int, like: torch.Tensor, what: str) -> torch.Tensor:
+    """the ``out=`` of a wrapper: a new ``[rows, cols]`` tensor like ``like``, or the caller's once ``_check_out`` passes it"""
+    if out is None:
+        return torch.empty((rows, cols), dtype=like.dtype, device=like.device)
+    _check_out(out, rows, cols, like, what)
+    return out
+
+
+def _second_part(part2: Optional[torch.Tensor], part1: torch.Tensor, name: str) -> Optional[torch.Tensor]:
+    """the second part of a two-part gathered table (the GAT wrappers): float32, contiguous, the row pitch of the first"""
+    if part2 is None:
+        return None
+    part2 = _f32c(part2, name)
+    if part2.stride(0) != part1.stride(0):
+        raise ValueError("the two parts of the table must share the row pitch")
+    return part2
+
+
 # ---------------------------------------------------------------------------------------------
 # raw ops
 # ---------------------------------------------------------------------------------------------
@@ -315,15 +333,6 @@ def prepare_weight(weight: torch.Tensor, backward: bool = True, f16: bool = Fals
     return Planes(ws[:one], f16), (Planes(ws[one:], f16) if backward else None)
 
 
-def _linear_out(out: Optional[torch.Tensor], rows: int, cols: int, like: torch.Tensor, what: str) -> torch.Tensor:
-    """the ``out=`` of ``linear_fwd`` / ``linear_bwd_data``: a new ``[rows, cols]`` tensor, or the caller's once it is that"""
-    if out is None:
-        return torch.empty((rows, cols), dtype=like.dtype, device=like.device)
-    if out.shape != (rows, cols) or out.dtype != like.dtype or out.stride(1) != 1 or out.device != like.device:
-        raise ValueError(f"{what}: out must be [{rows}, {cols}] {like.dtype} with unit column stride on the operands' device")
-    return out
-
-
 def _linear_call(flags: Optional[int], reserve_cus: int, scales: Optional[torch.Tensor], ws, *, f16_ok: bool, K: int, N: int, dev,
                  what: str):
     """what ``linear_fwd`` / ``linear_bwd_data`` make of their arithmetic arguments: ``(flags, scales or None, workspace tensor)``.
@@ -359,7 +368,7 @@ def linear_fwd(a: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     K, N = weight.shape
     if Ka != K and (Ka != _pad128(K) or a.dtype != torch.float32):
         raise ValueError(f"a has {Ka} columns, weight {K} rows (a zero-padded a must be f32 and {_pad128(K)} wide)")
-    out = _linear_out(out, M, N, a, "linear_fwd")
+    out = _out_or_new(out, M, N, a, "linear_fwd")
     _check_scales(a_scales, M, "linear_fwd")
     padded = Ka != K                                            # neither a prepared copy nor fp16 x 2 serves a zero-padded a
     fl, a_scales, ws = _linear_call(int(flags or 0) | (NPI_GEMM_A_ZERO_PADDED if padded else 0), reserve_cus, a_scales,
@@ -384,7 +393,7 @@ def linear_bwd_data(dc: torch.Tensor, weight: torch.Tensor,
     weight = _fc(weight, "weight", dc)
     M, N = dc.shape
     K = weight.size(0)
-    da = _linear_out(out, M, K, dc, "linear_bwd_data")
+    da = _out_or_new(out, M, K, dc, "linear_bwd_data")
     _check_scales(dc_scales, M, "linear_bwd_data")
     fl, dc_scales, ws = _linear_call(flags, reserve_cus, dc_scales, ws, f16_ok=dc.dtype == torch.float32, K=K, N=N, dev=dev,
                                      what="linear_bwd_data")
@@ -1597,14 +1606,8 @@ def _gat_aggregate(graph, side, x, H, C, a_dst, a_src, m, s, slope, by_source, b
     """``x2``: second part of a two-part table (see ``segsum``); ``out``: write into this ``[n_rows, H C]`` buffer."""
     dev = x.device
     x = _f32c(x, "x")
-    if x2 is not None:
-        x2 = _f32c(x2, "x2")
-        if x2.stride(0) != x.stride(0):
-            raise ValueError("the two parts of the table must share the row pitch")
-    if out is None:
-        out = torch.empty((side.n_rows, H * C), dtype=torch.float32, device=dev)
-    else:
-        _check_out(out, side.n_rows, H * C, x, "gat_aggregate")
+    x2 = _second_part(x2, x, "x2")
+    out = _out_or_new(out, side.n_rows, H * C, x, "gat_aggregate")
     check(load().npi_gat_aggregate_ex(ptr(side.rowptr), ptr(side.col), ptr(side.item_row), side.item, side.n_rows, side.nnz_max,
                                       ptr(x), x.stride(0), ptr(x2), x.size(0) if x2 is not None else 0,
                                       ptr(out), out.stride(0), H, C, ptr(a_dst), ptr(a_src),
@@ -1684,14 +1687,8 @@ def gat_aggregate_scores(side: CSRSide, table, table2, C, scores, m, s, bias=Non
     per-entry scores coming from ``gat_softmax_stats(..., want_scores=True)``; ``table2``: second part of a two-part table."""
     dev = table.device
     table = _f32c(table, "table")
-    if table2 is not None:
-        table2 = _f32c(table2, "table2")
-        if table2.stride(0) != table.stride(0):
-            raise ValueError("the two parts of the table must share the row pitch")
-    if out is None:
-        out = torch.empty((side.n_rows, C), dtype=torch.float32, device=dev)
-    else:
-        _check_out(out, side.n_rows, C, table, "gat_aggregate_scores")
+    table2 = _second_part(table2, table, "table2")
+    out = _out_or_new(out, side.n_rows, C, table, "gat_aggregate_scores")
     if side.nnz_max == 0:
         out = out.zero_() if bias is None else out.copy_(bias.view(1, -1).expand_as(out))
         return out.clamp_(min=0) if relu else out
@@ -1716,14 +1713,8 @@ def gat_aggregate_fused(side: CSRSide, table, table2, C, a_dst, att2, slope, bia
     adds ``alpha kappa h_j``; ``m``, ``s`` stay the statistics of the undropped scores."""
     dev = table.device
     table = _f32c(table, "table")
-    if table2 is not None:
-        table2 = _f32c(table2, "table2")
-        if table2.stride(0) != table.stride(0):
-            raise ValueError("the two parts of the table must share the row pitch")
-    if out is None:
-        out = torch.empty((side.n_rows, H * C), dtype=torch.float32, device=dev)
-    else:
-        _check_out(out, side.n_rows, H * C, table, "gat_aggregate_fused")
+    table2 = _second_part(table2, table, "table2")
+    out = _out_or_new(out, side.n_rows, H * C, table, "gat_aggregate_fused")
     m = torch.empty((side.n_rows, H), dtype=torch.float32, device=dev)
     s = torch.empty((side.n_rows, H), dtype=torch.float32, device=dev)
     lib = load()
@@ -1764,15 +1755,9 @@ def gat_backward_fused_packed(side: CSRSide, dout, dout2, hrow, C, tpack, a_src_
     ``dz = alpha (kappa <dOut_i, h_j> - D_i) leaky_relu'``."""
     dev = dout.device
     dout = _f32c(dout, "dout")
-    if dout2 is not None:
-        dout2 = _f32c(dout2, "dout2")
-        if dout2.stride(0) != dout.stride(0):
-            raise ValueError("the two parts of the table must share the row pitch")
+    dout2 = _second_part(dout2, dout, "dout2")
     hrow = _f32c(hrow, "hrow")
-    if out is None:
-        out = torch.empty((side.n_rows, H * C), dtype=torch.float32, device=dev)
-    else:
-        _check_out(out, side.n_rows, H * C, dout, "gat_backward_fused_packed")
+    out = _out_or_new(out, side.n_rows, H * C, dout, "gat_backward_fused_packed")
     dz = torch.empty(max(side.nnz_max, 1) * H, dtype=torch.float32, device=dev)
     if rowsum_out is not None and (H != 1 or rowsum_out.numel() != side.n_rows or rowsum_out.dtype != torch.float32
                                    or not rowsum_out.is_contiguous()):
@@ -1814,10 +1799,7 @@ def gat_edge_grad(side: CSRSide, col_feat, col_feat2, row_feat, H, C, a_dst, a_s
     dev = row_feat.device
     dz = torch.empty((max(side.nnz_max, 1), H), dtype=torch.float32, device=dev)
     col_feat = _f32c(col_feat, "col_feat")
-    if col_feat2 is not None:
-        col_feat2 = _f32c(col_feat2, "col_feat2")
-        if col_feat2.stride(0) != col_feat.stride(0):
-            raise ValueError("the two parts of the table must share the row pitch")
+    col_feat2 = _second_part(col_feat2, col_feat, "col_feat2")
     lib = load()
     fn, extra = (lib.npi_gat_edge_grad_ex, ()) if dropout is None else (lib.npi_gat_edge_grad_dropout, dropout.args(side))
     check(fn(ptr(side.rowptr), ptr(side.col), ptr(side.rowidx), side.n_rows, side.nnz_max,

@@ -105,6 +105,48 @@ def test_fused_heads_two_part_table_is_bit_equal(dev):
         assert torch.equal(a, b)
 
 
+def test_two_part_table_is_bit_equal_in_the_other_wrappers(dev):
+    """The second part of the table through the wrappers the fused launches above do not cover: ``_gat_aggregate`` by target and by
+    source, ``gat_aggregate_scores`` and ``gat_edge_grad`` in both orientations.  The same kernel adds the same entries in the same
+    order -- only the address of a gathered row differs -- so the result is bit equal to the call with the whole table."""
+    N, E, k = 600, 8000, 250
+    g = torch.Generator().manual_seed(3)
+    graph = npi.CSRGraph(torch.randint(0, N, (2, E), generator=g).to(dev), N)
+    d, sr = graph.by_dst, graph.by_src
+
+    def operands(H, C):
+        h, dout = torch.randn(N, H * C, generator=g).to(dev), torch.randn(N, H * C, generator=g).to(dev)
+        att = (torch.randn(H, 2 * C, generator=g) / C ** 0.5).to(dev)
+        a_dst, a_src = NF.gat_scores(h, att, H, C)
+        return h, dout, a_dst, a_src
+
+    H, C = 3, 16
+    h, dout, a_dst, a_src = operands(H, C)
+    m, s = NF.gat_softmax_stats(d, a_dst, a_src, H, 0.2)
+    for side, table, by_source in ((d, h, False), (sr, dout, True)):
+        one = NF._gat_aggregate(graph, side, table, H, C, a_dst, a_src, m, s, 0.2, by_source)
+        two = NF._gat_aggregate(graph, side, table[:k], H, C, a_dst, a_src, m, s, 0.2, by_source, x2=table[k:])
+        assert torch.equal(one, two), by_source
+
+    H, C = 1, 64
+    h, _, a_dst, a_src = operands(H, C)
+    bias = torch.randn(C, generator=g).to(dev)
+    m, s, sc = NF.gat_softmax_stats(d, a_dst, a_src, H, 0.2, want_scores=True)
+    one = NF.gat_aggregate_scores(d, h, None, C, sc, m, s, bias=bias, relu=True)
+    two = NF.gat_aggregate_scores(d, h[:k], h[k:], C, sc, m, s, bias=bias, relu=True)
+    assert torch.equal(one, two)
+
+    H, C = 2, 32
+    h, dout, a_dst, a_src = operands(H, C)
+    m, s = NF.gat_softmax_stats(d, a_dst, a_src, H, 0.2)
+    D = torch.randn(N, H, generator=g).to(dev)
+    for side, table, rows, swap in ((d, h, dout, 0), (sr, dout, h, 1)):
+        nnz = int(side.rowptr[-1])
+        one = NF.gat_edge_grad(side, table, None, rows, H, C, a_dst, a_src, m, s, D, 0.2, swap)
+        two = NF.gat_edge_grad(side, table[:k], table[k:], rows, H, C, a_dst, a_src, m, s, D, 0.2, swap)
+        assert nnz > 0 and torch.equal(one[:nnz], two[:nnz]), swap
+
+
 def test_four_heads_take_the_fused_launch(dev, monkeypatch):
     """With the statistics pass made to raise, the 4 x 64 layer still runs its forward (one-id-space and pair form); with
     Schedule(gat_fused_stats=False) the statistics pass is reached."""
